@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""bench.py -- ECG iterations/s on MI355X (+ SpMM roofline, + CPU baseline, + parity line).
+"""bench.py -- ECG iterations/s on MI355X (--full: + SpMM roofline, + CPU baseline, + parity line).
 
 Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line (rank 0).
 With --gpus N > 1 and no launcher environment (RANK unset) the script starts its own N
@@ -15,11 +15,18 @@ libprealps_hip.so.  Default workload = what BASELINE.json's metric is quoted on:
 nnz = 80,990,208), t = 4, block-Jacobi, fp64, inputs resident in HBM before the
 timed region.  `--workload poisson` runs BASELINE configs[1] (7-pt Poisson 100^3).  If the
 solve converges inside the timed region it is restarted from the same rhs (the restart is
-inside the timing).  After the timed region: the SpMM against the HBM roofline (HIP events on
-the library stream), the per-phase device times of the iteration in the layout of
-examples/test_ecg_bench_fused.c:300-336 (stderr + `phases`), and -- rank 0, N = 1 -- the CPU
-ports on a bounded sample with the parity line of BASELINE.md section 3 (max relative
-difference of the first residuals, GPU vs CPU oracle).
+inside the timing).
+
+A plain run sets up, warms up, times the steps and prints the line: `value` = iterations/s,
+`ms_per_step` = wall milliseconds of one timed step.  `--dump-outputs DIR` writes, after the timed
+steps, what the timed path left behind in its last step (dump_outputs below) as DIR/<name>.npy.
+
+`--full` adds everything else, after the timed region: the SpMM against the HBM roofline (HIP events
+on the library stream), the per-phase device times of the iteration in the layout of
+examples/test_ecg_bench_fused.c:300-336 (stderr + `phases`), the block solve's figures, and -- rank 0,
+N = 1 -- the CPU ports on a bounded sample with the parity line of BASELINE.md section 3 (max relative
+difference of the first residuals, GPU vs CPU oracle) and the same problem at the survey's subdomain
+count (`survey_nparts`).
 """
 import argparse
 import ctypes as C
@@ -101,7 +108,44 @@ def parse():
     ap.add_argument("--survey-nparts", type=int, default=64,
                     help="also time the same problem cut into this many cubic subdomains (SURVEY 8d asks for 64: the "
                          "reference's one large block per rank); 0 skips it")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the phases, the SpMM / block-solve rooflines, the CPU "
+                         "baselines with the parity line and the survey's subdomain count (the options above that "
+                         "tune these passes only matter with --full)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="write what the timed path computed in its last step to DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+# what --dump-outputs may write in all (split evenly between the ranks)
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(d, prob, e, t, rank, world):
+    """What a caller of the timed path (preAlps_ECGAdvance) holds after its last step, as float64 .npy files:
+    X and R, the m x t block iterate and block residual; x = X 1, the solution preAlps_ECGFinalize would
+    return; res, the residual norm of the stopping test.  Nothing here changes the solver's state.  If the
+    rows do not fit the budget, the same fixed, seeded sample of rows is written for x, X and R, and its row
+    indices as `rows`.  Several ranks: each writes its own rows, with a `_rank<r>` suffix."""
+    X = np.ascontiguousarray(prob.to_host(e.X.contents, t))
+    R = np.ascontiguousarray(prob.to_host(e.R.contents, t))
+    arrays = {"x": X.sum(axis=1), "X": X, "R": R}
+    m = X.shape[0]
+    per_row = 8 * (1 + X.shape[1] + R.shape[1])
+    budget = DUMP_BUDGET_BYTES // world - 4096
+    if m * per_row > budget:
+        k = budget // (per_row + 8)
+        rows = np.sort(np.random.default_rng(12345).choice(m, size=k, replace=False))
+        arrays = {name: v[rows] for name, v in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    arrays["res"] = np.array([e.res], dtype=np.float64)
+    os.makedirs(d, exist_ok=True)
+    suffix = "_rank%d" % rank if world > 1 else ""
+    for name, v in arrays.items():
+        np.save(os.path.join(d, name + suffix + ".npy"), np.asarray(v, dtype=np.float64))
 
 
 def launch_ranks(a):
@@ -252,113 +296,117 @@ def main():
         dt = float(tt.item())
     its = a.steps / dt
 
-    # ---- the same loop phase by phase: hipEvent pairs around every phase (one stream sync each,
-    #      so this is a separate, slower pass), accumulated by the library and in preAlps_ECG_t
-    phases, ecg_fields = {}, {}
-    if a.phase_iters > 0:
-        for k in ("tot_t", "comm_t", "trsm_t", "gemm_t", "potrf_t", "copy_t"):
-            setattr(e, k, 0.0)
-        L.preAlps_hip_timing(1)
-        L.preAlps_hip_timing_reset()
-        barrier()
-        tp0 = time.perf_counter()
-        run_iterations(prob, e, rhs, L, a.phase_iters, state)
-        barrier()
-        phases["total"] = time.perf_counter() - tp0
-        L.preAlps_hip_timing(0)
-        sec = C.c_double()
-        for k in PHASE_KEYS:
-            L.preAlps_hip_get_time(k.encode(), C.byref(sec))
-            phases[k] = sec.value
-        ecg_fields = {k: getattr(e, k) for k in ("tot_t", "comm_t", "trsm_t", "gemm_t", "potrf_t", "pstrf_t",
-                                                 "lapmt_t", "gesvd_t", "geqrf_t", "ormqr_t", "copy_t")}
-        if distributed:   # MPI_Allreduce(MAX) of the reference's report
-            keys = sorted(phases)
-            tt = torch.tensor([phases[k] for k in keys], dtype=torch.float64, device="cuda")
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            phases = dict(zip(keys, [float(v) for v in tt.tolist()]))
+    if a.dump_outputs:      # the solver's state after the last timed step, before anything else runs
+        dump_outputs(a.dump_outputs, prob, e, a.t, rank, world)
 
-    # ---- dominant kernel (SpMM) against the HBM roofline: HIP events on the library stream
     m_loc, nnz_loc = int(prob.stat("rows_local")), int(prob.stat("nnz_local"))
     halo = int(prob.stat("halo_rows"))
-    sec = C.c_double()
-    # (a) in context: between two SpMM launches of the solver lies a whole iteration that streams the
-    #     block-Jacobi factors and seven panels through the 256 MiB Infinity Cache, so each timed launch
-    #     here is preceded by one (untimed) preconditioner apply; one event pair per launch.
-    tot = 0.0
-    gram0 = prob.stat("spmm_gram_launches")
-    for _ in range(a.spmm_reps):
-        check(L.preAlps_BlockJacobiApply(e.AP, e.Z), "BlockJacobiApply")
+    phases, ecg_fields = {}, {}
+    if a.full:
+        # ---- the same loop phase by phase: hipEvent pairs around every phase (one stream sync each,
+        #      so this is a separate, slower pass), accumulated by the library and in preAlps_ECG_t
+        if a.phase_iters > 0:
+            for k in ("tot_t", "comm_t", "trsm_t", "gemm_t", "potrf_t", "copy_t"):
+                setattr(e, k, 0.0)
+            L.preAlps_hip_timing(1)
+            L.preAlps_hip_timing_reset()
+            barrier()
+            tp0 = time.perf_counter()
+            run_iterations(prob, e, rhs, L, a.phase_iters, state)
+            barrier()
+            phases["total"] = time.perf_counter() - tp0
+            L.preAlps_hip_timing(0)
+            sec = C.c_double()
+            for k in PHASE_KEYS:
+                L.preAlps_hip_get_time(k.encode(), C.byref(sec))
+                phases[k] = sec.value
+            ecg_fields = {k: getattr(e, k) for k in ("tot_t", "comm_t", "trsm_t", "gemm_t", "potrf_t", "pstrf_t",
+                                                     "lapmt_t", "gesvd_t", "geqrf_t", "ormqr_t", "copy_t")}
+            if distributed:   # MPI_Allreduce(MAX) of the reference's report
+                keys = sorted(phases)
+                tt = torch.tensor([phases[k] for k in keys], dtype=torch.float64, device="cuda")
+                dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+                phases = dict(zip(keys, [float(v) for v in tt.tolist()]))
+
+        # ---- dominant kernel (SpMM) against the HBM roofline: HIP events on the library stream
+        sec = C.c_double()
+        # (a) in context: between two SpMM launches of the solver lies a whole iteration that streams the
+        #     block-Jacobi factors and seven panels through the 256 MiB Infinity Cache, so each timed launch
+        #     here is preceded by one (untimed) preconditioner apply; one event pair per launch.
+        tot = 0.0
+        gram0 = prob.stat("spmm_gram_launches")
+        for _ in range(a.spmm_reps):
+            check(L.preAlps_BlockJacobiApply(e.AP, e.Z), "BlockJacobiApply")
+            check(L.preAlps_hip_timer_start(), "timer_start")
+            check(L.preAlps_BlockOperator(e.P, e.AP), "BlockOperator")
+            check(L.preAlps_hip_timer_stop(C.byref(sec)), "timer_stop")
+            tot += sec.value
+        spmm_s = tot / a.spmm_reps
+        # The product P -> AP of the solver also leaves the Gram block [AP | R]^T P behind (k_spmm_runs_gram, the
+        # default at t = 4): it reads the m x t rows of R on top of the product's bytes.  The request is made by the
+        # solver's own loop (preAlps_ECGIterate), so the stand-alone launches above are the PLAIN product; the
+        # solver's launch is timed where it happens -- the hipEvent pair of the library's `operator` phase, one pair
+        # per iteration of the phase-by-phase pass, same stream, same cache state by construction.
+        with_gram = bool(solver_forms_gram) and phases.get("operator", 0.0) > 0.0 and a.phase_iters > 0
+        plain_s = None
+        dx, dy = prob.panel(a.t, a.t), prob.panel(a.t, a.t)
+        prob.to_device(dx, np.random.default_rng(1).standard_normal((m_loc, a.t)), a.t)
+        if with_gram:
+            plain_s = spmm_s
+            spmm_s = phases["operator"] / a.phase_iters
+        # (b) back to back (matrix partly resident in the Infinity Cache): reported for comparison only
         check(L.preAlps_hip_timer_start(), "timer_start")
-        check(L.preAlps_BlockOperator(e.P, e.AP), "BlockOperator")
+        for _ in range(a.spmm_reps):
+            check(L.preAlps_BlockOperator(e.P, e.AP), "BlockOperator")
         check(L.preAlps_hip_timer_stop(C.byref(sec)), "timer_stop")
-        tot += sec.value
-    spmm_s = tot / a.spmm_reps
-    # The product P -> AP of the solver also leaves the Gram block [AP | R]^T P behind (k_spmm_runs_gram, the
-    # default at t = 4): it reads the m x t rows of R on top of the product's bytes.  The request is made by the
-    # solver's own loop (preAlps_ECGIterate), so the stand-alone launches above are the PLAIN product; the
-    # solver's launch is timed where it happens -- the hipEvent pair of the library's `operator` phase, one pair
-    # per iteration of the phase-by-phase pass, same stream, same cache state by construction.
-    with_gram = bool(solver_forms_gram) and phases.get("operator", 0.0) > 0.0 and a.phase_iters > 0
-    plain_s = None
-    dx, dy = prob.panel(a.t, a.t), prob.panel(a.t, a.t)
-    prob.to_device(dx, np.random.default_rng(1).standard_normal((m_loc, a.t)), a.t)
-    if with_gram:
-        plain_s = spmm_s
-        spmm_s = phases["operator"] / a.phase_iters
-    # (b) back to back (matrix partly resident in the Infinity Cache): reported for comparison only
-    check(L.preAlps_hip_timer_start(), "timer_start")
-    for _ in range(a.spmm_reps):
-        check(L.preAlps_BlockOperator(e.P, e.AP), "BlockOperator")
-    check(L.preAlps_hip_timer_stop(C.byref(sec)), "timer_stop")
-    spmm_b2b_s = sec.value / a.spmm_reps
-    # 12 B per nonzero + 4 B per row pointer + read X + write AX (8*t B per row each)
-    spmm_bytes = 12.0 * nnz_loc + 4.0 * (m_loc + 1) + 8.0 * (m_loc + halo) * a.t + 8.0 * m_loc * a.t
-    plain_bytes = spmm_bytes
-    if with_gram:
-        spmm_bytes += 8.0 * m_loc * a.t + 256.0 * prob.stat("spmm_blocks")     # rows of R read, one 8 x 4 block per workgroup written
-    spmm_gbs = spmm_bytes / spmm_s / 1e9
-    # block-Jacobi apply, same stopwatch
-    bjg0 = prob.stat("bj_gram_applies")
-    check(L.preAlps_hip_timer_start(), "timer_start")
-    for _ in range(a.spmm_reps):
-        check(L.preAlps_BlockJacobiApply(e.AP, e.Z), "BlockJacobiApply")
-    check(L.preAlps_hip_timer_stop(C.byref(sec)), "timer_stop")
-    bj_solver_s = sec.value / a.spmm_reps
-    bj_with_gram = prob.stat("bj_gram_applies") > bjg0
-    # the solver's own apply AP -> Z also forms [AP | AP_prev]^T Z (requested by its loop, not by these stand-alone
-    # calls): timed where it happens, the hipEvent pair of the library's `precond` phase
-    if solver_bj_forms_gram and a.phase_iters > 0 and phases.get("precond", 0.0) > 0.0:
-        bj_solver_s = phases["precond"] / a.phase_iters
-        bj_with_gram = True
-    # the block solve alone (other panels): this is the kernel the roofline figures below are about
-    check(L.preAlps_hip_timer_start(), "timer_start")
-    for _ in range(a.spmm_reps):
-        check(L.preAlps_BlockJacobiApply(C.byref(dx), C.byref(dy)), "BlockJacobiApply")
-    check(L.preAlps_hip_timer_stop(C.byref(sec)), "timer_stop")
-    bj_s = sec.value / a.spmm_reps
-    prob.panel_free(dx); prob.panel_free(dy)
-    bj_bytes = prob.stat("bj_factor_bytes") + 16.0 * m_loc * a.t + 8.0 * m_loc
-    # streaming ceilings of this very device (calibration kernels of the library, 1 GiB buffers)
-    copy_gbs, read_gbs = C.c_double(), C.c_double()
-    check(L.preAlps_hip_hbm_probe(1 << 30, 20, C.byref(copy_gbs), C.byref(read_gbs)), "hbm_probe")
-    # HBM bytes per launch from the rocprofv3 PMC passes of this same command (profiles/): the
-    # counters cannot be read from inside the process, so the committed summary is quoted when
-    # the workload is the one it was collected on.
-    traffic, traffic_src, bj_traffic = None, None, None
-    profiled = {("elasticity", 70, 4, "2,4,8"): "pmc_hbm_traffic_elasticity.json",
-                ("poisson", 100, 4, "5,5,10"): "pmc_hbm_traffic_poisson.json"}
-    pmc = profiled.get((a.workload, a.n, a.t, a.box)) if a.nparts == 0 else None
-    if world == 1 and pmc:
-        for rnd in (ROUND, "r03", "r01"):
-            path = os.path.join(ROOT, "profiles", "%s_%s" % (rnd, pmc))
-            if os.path.exists(path):
-                with open(path) as f:
-                    pmc_doc = json.load(f)
-                traffic = pmc_doc["k_spmm"]["traffic_bytes_per_launch"]
-                bj_traffic = (pmc_doc.get("k_bj") or {}).get("traffic_bytes_per_launch")
-                traffic_src = "profiles/%s_%s (2*FETCH_SIZE + WRITE_SIZE, KiB -> bytes)" % (rnd, pmc)
-                break
+        spmm_b2b_s = sec.value / a.spmm_reps
+        # 12 B per nonzero + 4 B per row pointer + read X + write AX (8*t B per row each)
+        spmm_bytes = 12.0 * nnz_loc + 4.0 * (m_loc + 1) + 8.0 * (m_loc + halo) * a.t + 8.0 * m_loc * a.t
+        plain_bytes = spmm_bytes
+        if with_gram:
+            spmm_bytes += 8.0 * m_loc * a.t + 256.0 * prob.stat("spmm_blocks")     # rows of R read, one 8 x 4 block per workgroup written
+        spmm_gbs = spmm_bytes / spmm_s / 1e9
+        # block-Jacobi apply, same stopwatch
+        bjg0 = prob.stat("bj_gram_applies")
+        check(L.preAlps_hip_timer_start(), "timer_start")
+        for _ in range(a.spmm_reps):
+            check(L.preAlps_BlockJacobiApply(e.AP, e.Z), "BlockJacobiApply")
+        check(L.preAlps_hip_timer_stop(C.byref(sec)), "timer_stop")
+        bj_solver_s = sec.value / a.spmm_reps
+        bj_with_gram = prob.stat("bj_gram_applies") > bjg0
+        # the solver's own apply AP -> Z also forms [AP | AP_prev]^T Z (requested by its loop, not by these stand-alone
+        # calls): timed where it happens, the hipEvent pair of the library's `precond` phase
+        if solver_bj_forms_gram and a.phase_iters > 0 and phases.get("precond", 0.0) > 0.0:
+            bj_solver_s = phases["precond"] / a.phase_iters
+            bj_with_gram = True
+        # the block solve alone (other panels): this is the kernel the roofline figures below are about
+        check(L.preAlps_hip_timer_start(), "timer_start")
+        for _ in range(a.spmm_reps):
+            check(L.preAlps_BlockJacobiApply(C.byref(dx), C.byref(dy)), "BlockJacobiApply")
+        check(L.preAlps_hip_timer_stop(C.byref(sec)), "timer_stop")
+        bj_s = sec.value / a.spmm_reps
+        prob.panel_free(dx); prob.panel_free(dy)
+        bj_bytes = prob.stat("bj_factor_bytes") + 16.0 * m_loc * a.t + 8.0 * m_loc
+        # streaming ceilings of this very device (calibration kernels of the library, 1 GiB buffers)
+        copy_gbs, read_gbs = C.c_double(), C.c_double()
+        check(L.preAlps_hip_hbm_probe(1 << 30, 20, C.byref(copy_gbs), C.byref(read_gbs)), "hbm_probe")
+        # HBM bytes per launch from the rocprofv3 PMC passes of this same command (profiles/): the
+        # counters cannot be read from inside the process, so the committed summary is quoted when
+        # the workload is the one it was collected on.
+        traffic, traffic_src, bj_traffic = None, None, None
+        profiled = {("elasticity", 70, 4, "2,4,8"): "pmc_hbm_traffic_elasticity.json",
+                    ("poisson", 100, 4, "5,5,10"): "pmc_hbm_traffic_poisson.json"}
+        pmc = profiled.get((a.workload, a.n, a.t, a.box)) if a.nparts == 0 else None
+        if world == 1 and pmc:
+            for rnd in (ROUND, "r03", "r01"):
+                path = os.path.join(ROOT, "profiles", "%s_%s" % (rnd, pmc))
+                if os.path.exists(path):
+                    with open(path) as f:
+                        pmc_doc = json.load(f)
+                    traffic = pmc_doc["k_spmm"]["traffic_bytes_per_launch"]
+                    bj_traffic = (pmc_doc.get("k_bj") or {}).get("traffic_bytes_per_launch")
+                    traffic_src = "profiles/%s_%s (2*FETCH_SIZE + WRITE_SIZE, KiB -> bytes)" % (rnd, pmc)
+                    break
     halo_rows = [halo]
     if distributed:
         halo_rows = [None] * world
@@ -379,53 +427,58 @@ def main():
                    "setup_breakdown_s": {k: prob.stat("setup_" + k + "_s") for k in ("build", "plan", "bj_factor", "bj_layout")},
                    "bj_max_bandwidth": int(prob.stat("bj_max_bandwidth")),
                    "spmm_blocks": int(prob.stat("spmm_blocks"))},
-        "roofline": {"kernel": ("k_spmm_runs_gram<3>" if prob.stat("spmm_runs") else ("k_spmm_runs_gram<1>" if prob.stat("spmm_staged") else "k_spmm_gram")) if with_gram else ("k_spmm_runs<.,.,3>" if prob.stat("spmm_runs") else ("k_spmm_runs<.,.,1>" if prob.stat("spmm_staged") else "k_spmm")), "bound": "hbm", "achieved": spmm_gbs, "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": spmm_gbs / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                     "algorithmic_bytes_per_launch": spmm_bytes, "avg_launch_us": 1e6 * spmm_s,
-                     "back_to_back_launch_us": 1e6 * spmm_b2b_s,
-                     "measured_copy_ceiling_GBs": copy_gbs.value, "measured_read_ceiling_GBs": read_gbs.value,
-                     # what the kernel really moves (PMC traffic of the committed profile) over this launch's time, against
-                     # what a plain read kernel streams on this very device: the honest distance to the ceiling.  (The
-                     # algorithmic bytes count 12 B per nonzero where the kernel reads 8.67, so they may exceed it.)
-                     "traffic_GBs": None if traffic is None else traffic / spmm_s / 1e9,
-                     "traffic_frac_of_measured_read_ceiling": None if traffic is None else traffic / spmm_s / 1e9 / read_gbs.value,
-                     "algorithmic_over_measured_read_ceiling": spmm_gbs / read_gbs.value,
-                     "plain_product": None if plain_s is None else {
-                         "kernel": "k_spmm_runs" if (prob.stat("spmm_runs") or prob.stat("spmm_staged")) else "k_spmm", "avg_launch_us": 1e6 * plain_s, "algorithmic_bytes_per_launch": plain_bytes,
-                         "achieved": plain_bytes / plain_s / 1e9, "frac": plain_bytes / plain_s / 1e9 / HBM_PEAK_GBS,
-                         "note": "the same product without the Gram block, stand-alone launches behind one block solve each (what rounds 1-2 reported)"},
-                     "note": ("the solver's own launches: hipEvent pair of the `operator` phase, one per iteration of the phase-by-phase pass; "
-                              "the product also forms [AP | R]^T P (rows of R counted in the bytes; `traffic` is the PMC figure of this kernel)"
-                              if with_gram else "each timed launch follows one preconditioner apply (cache state of the solver loop)")},
-        "block_jacobi": {"avg_apply_us": 1e6 * bj_s, "solver_apply_us": 1e6 * bj_solver_s, "solver_apply_forms_gram_block": bool(bj_with_gram),
-                         "factor_bytes": prob.stat("bj_factor_bytes"),
-                         "traffic": bj_traffic, "frac": bj_bytes / bj_s / 1e9 / HBM_PEAK_GBS,
-                         "achieved_GBs": bj_bytes / bj_s / 1e9,
-                         # panels of up to 4 columns: ONE stored copy of the band (bj_g4.hip), streamed once by each of
-                         # the two sweeps; else the paired copy of both sweeps' records, or the plain two copies
-                         "streamed_record_bytes": (2.0 * prob.stat("bj_g4_bytes") if a.t <= 4 and prob.stat("bj_g4_bytes") > 0 else
-                                                   prob.stat("bj_pairs_bytes") if a.t <= 4 and prob.stat("bj_pairs_bytes") > 0
-                                                   else prob.stat("bj_factor_bytes")),
-                         "stored_record_bytes": (prob.stat("bj_g4_bytes") if a.t <= 4 and prob.stat("bj_g4_bytes") > 0 else
-                                                 prob.stat("bj_factor_bytes")),
-                         "streamed_GBs": ((2.0 * prob.stat("bj_g4_bytes") if a.t <= 4 and prob.stat("bj_g4_bytes") > 0 else
-                                           prob.stat("bj_factor_bytes")) + 16.0 * m_loc * a.t) / bj_s / 1e9,
-                         "note": "achieved_GBs counts the plain two-sweep factor of SURVEY 8(d) (algorithmic bytes) + the "
-                                 "panels; streamed_GBs what the kernel really reads and writes; avg_apply_us = the block solve on "
-                                 "panels of its own, solver_apply_us = the solver's AP -> Z, which also reads AP again and AP_prev "
-                                 "for the Gram block beta (16 B x t per row more; the PMC traffic averages both kinds of launch)"},
-        "phases": {"iterations": a.phase_iters, "device_us_per_iteration": per_it,
-                   "ecg_struct_timers_s": ecg_fields,
-                   "note": "hipEvent pairs per phase (max over ranks); dense = gram + trsm + update + small; the pass "
-                           "syncs after every phase, so its total is above ms_per_step"},
     }
+    if a.full:
+        out.update({
+            "roofline": {"kernel": ("k_spmm_runs_gram<3>" if prob.stat("spmm_runs") else ("k_spmm_runs_gram<1>" if prob.stat("spmm_staged") else "k_spmm_gram")) if with_gram else ("k_spmm_runs<.,.,3>" if prob.stat("spmm_runs") else ("k_spmm_runs<.,.,1>" if prob.stat("spmm_staged") else "k_spmm")), "bound": "hbm", "achieved": spmm_gbs, "peak": HBM_PEAK_GBS,
+                         "unit": "GB/s", "frac": spmm_gbs / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                         "algorithmic_bytes_per_launch": spmm_bytes, "avg_launch_us": 1e6 * spmm_s,
+                         "back_to_back_launch_us": 1e6 * spmm_b2b_s,
+                         "measured_copy_ceiling_GBs": copy_gbs.value, "measured_read_ceiling_GBs": read_gbs.value,
+                         # what the kernel really moves (PMC traffic of the committed profile) over this launch's time, against
+                         # what a plain read kernel streams on this very device: the honest distance to the ceiling.  (The
+                         # algorithmic bytes count 12 B per nonzero where the kernel reads 8.67, so they may exceed it.)
+                         "traffic_GBs": None if traffic is None else traffic / spmm_s / 1e9,
+                         "traffic_frac_of_measured_read_ceiling": None if traffic is None else traffic / spmm_s / 1e9 / read_gbs.value,
+                         "algorithmic_over_measured_read_ceiling": spmm_gbs / read_gbs.value,
+                         "plain_product": None if plain_s is None else {
+                             "kernel": "k_spmm_runs" if (prob.stat("spmm_runs") or prob.stat("spmm_staged")) else "k_spmm", "avg_launch_us": 1e6 * plain_s, "algorithmic_bytes_per_launch": plain_bytes,
+                             "achieved": plain_bytes / plain_s / 1e9, "frac": plain_bytes / plain_s / 1e9 / HBM_PEAK_GBS,
+                             "note": "the same product without the Gram block, stand-alone launches behind one block solve each (what rounds 1-2 reported)"},
+                         "note": ("the solver's own launches: hipEvent pair of the `operator` phase, one per iteration of the phase-by-phase pass; "
+                                  "the product also forms [AP | R]^T P (rows of R counted in the bytes; `traffic` is the PMC figure of this kernel)"
+                                  if with_gram else "each timed launch follows one preconditioner apply (cache state of the solver loop)")},
+            "block_jacobi": {"avg_apply_us": 1e6 * bj_s, "solver_apply_us": 1e6 * bj_solver_s, "solver_apply_forms_gram_block": bool(bj_with_gram),
+                             "factor_bytes": prob.stat("bj_factor_bytes"),
+                             "traffic": bj_traffic, "frac": bj_bytes / bj_s / 1e9 / HBM_PEAK_GBS,
+                             "achieved_GBs": bj_bytes / bj_s / 1e9,
+                             # panels of up to 4 columns: ONE stored copy of the band (bj_g4.hip), streamed once by each of
+                             # the two sweeps; else the paired copy of both sweeps' records, or the plain two copies
+                             "streamed_record_bytes": (2.0 * prob.stat("bj_g4_bytes") if a.t <= 4 and prob.stat("bj_g4_bytes") > 0 else
+                                                       prob.stat("bj_pairs_bytes") if a.t <= 4 and prob.stat("bj_pairs_bytes") > 0
+                                                       else prob.stat("bj_factor_bytes")),
+                             "stored_record_bytes": (prob.stat("bj_g4_bytes") if a.t <= 4 and prob.stat("bj_g4_bytes") > 0 else
+                                                     prob.stat("bj_factor_bytes")),
+                             "streamed_GBs": ((2.0 * prob.stat("bj_g4_bytes") if a.t <= 4 and prob.stat("bj_g4_bytes") > 0 else
+                                               prob.stat("bj_factor_bytes")) + 16.0 * m_loc * a.t) / bj_s / 1e9,
+                             "note": "achieved_GBs counts the plain two-sweep factor of SURVEY 8(d) (algorithmic bytes) + the "
+                                     "panels; streamed_GBs what the kernel really reads and writes; avg_apply_us = the block solve on "
+                                     "panels of its own, solver_apply_us = the solver's AP -> Z, which also reads AP again and AP_prev "
+                                     "for the Gram block beta (16 B x t per row more; the PMC traffic averages both kinds of launch)"},
+            "phases": {"iterations": a.phase_iters, "device_us_per_iteration": per_it,
+                       "ecg_struct_timers_s": ecg_fields,
+                       "note": "hipEvent pairs per phase (max over ranks); dense = gram + trsm + update + small; the pass "
+                               "syncs after every phase, so its total is above ms_per_step"},
+        })
     if a.shard_of > 1:
         kern = sum(per_it.get(k, 0.0) for k in PHASE_KEYS)
         out["scaling"] = "rehearsal"
         out["shard"] = {"of": a.shard_of, "rank": a.shard, "rows": m_loc, "nnz": nnz_loc, "halo_rows": halo,
                         "send_rows": int(prob.stat("send_rows")), "bj_blocks": int(prob.stat("bj_parts_local")),
                         "iteration_device_us": 1e6 * dev_s.value / a.steps,
-                        "sum_of_phase_device_us": kern, "launch_gap_us": 1e6 * dev_s.value / a.steps - kern,
+                        # (phase times come from the --full pass only)
+                        "sum_of_phase_device_us": kern if per_it else None,
+                        "launch_gap_us": 1e6 * dev_s.value / a.steps - kern if per_it else None,
                         "halo_overlap": os.environ.get("PREALPS_HALO_OVERLAP", "auto"),
                         "note": "one rank of a %d-GPU run on one GPU (preAlps_hip_loopback): its rows, SpMM plan, pack, "
                                 "exchange (main stream in front of one SpMM launch for small interiors, else side stream "
@@ -441,7 +494,7 @@ def main():
     #      a bounded sample and the FASTER one is reported: (a) oracle/ecg_oracle.c, plain C + OpenMP,
     #      one thread per group of subdomains (the reference's one-rank-per-core layout); (b) the
     #      reference's own kernels, mkl_dcsrmm + MKL PARDISO + BLAS, threaded inside one process.
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu:
         from oracle import oracle as O
         from oracle import mkl_path as M
         import scipy.sparse as sp
@@ -493,7 +546,7 @@ def main():
     #      nested-dissection factors (nd.c) instead of bands.  Iterations/s there and at the tuned
     #      subdomain size are different quantities (fewer, more expensive iterations), so this goes
     #      beside the headline value, not into it.
-    if a.survey_nparts > 0 and world == 1 and a.nparts == 0:
+    if a.full and a.survey_nparts > 0 and world == 1 and a.nparts == 0:
         k = max(1, round(a.survey_nparts ** (1.0 / 3.0)))
         if k ** 3 == a.survey_nparts:
             edge = -(-a.n // k)

@@ -637,7 +637,7 @@ def test_bench_launches_its_own_ranks():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "poisson",
-                        "--n", "32", "--box", "4,4,8", "--steps", "10", "--warmup", "2", "--no-cpu",
+                        "--n", "32", "--box", "4,4,8", "--steps", "10", "--warmup", "2", "--full", "--no-cpu",
                         "--spmm-reps", "3", "--phase-iters", "4"],
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -651,6 +651,39 @@ def test_bench_launches_its_own_ranks():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], capture_output=True,
                        text=True, env=env1, timeout=120)
     assert r.returncode != 0 and "WORLD_SIZE" in (r.stderr + r.stdout)
+
+
+def test_bench_plain_run_dumps_the_timed_path_outputs(tmp_path):
+    """A plain `bench.py` run reports the headline figures only (the passes of --full stay off), times exactly
+    --steps steps, and --dump-outputs writes the solver's state after its last step: 2 warm-up + 10 timed steps
+    of a solve that needs more, so X, R and x = X 1 are those of the oracle's 12th iteration."""
+    from oracle import oracle as O
+    from prealps_amd import gen
+    n, box, t, its = 32, (4, 4, 8), 4, 12
+    d = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "poisson",
+                        "--n", str(n), "--box", "4,4,8", "--t", str(t), "--steps", "10", "--warmup", "2",
+                        "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["unit"] == "iterations/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+    assert out["steps"] == 10 and out["ms_per_step"] > 0
+    np.testing.assert_allclose(out["value"] * out["ms_per_step"], 1e3, rtol=1e-9)
+    assert not {"phases", "roofline", "block_jacobi", "parity", "cpu_baseline", "survey_nparts"} & set(out)
+    assert out["config"]["restarts_in_timed_region"] == 0
+    got = {f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))}
+    assert set(got) == {"x", "X", "R", "res"} and all(v.dtype == np.float64 for v in got.values())
+    rp, ci, v = gen.poisson3d_csr(n)
+    part, nparts = gen.box_partition(n, box)
+    A = sp.csr_matrix((v, ci, rp), shape=(n ** 3, n ** 3))
+    B, perm, rowpos = O.permute_by_part(O.symrac_scale(A), part, nparts)
+    ref = O.ECG(B, rowpos, t, max_iter=its).solve(O.reference_rhs(rowpos))
+    assert ref["iters"] == its
+    assert got["X"].shape == (n ** 3, t) and got["R"].shape == (n ** 3, t)
+    np.testing.assert_allclose(got["res"][0], ref["final_res"], rtol=1e-8)
+    np.testing.assert_allclose(np.linalg.norm(got["R"]), got["res"][0], rtol=1e-8)
+    np.testing.assert_allclose(got["X"].sum(axis=1), got["x"], rtol=1e-12, atol=1e-15)
+    np.testing.assert_allclose(got["x"], ref["x"], rtol=1e-7, atol=1e-10 * np.abs(ref["x"]).max())
 
 
 # ---- opt-in kernel variants (their switches are read once per process: run in a child) ---------------

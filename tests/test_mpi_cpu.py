@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MPIEXEC = shutil.which("mpiexec") or "/opt/conda/bin/mpiexec"
 MPI_INC, MPI_LIB = "/opt/conda/include", "/opt/conda/lib"
 have_mpi = os.path.exists(MPIEXEC) and os.path.exists(os.path.join(MPI_INC, "mpi.h"))
-REF_DRIVER = "/root/reference/examples/test_ecg_prealps_op.c"
+REF_BIN = os.path.join(ROOT, "oracle", "_ref", "test_ecg_prealps_op_mpi")
 
 
 def _cc(src, exe, extra=()):
@@ -126,16 +126,15 @@ def test_mpi_ranks_hold_their_panel_and_the_replicated_plan(tmp_path, size, npar
     assert rows_seen == n ** 3
 
 
-@pytest.mark.skipif(not (have_mpi and os.path.exists(REF_DRIVER)), reason="needs MPI and the reference tree")
+@pytest.mark.skipif(not (have_mpi and os.path.exists(REF_BIN)), reason="needs MPI and the prebuilt reference driver (oracle/Makefile)")
 def test_unmodified_reference_driver_plans_under_mpiexec(tmp_path):
-    """The reference's own driver, compiled unchanged against the system MPI, started with two ranks:
-    both ranks get through preAlps_OperatorBuild (rank and size from MPI_COMM_WORLD, panels from rank 0)
-    and then stop loudly at the first call that needs the GPU -- there is no CPU path."""
+    """The reference's own driver, compiled unchanged against the system MPI (oracle/Makefile), started with
+    two ranks: both ranks get through preAlps_OperatorBuild (rank and size from MPI_COMM_WORLD, panels from
+    rank 0) and then stop loudly at the first call that needs the GPU -- there is no CPU path."""
     rp, ci, v = gen.poisson3d_csr(8)
     mtx = str(tmp_path / "a.mtx")
     write_mtx(mtx, rp, ci, v)
-    exe = str(tmp_path / "ref_driver_mpi")
-    _cc(REF_DRIVER, exe, extra=("-I" + os.path.join(ROOT, "include", "compat"),))
+    exe = REF_BIN
     env = dict(os.environ, PREALPS_PLAN_ONLY="1", PREALPS_SETUP_TRACE="1", OMP_NUM_THREADS="2")
     r = subprocess.run([MPIEXEC, "-n", "2", exe, "-m", mtx, "-e", "2"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0

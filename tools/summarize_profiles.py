@@ -61,7 +61,7 @@ spmm_pick = next((k for k in spmm if "gram" in k), spmm[0] if spmm else None)
 bench = json.loads(open(os.path.join(out, "prof_stats_bench.json")).read().strip().splitlines()[-1])
 doc = {
     "command": "tools/profile_bench.sh: rocprofv3 --pmc FETCH_SIZE (and, separately, WRITE_SIZE) --kernel-trace "
-               "--output-format csv -- python3 bench.py --workload %s --steps 10 --warmup 2 --no-cpu --spmm-reps 10 --survey-nparts 0 --phase-iters 0" % workload,
+               "--output-format csv -- python3 bench.py --workload %s --steps 10 --warmup 2 --full --no-cpu --spmm-reps 10 --survey-nparts 0 --phase-iters 0" % workload,
     "workload": bench["config"]["workload"],
     "units": "counter values are KiB; FETCH_SIZE is doubled (gfx950 reports half of the bytes of wide coalesced "
              "reads, MI355X_MICROARCH.md HBM section); WRITE_SIZE is exact",
