@@ -120,6 +120,12 @@ int preAlps_ECGSolve(preAlps_ECG_t* ecg, double* rhs, double* sol,
 /* 1 / 0: the two driver loops above and below replay each half of an iteration from a HIP graph
  * captured on its first passes (default: off, or PREALPS_ECG_GRAPH; plain launches measured faster). */
 void preAlps_hip_graphs(int on);
+/* 1: the two driver loops run an Orthodir iteration of a solver described by the arguments with the block solve
+ * before the update of X and R (one finish and one row pass per iteration; bitwise the same results), 0: in the
+ * order of preAlps_ECGIterate.  PREALPS_ECG_SOLVE_FIRST=0 (read here as a solver reads it when it is reset) keeps
+ * the latter everywhere.  bj_gram / spmm_gram: the block solve / the SpMM can leave the Gram blocks behind. */
+int preAlps_hip_ecg_solve_first(int nprocs, int ortho_alg, int bs_red, int enlFac, int fuse, int lazy_norm,
+                                int lazy_stop, int bj_gram, int spmm_gram, int graphs);
 /* The same loop advanced by nsteps full iterations from the current RCI state,
  * restarting from rhs when the stopping test fires (counts go to the optional
  * out-parameters).  Used for timing a fixed number of iterations. */

@@ -98,6 +98,10 @@ typedef struct {
    * the residual norm, 1: preconditioner apply + second half + product -- and the panel pointers
    * rotate with period 6 (three P slots x two AP slots), so there are 2 x 6 graphs */
   int use_graphs;
+  /* solve_first: the library's own loops run an Orthodir iteration with the block solve before the update (see
+   * solve_first_step; PREALPS_ECG_SOLVE_FIRST, read at reset).  sf_ready: the block solve and the finish of the
+   * next iteration are queued behind its product (only inside one call of those loops, see solve_first_step). */
+  int solve_first, sf_ready;
   int phase;          /* iterations since the last reset, mod 6 */
   void* graph[2][6];
   unsigned char seen[2][6];
@@ -128,6 +132,21 @@ static void publish_pointers(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
 }
 
 static int pa_env_flag(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+static int solve_first_switch(void) { return pa_env_flag("PREALPS_ECG_SOLVE_FIRST", 1); }
+
+/* Where the order of solve_first_step applies (the switch on): one process, Orthodir without block-size reduction,
+ * the two-pass first half with lazy normalisation and the lazy stopping test, 4 columns, the Gram blocks left behind
+ * by the block solve and by the SpMM, no graphs.  Everything else keeps the order of preAlps_ECGIterate. */
+static int solve_first_rule(int on, int nprocs, int ortho_alg, int bs_red, int enlFac, int fuse, int lazy_norm,
+                            int lazy_stop, int bj_gram, int spmm_gram, int graphs) {
+  return on && nprocs == 1 && ortho_alg == ORTHODIR && bs_red == NO_BS_RED && enlFac == 4 && fuse && lazy_norm &&
+         lazy_stop && bj_gram && spmm_gram && !graphs;
+}
+int preAlps_hip_ecg_solve_first(int nprocs, int ortho_alg, int bs_red, int enlFac, int fuse, int lazy_norm,
+                                int lazy_stop, int bj_gram, int spmm_gram, int graphs) {
+  return solve_first_rule(solve_first_switch(), nprocs, ortho_alg, bs_red, enlFac, fuse, lazy_norm, lazy_stop,
+                          bj_gram, spmm_gram, graphs);
+}
 
 /* ------------------------------------------------------------- malloc ---- */
 int _preAlps_ECGMalloc(preAlps_ECG_t* ecg) {
@@ -230,6 +249,8 @@ int _preAlps_ECGReset(preAlps_ECG_t* ecg, double* rhs, int* rci_request) {
   pv->lazy_norm = pv->fuse && ecg->ortho_alg == ORTHODIR && pa_env_flag("PREALPS_ECG_LAZY_NORM", 1);
   pv->uu_cur = 0;
   pv->z_ready = 0;
+  pv->solve_first = solve_first_switch();
+  pv->sf_ready = 0;
   /* With more than one process every collective costs tens of microseconds.  The norm of the
    * new residual is only needed for the stopping decision, so the driver loops of this library
    * (preAlps_ECGSolve / ECGAdvance) let it travel with the beta all-reduce of the same
@@ -1024,6 +1045,83 @@ void preAlps_ECGPrint(preAlps_ECG_t* ecg, int verbosity) {
   printf("[%d] ends printing ECG_t!\n", rank);
 }
 
+/* ---- solve first ---------------------------------------------------------------------------------------------
+ * With lazy normalisation the block solve Z = M^-1 AP reads the raw AP, which the update of X and R does not touch,
+ * and both Gram blocks come from raw panels: [AP | R]^T P from the SpMM, [AP | AP_prev]^T Z from the block solve.
+ * So the library's own loops can run an Orthodir iteration as
+ *   SpMM + Gram -> block solve + Gram -> one finish (U, alpha, beta) -> one row pass (X, R, Z and the column sums
+ *   of R^2) -> the norm to the host,
+ * five launches instead of six, with P read once.  Every operation and every sum is that of _preAlps_ECGIterateOdir,
+ * in the same order: the results are bitwise the same.  The host must know the norm of R_k+1 before it queues the
+ * row pass of the next iteration (it overwrites X and R), so the product, the block solve and the finish of that
+ * iteration go out behind the norm before the host waits for it (pv->sf_ready).  After a stop they are unused: they
+ * only wrote AP, Z and the Gram blocks, which a restart writes anew.  The last step of a call queues the product
+ * only, as the other order does: leaving the library's loop ends the Gram request of the SpMM (leave_own_loop), so
+ * that order forms the first alpha of the next call with pa_k_gram_finish, and so must this one to give the same
+ * bits; a call therefore returns in the state "AP = A P is queued" of the RCI protocol (rci 0), as it always did. */
+static int solve_first_applies(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
+  return g_own_loop > 0 && ecg->P->info.n == 4 && pv->ts == 4 &&
+         solve_first_rule(pv->solve_first, pa_world_size(), ecg->ortho_alg, ecg->bs_red, ecg->enlFac, pv->fuse,
+                          pv->lazy_norm, pv->lazy_stop, pv->bj_cap > 0, pv->spmm_cap > 0, pv->use_graphs);
+}
+/* From "AP = A P is queued": the block solve and one launch that sums both Gram blocks -- U = chol(W) and alpha
+ * (fused_gram) and beta (orthogonalise_z).  A product or a block solve that did not leave its block behind: the
+ * block is formed here, as those two do it. */
+static int sf_queue_solve(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
+  int m = pv->m, ts = pv->ts, t = 4, T = ecg->enlFac;
+  double t0;
+  pa_k_bj_gram_arm(pv->buf_av[0], pv->buf_z, pv->buf_av[1], pv->d_bj_parts, pv->bj_cap);
+  if (preAlps_BlockJacobiApply(ecg->AP, ecg->Z)) return 1;
+  int from_spmm = pa_k_spmm_gram_take(ecg->P->val, ecg->AP->val);
+  int from_bj = pa_k_bj_gram_take(pv->buf_av[0], pv->buf_z);
+  double* spmm_scratch = pv->d_spmm_parts + (size_t)pv->spmm_cap * 32;
+  double* bj_scratch = pv->d_bj_parts + (size_t)pv->bj_cap * 32;
+  TIC(PA_T_GRAM);
+  if (from_spmm && from_bj) {
+    PA_CHECK(pa_k_finish32_pair(pv->d_spmm_parts, from_spmm, spmm_scratch, t, T, pv->d_q, pv->d_mu, pv->d_alpha,
+                                pv->d_info, pv->d_bj_parts, from_bj, bj_scratch, pv->d_beta));
+  } else {
+    if (from_spmm) PA_CHECK(pa_k_finish32(pv->d_spmm_parts, from_spmm, spmm_scratch, t, T, pv->d_q, pv->d_mu, pv->d_alpha,
+                                         pv->d_info));
+    else PA_CHECK(pa_k_gram_finish(m, ts, ecg->AP->val, pv->d_R, ecg->P->val, pv->d_partials, t, T, t, pv->d_q, t + T,
+                                   t, T, pv->d_mu, pv->d_alpha, pv->d_info));
+    if (from_bj) PA_CHECK(pa_k_finish32(pv->d_bj_parts, from_bj, bj_scratch, 0, 0, pv->d_beta, NULL, NULL, NULL));
+    else PA_CHECK(pa_k_gram_finish(m, ts, pv->buf_av[0], pv->buf_av[1], pv->buf_z, pv->d_partials, t, t, t,
+                                   pv->d_beta, 2 * t, 0, 0, NULL, NULL, NULL));
+  }
+  TAC(PA_T_GRAM, gemm_t);
+  pv->sf_ready = 1;
+  return 0;
+}
+/* One full iteration: the row pass, the norm to the host, the next iteration's product (ahead: and its block solve
+ * and finish), then the stopping test. */
+static int solve_first_step(preAlps_ECG_t* ecg, ecg_priv_t* pv, int ahead, int* stop) {
+  int t = 4, T = ecg->enlFac, nb = 0;
+  double tg = pa_wtime(), t0;
+  if (!pv->sf_ready && sf_queue_solve(ecg, pv)) return 1;
+  pv->sf_ready = 0;
+  TIC(PA_T_UPDATE);
+  PA_CHECK(pa_k_update_xrz(pv->m, pv->ts, t, pv->d_mu, pv->d_alpha, ecg->P->val, ecg->AP->val, pv->buf_v[1], pv->d_X,
+                           pv->d_R, pv->buf_z, pv->d_rtr_part, &nb, pv->d_uu + (size_t)pv->uu_cur * T * T, pv->d_beta,
+                           ecg->beta->info.lda, pv->d_uu + (size_t)(1 - pv->uu_cur) * T * T));
+  TAC(PA_T_UPDATE, trsm_t);
+  pv->rtr_nblk = nb;
+  pv->uu_cur ^= 1;
+  ecg->iter++;
+  /* the norm of the new residual (and the Cholesky status) straight to the pinned words the host reads */
+  pv->wait_seq = 0.0;
+  if (pv->poll) { pv->wait_seq = (pv->seq += 1.0); pa_k_note_seq(pv->wait_seq); }
+  PA_CHECK(pa_k_trace_finish(pv->d_rtr_part, nb, pv->ts, T, pv->d_res2, pv->d_info, pv->h_pin));
+  if (!pv->poll) PA_CHECK(pa_rt_event_record(pv->ev_res));
+  pv->rtr_valid = 0; pv->sent_seq = 0.0; pv->lazy_ptr = NULL;
+  if (shift_directions(ecg, pv, t)) return 1;
+  request_gram_from_spmm(ecg, pv);
+  if (preAlps_BlockOperator(ecg->P, ecg->AP)) return 1;
+  if (ahead && sf_queue_solve(ecg, pv)) return 1;
+  ecg->tot_t += pa_wtime() - tg;
+  return stopping_end(ecg, pv, stop);
+}
+
 /* The driver loop of examples/test_ecg_prealps_op.c:203-223 (fused:
  * examples/test_ecg_bench_fused.c:243-259). */
 static int ecg_solve_loop(preAlps_ECG_t* ecg, double* rhs, double* sol, double* res_hist, int* bs_hist,
@@ -1048,6 +1146,13 @@ static int ecg_solve_loop(preAlps_ECG_t* ecg, double* rhs, double* sol, double* 
     if (preAlps_BlockOperator(ecg->P, ecg->AP)) return 1;
     while (stop != 1) {
       if (graph_iteration(ecg, pvg, &rci, &stop)) return 1;
+      if (res_hist && nh < max_hist) { res_hist[nh] = ecg->res; if (bs_hist) bs_hist[nh] = ecg->bs; }
+      ++nh;
+    }
+  } else if (pvg && ecg->ortho_alg != ORTHODIR_FUSED && solve_first_applies(ecg, pvg)) {
+    if (preAlps_BlockOperator(ecg->P, ecg->AP)) return 1;
+    while (stop != 1) {
+      if (solve_first_step(ecg, pvg, 1, &stop)) return 1;
       if (res_hist && nh < max_hist) { res_hist[nh] = ecg->res; if (bs_hist) bs_hist[nh] = ecg->bs; }
       ++nh;
     }
@@ -1139,6 +1244,21 @@ static int ecg_advance_loop(preAlps_ECG_t* ecg, double* rhs, int* rci_request, i
     if (pvg && pvg->use_graphs && *rci_request == 0) {
       while (done < nsteps) {
         if (graph_iteration(ecg, pvg, rci_request, &stop)) return 1;
+        ++done;
+        if (stop == 1) {
+          if (restarts) ++*restarts;
+          if (last_iters) *last_iters = ecg->iter;
+          if (last_res) *last_res = ecg->res;
+          if (_preAlps_ECGReset(ecg, rhs, rci_request)) return 1;
+          if (preAlps_BlockJacobiApply(ecg->R, ecg->P)) return 1;
+          if (preAlps_BlockOperator(ecg->P, ecg->AP)) return 1;
+        }
+      }
+      return 0;
+    }
+    if (pvg && *rci_request == 0 && solve_first_applies(ecg, pvg)) {
+      while (done < nsteps) {
+        if (solve_first_step(ecg, pvg, done + 1 < nsteps, &stop)) return 1;
         ++done;
         if (stop == 1) {
           if (restarts) ++*restarts;

@@ -745,18 +745,17 @@ __global__ __launch_bounds__(WG) void k_finish_wide(const double* __restrict__ p
 // read): FIN32_WG workgroups sum a contiguous share each (32-byte loads, 32 blocks side by
 // side, fixed order) into scratch; the last one to finish (ticket counter) adds
 // the shares in order and, t > 0, factors and forms alpha as k_finish_potrf_alpha does.
+// The body, for workgroup `bid` of the FIN32_WG that share one sum (k_finish32: the grid; k_finish32_pair: half of it).
 constexpr int FIN32_WG = 64;
-__global__ __launch_bounds__(WG) void k_finish32(const double* __restrict__ partials, int nblk,
-                                                 double* scratch, int t, int T, double* out,
-                                                 double* __restrict__ mu, double* __restrict__ alpha,
-                                                 int* __restrict__ info, const double* __restrict__ rtr,
-                                                 int rtr_nblk, int rtr_ts, int rtr_nc, double* __restrict__ res2) {
-  __shared__ double red[32 * 32];
-  __shared__ int s_last;
+__device__ __forceinline__ void finish32_wg(const double* __restrict__ partials, int nblk, double* scratch, int t,
+                                            int T, double* out, double* __restrict__ mu, double* __restrict__ alpha,
+                                            int* __restrict__ info, const double* __restrict__ rtr, int rtr_nblk,
+                                            int rtr_ts, int rtr_nc, double* __restrict__ res2, int bid,
+                                            double* red, int& s_last) {
   typedef double d4 __attribute__((ext_vector_type(4)));
   const int tid = threadIdx.x, e4 = tid & 7, sl = tid >> 3;
   const int per = (nblk + FIN32_WG - 1) / FIN32_WG;
-  const int b0 = blockIdx.x * per, b1 = min(nblk, b0 + per);
+  const int b0 = bid * per, b1 = min(nblk, b0 + per);
   const d4* __restrict__ q = reinterpret_cast<const d4*>(partials) + e4;
   d4 sum = {0.0, 0.0, 0.0, 0.0};
   // four blocks per thread in flight, the last round too (blocks beyond the share: the thread's first block
@@ -781,12 +780,12 @@ __global__ __launch_bounds__(WG) void k_finish32(const double* __restrict__ part
   // the share goes out with device-scope (write-through) stores, the ticket is taken once they have
   // completed, and the last workgroup reads the shares with device-scope loads: no fence, which
   // costs 10 us on gfx950 even when the L2 holds nothing dirty
-  if (tid < 32) __hip_atomic_store(scratch + blockIdx.x * 32 + tid, red[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid < 32) __hip_atomic_store(scratch + bid * 32 + tid, red[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   // (the ticket lives behind the shares of THIS call's scratch -- zero when the buffer is made, set back by the
   // last workgroup -- so that two solver objects, or two streams, never elect across each other's launches)
   unsigned* ticket = reinterpret_cast<unsigned*>(scratch + FIN32_WG * 32);
-  if (tid == 0) s_last = (__hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1);
+  if (tid == 0) s_last = (__hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == FIN32_WG - 1);
   __syncthreads();
   if (!s_last) return;
   {
@@ -818,6 +817,31 @@ __global__ __launch_bounds__(WG) void k_finish32(const double* __restrict__ part
     __syncthreads();
     trace_finish_wg(rtr, rtr_nblk, rtr_ts, rtr_nc, res2, info, nullptr, red);
   }
+}
+__global__ __launch_bounds__(WG) void k_finish32(const double* __restrict__ partials, int nblk,
+                                                 double* scratch, int t, int T, double* out,
+                                                 double* __restrict__ mu, double* __restrict__ alpha,
+                                                 int* __restrict__ info, const double* __restrict__ rtr,
+                                                 int rtr_nblk, int rtr_ts, int rtr_nc, double* __restrict__ res2) {
+  __shared__ double red[32 * 32];
+  __shared__ int s_last;
+  finish32_wg(partials, nblk, scratch, t, T, out, mu, alpha, info, rtr, rtr_nblk, rtr_ts, rtr_nc, res2, blockIdx.x,
+              red, s_last);
+}
+// Two k_finish32 in one launch (2 FIN32_WG workgroups): the first half sums the blocks the SpMM left, factors and
+// forms alpha (t > 0); the second half sums the blocks the block solve left (beta).  Each half is one k_finish32 --
+// same shares, same order of additions, own scratch and ticket -- so both results are those of two launches.
+__global__ __launch_bounds__(WG) void k_finish32_pair(const double* __restrict__ pa, int na, double* sa, int t, int T,
+                                                      double* outa, double* __restrict__ mu, double* __restrict__ alpha,
+                                                      int* __restrict__ info, const double* __restrict__ pb, int nb,
+                                                      double* sb, double* outb) {
+  __shared__ double red[32 * 32];
+  __shared__ int s_last;
+  if (blockIdx.x < FIN32_WG)
+    finish32_wg(pa, na, sa, t, T, outa, mu, alpha, info, nullptr, 0, 0, 0, nullptr, blockIdx.x, red, s_last);
+  else
+    finish32_wg(pb, nb, sb, 0, 0, outb, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, blockIdx.x - FIN32_WG,
+                red, s_last);
 }
 
 // t x t upper Cholesky, one lane (t <= 16).  LAPACK dpotf2 'U': on failure
@@ -990,15 +1014,12 @@ __global__ void k_potrf_alpha(const double* __restrict__ buf, int t, int T, doub
 // gram != null (runs of several processes, where an all-reduce of [W ; G^T] sits between the Gram
 // kernel and this one): every workgroup factors W and forms alpha itself (k_potrf_alpha's
 // arithmetic, a microsecond), workgroup 0 stores them and the status -- one launch less.
+// Prologue of k_trsm_update / k_update_xrz, whole workgroup: U (su), 1 / diag(U) (sd) and alpha (sa) into LDS -- from
+// U and alpha, or formed from gram = [W ; G^T] -- and, ukeep != null, U kept there by workgroup 0.
 template <int TS>
-__global__ __launch_bounds__(WG) void k_trsm_update(int m, int t, int nc, double* U, double* alpha,
-                                                    double* __restrict__ P, double* __restrict__ AP,
-                                                    double* __restrict__ X, double* __restrict__ R,
-                                                    double* __restrict__ rtr, const double* gram, int* info,
-                                                    double* __restrict__ ukeep, int xnt) {
-  __shared__ double su[TS * TS];
-  __shared__ double sd[TS];
-  __shared__ double sa[TS * TS];
+__device__ __forceinline__ void trsm_update_prologue(int t, int nc, double* U, double* alpha, const double* gram,
+                                                     int* info, double* __restrict__ ukeep, double* su, double* sd,
+                                                     double* sa) {
   if (gram) {
     const bool first = blockIdx.x == 0;
     potrf_alpha_wg(gram, t, nc, first ? U : nullptr, first ? alpha : nullptr, first ? info : nullptr, su, sa);
@@ -1012,6 +1033,52 @@ __global__ __launch_bounds__(WG) void k_trsm_update(int m, int t, int nc, double
   // registers for X and R only -- and the factor is kept for the kernels that meet the raw panels later
   if (ukeep && blockIdx.x == 0) for (int e = threadIdx.x; e < t * t; e += WG) ukeep[e] = su[e];
   __syncthreads();
+}
+// One row of k_trsm_update / k_update_xrz: p <- p U^-1, ap <- ap U^-1 (in registers), x += p alpha, r -= ap alpha,
+// rr += r^2 per column.
+template <int TS>
+__device__ __forceinline__ void trsm_update_row(double (&p)[TS], double (&ap)[TS], double (&x)[TS], double (&r)[TS],
+                                                double (&rr)[TS], const double* su, const double* sd, const double* sa,
+                                                int t, int nc) {
+#pragma unroll
+  for (int j = 0; j < TS; ++j) {
+    if (j < t) {
+      double s1 = p[j], s2 = ap[j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) { const double u = su[k + t * j]; s1 = fma(-p[k], u, s1); s2 = fma(-ap[k], u, s2); }
+      p[j] = s1 * sd[j];
+      ap[j] = s2 * sd[j];
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < TS; ++c) {
+    if (c < nc) {
+      double sx = 0.0, sr = 0.0;
+#pragma unroll
+      for (int k = 0; k < TS; ++k) {
+        if (k < t) {
+          const double a = sa[k + t * c];
+          sx = fma(p[k], a, sx);
+          sr = fma(ap[k], a, sr);
+        }
+      }
+      x[c] += sx;
+      r[c] -= sr;
+      rr[c] = fma(r[c], r[c], rr[c]);
+    }
+  }
+}
+
+template <int TS>
+__global__ __launch_bounds__(WG) void k_trsm_update(int m, int t, int nc, double* U, double* alpha,
+                                                    double* __restrict__ P, double* __restrict__ AP,
+                                                    double* __restrict__ X, double* __restrict__ R,
+                                                    double* __restrict__ rtr, const double* gram, int* info,
+                                                    double* __restrict__ ukeep, int xnt) {
+  __shared__ double su[TS * TS];
+  __shared__ double sd[TS];
+  __shared__ double sa[TS * TS];
+  trsm_update_prologue<TS>(t, nc, U, alpha, gram, info, ukeep, su, sd, sa);
   double rr[TS];
 #pragma unroll
   for (int c = 0; c < TS; ++c) rr[c] = 0.0;
@@ -1030,33 +1097,7 @@ __global__ __launch_bounds__(WG) void k_trsm_update(int m, int t, int nc, double
     // caches from one iteration to the next and the hint would send it to memory
     if (xnt) load_row_nt<TS>(X, row, x); else load_row<TS>(X, row, x);
     load_row<TS>(R, row, r);
-#pragma unroll
-    for (int j = 0; j < TS; ++j) {
-      if (j < t) {
-        double s1 = p[j], s2 = ap[j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) { const double u = su[k + t * j]; s1 = fma(-p[k], u, s1); s2 = fma(-ap[k], u, s2); }
-        p[j] = s1 * sd[j];
-        ap[j] = s2 * sd[j];
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < TS; ++c) {
-      if (c < nc) {
-        double sx = 0.0, sr = 0.0;
-#pragma unroll
-        for (int k = 0; k < TS; ++k) {
-          if (k < t) {
-            const double a = sa[k + t * c];
-            sx = fma(p[k], a, sx);
-            sr = fma(ap[k], a, sr);
-          }
-        }
-        x[c] += sx;
-        r[c] -= sr;
-        rr[c] = fma(r[c], r[c], rr[c]);
-      }
-    }
+    trsm_update_row<TS>(p, ap, x, r, rr, su, sd, sa, t, nc);
     if (!ukeep) {
       store_row<TS>(P, row, p);
       store_row<TS>(AP, row, ap);
@@ -1251,6 +1292,76 @@ __global__ __launch_bounds__(WG) void k_trace_finish(const double* __restrict__ 
   trace_finish_wg(rtr, nblk, ts, nc, res2, info, host, red, seq);
 }
 
+// Lazy normalisation, panels of up to 4 columns (k_update_z<TS>, k_update_xrz): C0 = Ui, C1 = Ui (Ui^T G1 Ui),
+// C2 = Up (Up^T G2 Ui) from the raw Gram blocks sb = [G1 ; G2] ((a_lo + a_hi) x a_lo) and the two factors sfac =
+// [ucur | uprev] in LDS, into sc + 4, 5, 6 TS^2 (sc: 7 TS^2 doubles); called by a whole workgroup, ends synchronised.
+template <int TS>
+__device__ __forceinline__ void lazy_coeffs_wg(const double* sb, const double* sfac, int a_lo, int a_hi, double* sc) {
+  const int na = a_lo + a_hi;
+  const int t = a_lo, tt = t * t, tid = threadIdx.x;
+  double* Ui = sc; double* Up = sc + TS * TS; double* T1 = sc + 2 * TS * TS; double* T2 = sc + 3 * TS * TS;
+  double* C0 = sc + 4 * TS * TS; double* C1 = sc + 5 * TS * TS; double* C2 = sc + 6 * TS * TS;
+  if (tid < 64) {
+    if (tid < 2 * t) {          // column c of the inverse of an upper-triangular factor: back substitution on e_c
+      const double* Uf = tid < t ? sfac : sfac + tt;
+      double* inv = tid < t ? Ui : Up;
+      const int c = tid < t ? tid : tid - t;
+      double x[TS];
+#pragma unroll
+      for (int i = TS - 1; i >= 0; --i) {
+        x[i] = 0.0;
+        if (i < t && i <= c) {
+          double sv = i == c ? 1.0 : 0.0;
+#pragma unroll
+          for (int k = i + 1; k < TS; ++k) if (k < t && k <= c) sv = fma(-Uf[i + t * k], x[k], sv);
+          x[i] = sv / Uf[i + t * i];
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < TS; ++i) if (i < t) inv[i + t * c] = x[i];
+    }
+    wave_lds_sync();
+    const int r = tid % (t > 0 ? t : 1), c = tid / (t > 0 ? t : 1);
+    const bool on = tid < tt;
+    if (on) {                     // T1 = G1 Ui, T2 = G2 Ui
+      double s1 = 0.0, s2 = 0.0;
+      for (int k = 0; k < t; ++k) { s1 = fma(sb[r + na * k], Ui[k + t * c], s1); if (a_hi > 0) s2 = fma(sb[a_lo + r + na * k], Ui[k + t * c], s2); }
+      T1[tid] = s1; T2[tid] = s2;
+    }
+    wave_lds_sync();
+    double b1 = 0.0, b2 = 0.0;
+    if (on) {                     // beta1 = Ui^T T1, beta2 = Up^T T2
+      for (int k = 0; k < t; ++k) { b1 = fma(Ui[k + t * r], T1[k + t * c], b1); b2 = fma(Up[k + t * r], T2[k + t * c], b2); }
+    }
+    wave_lds_sync();
+    if (on) { T1[tid] = b1; T2[tid] = b2; }
+    wave_lds_sync();
+    if (on) {                     // C1 = Ui beta1, C2 = Up beta2, C0 = Ui
+      double c1 = 0.0, c2 = 0.0;
+      for (int k = 0; k < t; ++k) { c1 = fma(Ui[r + t * k], T1[k + t * c], c1); c2 = fma(Up[r + t * k], T2[k + t * c], c2); }
+      C0[tid] = Ui[tid]; C1[tid] = c1; C2[tid] = c2;
+    }
+  }
+  __syncthreads();
+}
+// One row of Z: o = z C0 - v0 C1 - v1 C2 on the first nc columns, z elsewhere.
+template <int TS>
+__device__ __forceinline__ void update_z_lazy_row(const double (&z)[TS], const double (&v0)[TS], const double (&v1)[TS],
+                                                  double (&o)[TS], const double* C0, const double* C1, const double* C2,
+                                                  int t, int a_hi, int nc) {
+#pragma unroll
+  for (int c = 0; c < TS; ++c) {
+    o[c] = z[c];
+    if (c < nc) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < TS; ++k)
+        if (k < t) { s = fma(z[k], C0[k + t * c], s); s = fma(-v0[k], C1[k + t * c], s); if (a_hi > 0) s = fma(-v1[k], C2[k + t * c], s); }
+      o[c] = s;
+    }
+  }
+}
+
 // Z(:, :nc) -= [V0(:, :a_lo) | V1(:, :a_hi)] beta
 template <int TS>
 __global__ __launch_bounds__(WG) void k_update_z(int m, int a_lo, int a_hi, int nc,
@@ -1293,67 +1404,15 @@ __global__ __launch_bounds__(WG) void k_update_z(int m, int a_lo, int a_hi, int 
     // AP_prev_raw^T Z_raw.  With Ui = U^-1, Up = uprev^-1 the reference's update Z_n - P_n beta1 - P_prev_n beta2
     // (ecg.c:510-517 on the normalised panels) is  Z_raw C0 - P_raw C1 - P_prev_raw C2,  C0 = Ui,
     // C1 = Ui (Ui^T G1 Ui), C2 = Up (Up^T G2 Ui): sixteen threads form the three t x t blocks in LDS.
-    const int t = a_lo, tt = t * t, tid = threadIdx.x;
-    double* Ui = sc; double* Up = sc + TS * TS; double* T1 = sc + 2 * TS * TS; double* T2 = sc + 3 * TS * TS;
-    double* C0 = sc + 4 * TS * TS; double* C1 = sc + 5 * TS * TS; double* C2 = sc + 6 * TS * TS;
-    if (tid < 64) {
-      if (tid < 2 * t) {          // column c of the inverse of an upper-triangular factor: back substitution on e_c
-        const double* Uf = tid < t ? sfac : sfac + tt;
-        double* inv = tid < t ? Ui : Up;
-        const int c = tid < t ? tid : tid - t;
-        double x[TS];
-#pragma unroll
-        for (int i = TS - 1; i >= 0; --i) {
-          x[i] = 0.0;
-          if (i < t && i <= c) {
-            double sv = i == c ? 1.0 : 0.0;
-#pragma unroll
-            for (int k = i + 1; k < TS; ++k) if (k < t && k <= c) sv = fma(-Uf[i + t * k], x[k], sv);
-            x[i] = sv / Uf[i + t * i];
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < TS; ++i) if (i < t) inv[i + t * c] = x[i];
-      }
-      wave_lds_sync();
-      const int r = tid % (t > 0 ? t : 1), c = tid / (t > 0 ? t : 1);
-      const bool on = tid < tt;
-      if (on) {                     // T1 = G1 Ui, T2 = G2 Ui
-        double s1 = 0.0, s2 = 0.0;
-        for (int k = 0; k < t; ++k) { s1 = fma(sb[r + na * k], Ui[k + t * c], s1); if (a_hi > 0) s2 = fma(sb[a_lo + r + na * k], Ui[k + t * c], s2); }
-        T1[tid] = s1; T2[tid] = s2;
-      }
-      wave_lds_sync();
-      double b1 = 0.0, b2 = 0.0;
-      if (on) {                     // beta1 = Ui^T T1, beta2 = Up^T T2
-        for (int k = 0; k < t; ++k) { b1 = fma(Ui[k + t * r], T1[k + t * c], b1); b2 = fma(Up[k + t * r], T2[k + t * c], b2); }
-      }
-      wave_lds_sync();
-      if (on) { T1[tid] = b1; T2[tid] = b2; }
-      wave_lds_sync();
-      if (on) {                     // C1 = Ui beta1, C2 = Up beta2, C0 = Ui
-        double c1 = 0.0, c2 = 0.0;
-        for (int k = 0; k < t; ++k) { c1 = fma(Ui[r + t * k], T1[k + t * c], c1); c2 = fma(Up[r + t * k], T2[k + t * c], c2); }
-        C0[tid] = Ui[tid]; C1[tid] = c1; C2[tid] = c2;
-      }
-    }
-    __syncthreads();
+    lazy_coeffs_wg<TS>(sb, sfac, a_lo, a_hi, sc);
+    const double* C0 = sc + 4 * TS * TS; const double* C1 = sc + 5 * TS * TS; const double* C2 = sc + 6 * TS * TS;
+    const int t = a_lo;
     for (size_t row = (size_t)blockIdx.x * WG + threadIdx.x; row < (size_t)m; row += stride) {
       double z[TS], v0[TS], v1[TS], o[TS];
       load_row<TS>(Z, row, z);
       load_row<TS>(V0, row, v0);
       if (a_hi > 0) load_row<TS>(V1, row, v1);
-#pragma unroll
-      for (int c = 0; c < TS; ++c) {
-        o[c] = z[c];
-        if (c < nc) {
-          double s = 0.0;
-#pragma unroll
-          for (int k = 0; k < TS; ++k)
-            if (k < t) { s = fma(z[k], C0[k + t * c], s); s = fma(-v0[k], C1[k + t * c], s); if (a_hi > 0) s = fma(-v1[k], C2[k + t * c], s); }
-          o[c] = s;
-        }
-      }
+      update_z_lazy_row<TS>(z, v0, v1, o, C0, C1, C2, t, a_hi, nc);
       store_row<TS>(Z, row, o);
       if (pk_off) for (int k = pk_off[row], k1 = pk_off[row + 1]; k < k1; ++k) store_row<TS>(sendbuf, (size_t)pk_slot[k], o);
     }
@@ -1382,6 +1441,54 @@ __global__ __launch_bounds__(WG) void k_update_z(int m, int a_lo, int a_hi, int 
     store_row<TS>(Z, row, z);
     if (pk_off) for (int k = pk_off[row], k1 = pk_off[row + 1]; k < k1; ++k) store_row<TS>(sendbuf, (size_t)pk_slot[k], z);
   }
+}
+
+// k_trsm_update (lazy normalisation: ukeep, X nontemporal under xnt) and k_update_z (lazy coefficients, V0 = P,
+// V1 = P_prev, a_lo = a_hi = nc = t) in one pass over the rows, for the order in which the block solve runs before
+// the update (ecg.c: solve_first): both halves of the update read P, so P is read once, and the six panels go
+// through one launch.  Per element the arithmetic of the two kernels (the same device functions); the grid, the
+// row -> workgroup map and the column sums of R^2 are k_trsm_update's (update_grid), so k_trace_finish forms the
+// same norm.  ucur of k_update_z is U itself: the factor k_trsm_update keeps in ukeep for it.
+template <int TS>
+__global__ __launch_bounds__(WG) void k_update_xrz(int m, int t, double* U, double* alpha, const double* __restrict__ P,
+                                                   const double* __restrict__ AP, const double* __restrict__ Pprev,
+                                                   double* __restrict__ X, double* __restrict__ R,
+                                                   double* __restrict__ Z, double* __restrict__ rtr,
+                                                   double* __restrict__ ukeep, const double* __restrict__ beta,
+                                                   int ldb, const double* __restrict__ uprev, int xnt) {
+  __shared__ double su[TS * TS];
+  __shared__ double sd[TS];
+  __shared__ double sa[TS * TS];
+  __shared__ double sb[2 * TS * TS];
+  __shared__ double sfac[2 * TS * TS];
+  __shared__ double sc[7 * TS * TS];
+  const int na = 2 * t, tt = t * t;
+  for (int e = threadIdx.x; e < na * t; e += WG) sb[e] = beta[(e % na) + ldb * (e / na)];
+  for (int e = threadIdx.x; e < 2 * tt; e += WG) sfac[e] = e < tt ? U[e] : uprev[e - tt];
+  trsm_update_prologue<TS>(t, t, U, alpha, nullptr, nullptr, ukeep, su, sd, sa);    // (its barriers cover sb / sfac)
+  lazy_coeffs_wg<TS>(sb, sfac, t, t, sc);
+  const double* C0 = sc + 4 * TS * TS; const double* C1 = sc + 5 * TS * TS; const double* C2 = sc + 6 * TS * TS;
+  double rr[TS];
+#pragma unroll
+  for (int c = 0; c < TS; ++c) rr[c] = 0.0;
+  const size_t stride = (size_t)gridDim.x * WG;
+  for (size_t row = (size_t)blockIdx.x * WG + threadIdx.x; row < (size_t)m; row += stride) {
+    double p[TS], ap[TS], x[TS], r[TS], z[TS], v0[TS], v1[TS], o[TS];
+    load_row<TS>(P, row, v0);
+    load_row<TS>(AP, row, ap);
+    if (xnt) load_row_nt<TS>(X, row, x); else load_row<TS>(X, row, x);
+    load_row<TS>(R, row, r);
+    load_row<TS>(Z, row, z);
+    load_row<TS>(Pprev, row, v1);
+#pragma unroll
+    for (int c = 0; c < TS; ++c) p[c] = v0[c];      // (normalised in registers below; Z's update takes the raw row)
+    trsm_update_row<TS>(p, ap, x, r, rr, su, sd, sa, t, t);
+    update_z_lazy_row<TS>(z, v0, v1, o, C0, C1, C2, t, t, t);
+    if (xnt) store_row_nt<TS>(X, row, x); else store_row<TS>(X, row, x);
+    store_row<TS>(R, row, r);
+    store_row<TS>(Z, row, o);
+  }
+  block_sum_cols<TS>(rr, rtr + (size_t)blockIdx.x * TS);
 }
 
 // 16-column panels on the f64 matrix cores: a tile of 16 rows of Z is the C/D operand (lane l
@@ -3036,6 +3143,13 @@ int pa_k_finish32(const double* partials, int nblk, double* scratch, int t, int 
   return kfail("k_finish32");
 }
 
+int pa_k_finish32_pair(const double* pa, int na, double* sa, int t, int T, double* outa, double* mu, double* alpha,
+                       int* info, const double* pb, int nb, double* sb, double* outb) {
+  PA_LAUNCH(k_finish32_pair, dim3(2 * FIN32_WG), dim3(WG), 0, cur_stream(), pa, na, sa, t, T, outa, mu, alpha, info,
+            pb, nb, sb, outb);
+  return kfail("k_finish32_pair");
+}
+
 int pa_k_finish32_trace(const double* partials, int nblk, double* scratch, double* out, const double* rtr_partials,
                         int rtr_nblk, int ts, int nc, double* res2, int* info) {
   PA_LAUNCH(k_finish32, dim3(FIN32_WG), dim3(WG), 0, cur_stream(), partials, nblk, scratch, 0, 0, out,
@@ -3203,11 +3317,19 @@ int pa_k_potrf_alpha(const double* buf, int t, int T, double* mu, double* alpha,
   return kfail("k_potrf_alpha");
 }
 
+/* The grid of k_trsm_update and k_update_xrz: the layout of their column sums of R^2 (and so the norm summed from
+ * them) depends on it. */
+static int update_grid(int m) {
+  int blocks = grid_rows(m, 2);
+  return blocks > GRAM_MAX_BLOCKS ? GRAM_MAX_BLOCKS : blocks;
+}
+/* X with the nontemporal hint (k_trsm_update): only a panel of 16 MiB or more; a smaller one stays in the caches */
+static int x_nontemporal(int m, int ts) { return (size_t)m * ts * sizeof(double) >= ((size_t)16 << 20) ? 1 : 0; }
+
 int pa_k_trsm_update(int m, int ts, int t, int nc, double* U, double* alpha, double* P,
                      double* AP, double* X, double* R, double* rtr_partials, int* nblk, int trace_nc,
                      double* res2, int* info, double* host, const double* gram, double* ukeep) {
-  int blocks = grid_rows(m, 2);
-  if (blocks > GRAM_MAX_BLOCKS) blocks = GRAM_MAX_BLOCKS;
+  const int blocks = update_grid(m);
   *nblk = blocks;
   // PREALPS_TRSM_MFMA=0: lane-per-row substitution at every width (the matrix-core variant forms U^-1)
   static int use_mfma = -1;
@@ -3219,13 +3341,27 @@ int pa_k_trsm_update(int m, int ts, int t, int nc, double* U, double* alpha, dou
   else {
     TS_DISPATCH(ts, PA_LAUNCH((k_trsm_update<TS_>), dim3(blocks), dim3(WG), 0, cur_stream(), m,
                                        t, nc, U, alpha, P, AP, X, R, rtr_partials, gram, info, ukeep,
-                                       (size_t)m * ts * sizeof(double) >= ((size_t)16 << 20) ? 1 : 0));
+                                       x_nontemporal(m, ts)));
   }
   if (kfail("k_trsm_update")) return 1;
   if (trace_nc <= 0) return 0;
   PA_LAUNCH(k_trace_finish, dim3(1), dim3(WG), 0, cur_stream(), rtr_partials, blocks, ts, trace_nc,
                      res2, (const int*)info, host, take_note_seq(host));
   return kfail("k_trace_finish");
+}
+
+int pa_k_update_xrz(int m, int ts, int t, double* U, double* alpha, const double* P, const double* AP,
+                    const double* P_prev, double* X, double* R, double* Z, double* rtr_partials, int* nblk,
+                    double* ukeep, const double* beta, int ldb, const double* uprev) {
+  if (ts != 4 || t < 1 || t > 4 || ldb < 2 * t || !U || !alpha || !P_prev || !ukeep || !beta || !uprev) {
+    snprintf(g_kerr, sizeof(g_kerr), "pa_k_update_xrz: 4-column panels with lazy normalisation only");
+    return 1;
+  }
+  const int blocks = update_grid(m);
+  *nblk = blocks;
+  PA_LAUNCH((k_update_xrz<4>), dim3(blocks), dim3(WG), 0, cur_stream(), m, t, U, alpha, P, AP, P_prev, X, R, Z,
+            rtr_partials, ukeep, beta, ldb, uprev, x_nontemporal(m, ts));
+  return kfail("k_update_xrz");
 }
 
 int pa_k_colnorm2(int m, int ts, const double* R, double* rtr_partials, int* nblk) {

@@ -112,6 +112,10 @@ int pa_k_spmm_gram_take(const double* X, const double* Y);
 int pa_k_finish32(const double* partials, int nblk, double* scratch, int t, int T, double* out, double* mu,
                   double* alpha, int* info);       /* scratch: pa_finish32_scratch_blocks() x 32 doubles */
 int pa_finish32_scratch_blocks(void);
+/* Two pa_k_finish32 in one launch, each with its own partials, scratch and result, and the same sums as alone:
+ * a (t > 0: factored, alpha formed, as pa_k_finish32) and b (summed only). */
+int pa_k_finish32_pair(const double* pa, int na, double* sa, int t, int T, double* outa, double* mu, double* alpha,
+                       int* info, const double* pb, int nb, double* sb, double* outb);
 /* the same sum, followed by the residual norm from the update kernel's column sums (res2[0], res2[1] = *info) */
 int pa_k_finish32_trace(const double* partials, int nblk, double* scratch, double* out, const double* rtr_partials,
                         int rtr_nblk, int ts, int nc, double* res2, int* info);
@@ -178,6 +182,13 @@ int pa_k_trsm_update(int m, int ts, int t, int nc, double* U, double* alpha, dou
                      double* res2, int* info, double* host, const double* gram, double* ukeep);
 /* ukeep != NULL (lazy normalisation, panels of up to 4 columns): P and AP are NOT overwritten -- X and R get the
  * same update from rows normalised in registers -- and the t x t factor U is stored in ukeep for pa_k_update_z. */
+/* pa_k_trsm_update (ukeep, no gram, no trace) and pa_k_update_z (ucur = U, uprev, V0 = P, V1 = P_prev, a_lo = a_hi =
+ * nc = t) in one pass over P, AP, P_prev, X, R and Z: X += P U^-1 alpha, R -= AP U^-1 alpha, Z <- Z C0 - P C1 -
+ * P_prev C2, U kept in ukeep, and the column sums of R^2 in pa_k_trsm_update's layout (*nblk blocks).  4-column
+ * panels only. */
+int pa_k_update_xrz(int m, int ts, int t, double* U, double* alpha, const double* P, const double* AP,
+                    const double* P_prev, double* X, double* R, double* Z, double* rtr_partials, int* nblk,
+                    double* ukeep, const double* beta, int ldb, const double* uprev);
 /* Standalone sums of R(:,c)^2 (same layout as above). */
 int pa_k_colnorm2(int m, int ts, const double* R, double* rtr_partials, int* nblk);
 /* res2[0] = sum over blocks and columns c < nc; res2[1] = *info (0 if info is NULL). */

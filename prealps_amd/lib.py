@@ -78,7 +78,7 @@ EXPORTS = [
     "preAlps_hip_partition_kway", "preAlps_hip_rccl_available",
     "preAlps_hip_panel_gram", "preAlps_hip_panel_update", "preAlps_hip_panel_trsm_update",
     "preAlps_hip_panel_permute_solve",
-    "preAlps_hip_nd_selfcheck", "preAlps_hip_loopback", "preAlps_hip_graphs",
+    "preAlps_hip_nd_selfcheck", "preAlps_hip_loopback", "preAlps_hip_graphs", "preAlps_hip_ecg_solve_first",
 ]
 
 _lib = None
