@@ -120,6 +120,13 @@ int preAlps_ECGSolve(preAlps_ECG_t* ecg, double* rhs, double* sol,
 /* 1 / 0: the two driver loops above and below replay each half of an iteration from a HIP graph
  * captured on its first passes (default: off, or PREALPS_ECG_GRAPH; plain launches measured faster). */
 void preAlps_hip_graphs(int on);
+/* Storage of the sparse (nested-dissection) factors that large diagonal blocks get, from the next
+ * preAlps_BlockJacobiCreate on: 64 = fp64; 32 = fp32 (factored in fp64, both panel copies rounded from the
+ * same values, every operation of the apply in fp64: half the bytes the block solve streams, a preconditioner
+ * that stays exactly symmetric positive definite and loses fp32 rounding in quality); 0 (default) = follow
+ * PREALPS_BJ_ND_PRECISION (`double`, the default, or `single`; any other value makes the create fail).  Band
+ * blocks -- every block without the sparse factor -- stay fp64 either way.  Other values are refused; needs no GPU. */
+int preAlps_hip_set_nd_precision(int bits);
 /* 1: the two driver loops run an Orthodir iteration of a solver described by the arguments with the block solve
  * before the update of X and R (one finish and one row pass per iteration; bitwise the same results), 0: in the
  * order of preAlps_ECGIterate.  PREALPS_ECG_SOLVE_FIRST=0 (read here as a solver reads it when it is reset) keeps
@@ -155,10 +162,11 @@ int preAlps_hip_panel_trsm_update(CPLM_Mat_Dense_t* P, CPLM_Mat_Dense_t* AP, CPL
 int preAlps_hip_panel_permute_solve(const CPLM_Mat_Dense_t* Z, CPLM_Mat_Dense_t* P, const int* host_piv, int t,
                                     const double* host_U, int one_pass);
 /* Numeric facts about the built operator / preconditioner, by name:
- * "nnz_local", "rows_local", "halo_rows", "spmm_blocks", "bj_factor_bytes",
- * "bj_max_bandwidth", "bj_parts_local", "bj_nd_blocks" (blocks with the sparse factor),
- * "bj_nd_inverse_dev" (largest deviation of its inverted pivot triangles), ...  Returns non-zero
- * for unknown keys. */
+ * "nnz_local", "rows_local", "halo_rows", "spmm_blocks", "bj_factor_bytes" (bytes of block factors
+ * stored: the sparse ones at 4 bytes per entry in single precision), "bj_max_bandwidth", "bj_parts_local",
+ * "bj_nd_blocks" (blocks with the sparse factor), "bj_nd_inverse_dev" (largest deviation of its inverted
+ * pivot triangles), "bj_nd_precision" (64 / 32: storage of the sparse factors, 0: no block has one; band
+ * blocks are always fp64), ...  Returns non-zero for unknown keys. */
 int preAlps_hip_get_stat(const char* key, double* value);
 /* A stopwatch made of two hipEvents on the library stream: start records the
  * first, stop records the second, waits for it and returns the device time

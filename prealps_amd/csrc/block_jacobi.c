@@ -68,6 +68,16 @@ double pa_bj_factor_bytes(void) { return g_bj.created ? g_bj.factor_bytes : 0.0;
 int pa_bj_max_bandwidth(void) { return g_bj.created ? g_bj.max_bw : 0; }
 int pa_bj_nparts(void) { return g_bj.created ? g_bj.np : 0; }
 int pa_bj_nd_blocks(void) { return g_bj.created ? g_bj.nd_blocks : 0; }
+int pa_bj_nd_precision(void) { return g_bj.created && g_bj.nd_blocks > 0 ? pa_nd_precision() : 0; }
+
+/* Storage of the sparse factors of the next creates: 64 / 32 bits, 0 = PREALPS_BJ_ND_PRECISION (band blocks: fp64) */
+static int g_nd_bits = 0;
+int preAlps_hip_set_nd_precision(int bits) {
+  if (bits != 0 && bits != 32 && bits != 64)
+    return PA_FAIL("precision %d refused: 64 (double), 32 (single) or 0 (follow PREALPS_BJ_ND_PRECISION)", bits);
+  g_nd_bits = bits;
+  return 0;
+}
 double pa_bj_pairs_bytes(void) { return g_bj.created ? g_bj.pairs_bytes : 0.0; }
 double pa_bj_g4_bytes(void) { return g_bj.created ? g_bj.g4_bytes : 0.0; }
 /* blocks of the apply when it can leave the ECG Gram block [in | prev]^T out behind (pa_k_bj_gram_arm): every
@@ -158,6 +168,14 @@ int preAlps_BlockJacobiCreate(CPLM_Mat_CSR_t* A, int* rowPos, int sizeRowPos, in
   if (!op) return PA_FAIL("the operator must be built before the preconditioner");
   if (!A || !A->rowPtr || !rowPos || sizeRowPos != op->nparts + 1)
     return PA_FAIL(" wrong test 'A != NULL && sizeRowPos == nparts + 1'");
+  /* storage of the sparse factors (band blocks stay fp64): preAlps_hip_set_nd_precision, else the switch */
+  int nd_bits = g_nd_bits;
+  if (!nd_bits) {
+    const char* pe = getenv("PREALPS_BJ_ND_PRECISION");
+    if (!pe || !*pe || !strcmp(pe, "double")) nd_bits = 64;
+    else if (!strcmp(pe, "single")) nd_bits = 32;
+    else return PA_FAIL("PREALPS_BJ_ND_PRECISION=%s: expected double or single (storage of the sparse block factors)", pe);
+  }
   if (g_bj.created) preAlps_BlockJacobiFree();
   pa_bj_t* s = &g_bj;
   int np = op->part1 - op->part0, m = op->m, row_off = op->row_off;
@@ -550,7 +568,7 @@ int preAlps_BlockJacobiCreate(CPLM_Mat_CSR_t* A, int* rowPos, int sizeRowPos, in
     int* grow0 = (int*)malloc((size_t)np * sizeof(int));
     int x = 0, nd_fail = -1;
     for (int q = 0; q < np; ++q) { grow0[q] = rowPos[op->part0 + q]; if (is_nd[q]) ndl[x++] = q; }
-    int r2 = pa_nd_create(A, nnd, ndl, row0, nrows, grow0, m, &nd_fail);
+    int r2 = pa_nd_create(A, nnd, ndl, row0, nrows, grow0, m, nd_bits, &nd_fail);
     if (r2 == 2) rc = PA_FAIL("diagonal block is not SPD (global row %d)", row_off + nd_fail);
     else if (r2) rc = 1;
     free(ndl); free(grow0);

@@ -14,8 +14,12 @@
  *              -G = -(L_21 D^-1) T (D = diag L_11), so that the solves are products, not
  *              recurrences; twice -- column major for the forward sweep, row major for the
  *              backward sweep -- each sweep streams its copy once with coalesced loads;
- *   solve      level by level up the forest and down again (kernels.hip: k_nd_forward /
- *              k_nd_backward), one launch per level, t right-hand sides at once.
+ *   solve      level by level up the forest and down again (nd_apply.hip: k_nd_forward /
+ *              k_nd_backward), one launch per level, t right-hand sides at once;
+ *   precision  the panels are computed in fp64 and stored in fp64 or, on request
+ *              (PREALPS_BJ_ND_PRECISION=single, preAlps_hip_set_nd_precision(32)), both copies rounded
+ *              to fp32 from the same fp64 values: half the bytes the solve streams, all its
+ *              arithmetic still fp64, the preconditioner still exactly symmetric.
  *
  * Against the band factor of a 18^3-node elasticity block (17.5 k rows, band 1031: 281 MB in two
  * copies) this needs ~130 MB, and a level of the tree is thousands of independent workgroups
@@ -37,6 +41,7 @@ typedef struct {
   int* d_coff; int* d_ccoff; int* d_rows; int* d_src; double* d_dinv; double* d_F; double* d_B;
   double* d_contrib; size_t contrib_rows; int contrib_ts;
   double* d_Y; int m_local; double inv_dev;
+  float* d_F32; float* d_B32; int bits;      /* bits = 32: the panels live in d_F32 / d_B32 only */
   int nlevel; int* f_count; int** f_front; int** f_row0; int* b_count; int** b_front; int** b_col0;
   double bytes;
 } pa_nd_t;
@@ -45,12 +50,14 @@ static pa_nd_t g_nd;
 
 double pa_nd_factor_bytes(void) { return g_nd.created ? g_nd.bytes : 0.0; }
 int pa_nd_active(void) { return g_nd.created; }
+int pa_nd_precision(void) { return g_nd.created ? g_nd.bits : 0; }
 
 void pa_nd_free(void) {
   pa_nd_t* s = &g_nd;
   pa_rt_free(s->d_n); pa_rt_free(s->d_m); pa_rt_free(s->d_ld); pa_rt_free(s->d_offF); pa_rt_free(s->d_offB);
   pa_rt_free(s->d_rows_off); pa_rt_free(s->d_coff); pa_rt_free(s->d_ccoff); pa_rt_free(s->d_rows); pa_rt_free(s->d_src);
   pa_rt_free(s->d_dinv); pa_rt_free(s->d_F); pa_rt_free(s->d_B); pa_rt_free(s->d_contrib);
+  pa_rt_free(s->d_F32); pa_rt_free(s->d_B32);
   for (int i = 0; i < s->nlevel; ++i) {
     if (s->f_front) pa_rt_free(s->f_front[i]);
     if (s->f_row0) pa_rt_free(s->f_row0[i]);
@@ -325,7 +332,7 @@ static int front_factor(int f, int n, double* F) {
  * dimension ld, columns already divided by their pivots: I + Lhat_11 on top, Lhat_21 below):
  *   triangle   <- strictly lower part of T = (I + Lhat_11)^-1 (unit lower triangular),
  *   rows below <- -G, G = Lhat_21 T.
- * With these the solves are products (kernels.hip): forward a = T w and contribution -= G w,
+ * With these the solves are products (nd_apply.hip): forward a = T w and contribution -= G w,
  * backward z_1 = T^T D^-1 y_1 - G^T z_2 -- exactly transposed operators, so the block solve stays
  * symmetric.  wk: n * n + n doubles.  Returns the largest entry of T (I + Lhat_11) - I. */
 __attribute__((target_clones("avx2,fma", "default")))
@@ -702,7 +709,7 @@ static int nd_numeric_device(pa_nd_t* S, const nd_block_t* B, int nblk, const in
 /* ---- build ------------------------------------------------------------------------------------------------- */
 /* blocks: nblk local block ids q; row0[q] / nrows[q] local panel rows; grow0[q] global first row. */
 int pa_nd_create(const CPLM_Mat_CSR_t* A, int nblk, const int* blocks, const int* row0, const int* nrows,
-                 const int* grow0, int m_local, int* fail_row) {
+                 const int* grow0, int m_local, int bits, int* fail_row) {
   if (g_nd.created) pa_nd_free();
   if (nblk <= 0) return 0;
   pa_nd_t* S = &g_nd;
@@ -905,16 +912,39 @@ int pa_nd_create(const CPLM_Mat_CSR_t* A, int nblk, const int* blocks, const int
       *fail_row = B[x].row0 + B[x].tree.perm[B[x].tree.first[fg - sn0[x]] + fc];
     }
   }
+  /* single-precision storage: both copies rounded from the same fp64 panels (host path: the pair that was
+   * uploaded).  B is the exact transpose of F, so the rounded B is the exact transpose of the rounded F: the
+   * forward sweep applies some unit lower Ft, the backward sweep exactly Ft^T, and Ft^T D^-2 Ft stays
+   * symmetric positive definite.  Then the fp64 panels go; dinv, the contributions and Y stay fp64.  Set-up
+   * peak: the fp64 factor plus half of it. */
+  if (!rc && bits == 32) {
+    const double t_r = pa_wtime();
+    S->d_F32 = (float*)pa_rt_malloc((size_t)(totF + 64) * sizeof(float));
+    S->d_B32 = (float*)pa_rt_malloc((size_t)(totB + 64) * sizeof(float));
+    if (!S->d_F32 || !S->d_B32)
+      rc = PA_FAIL("allocating %.2f GB of single-precision block factors on the device failed: %s", 4e-9 * (double)(totF + totB), pa_rt_error());
+    else if (pa_k_nd_round(S->d_F, S->d_F32, (size_t)totF) || pa_k_nd_round(S->d_B, S->d_B32, (size_t)totB) || pa_rt_sync())
+      rc = PA_FAIL("rounding the block factors to single precision failed: %s", pa_rt_error());
+    if (!rc) {
+      pa_rt_free(S->d_F); pa_rt_free(S->d_B);
+      S->d_F = NULL; S->d_B = NULL;
+      if (trace)
+        fprintf(stderr, "[nd] factor stored in single precision: %.2f GB (fp64: %.2f GB; %.2f GB more at the set-up peak, "
+                        "while both exist), rounded in %.3f s\n", 4e-9 * (double)(totF + totB), 8e-9 * (double)(totF + totB),
+                4e-9 * (double)(totF + totB), pa_wtime() - t_r);
+    }
+  }
   free(h_n); free(h_m); free(h_ld); free(h_offF); free(h_offB); free(h_rows_off); free(h_coff); free(h_ccoff);
   free(h_rows); free(h_src); free(h_height); free(h_dinv); free(sn0); free(bF); free(bB);
   for (int x = 0; x < nblk; ++x) nd_block_free(&B[x]);
   free(B);
   if (rc) { pa_nd_free(); return rc == 2 ? 2 : 1; }
-  S->nsn = nsn; S->contrib_rows = (size_t)totc; S->m_local = m_local; S->bytes = 8.0 * (double)(totF + totB);
+  S->nsn = nsn; S->contrib_rows = (size_t)totc; S->m_local = m_local; S->bits = bits;
+  S->bytes = (bits == 32 ? 4.0 : 8.0) * (double)(totF + totB);
   pa_nd_plan_t* pl = &S->plan;
   pl->n = S->d_n; pl->m = S->d_m; pl->ld = S->d_ld; pl->offF = S->d_offF; pl->offB = S->d_offB; pl->rows_off = S->d_rows_off;
   pl->coff = S->d_coff; pl->ccoff = S->d_ccoff; pl->rows = S->d_rows; pl->src = S->d_src; pl->dinv = S->d_dinv;
-  pl->F = S->d_F; pl->B = S->d_B;
+  pl->F = S->d_F; pl->B = S->d_B; pl->F32 = S->d_F32; pl->B32 = S->d_B32;
   pl->nlevel = S->nlevel; pl->f_count = S->f_count; pl->b_count = S->b_count;
   pl->f_front = (const int* const*)S->f_front; pl->f_row0 = (const int* const*)S->f_row0;
   pl->b_front = (const int* const*)S->b_front; pl->b_col0 = (const int* const*)S->b_col0;

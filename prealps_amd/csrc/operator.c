@@ -1417,6 +1417,7 @@ int preAlps_hip_get_stat(const char* key, double* value) {
   else if (!strcmp(key, "bj_pairs_bytes")) *value = pa_bj_pairs_bytes();
   else if (!strcmp(key, "bj_g4_bytes")) *value = pa_bj_g4_bytes();
   else if (!strcmp(key, "bj_nd_inverse_dev")) *value = pa_nd_inverse_deviation();
+  else if (!strcmp(key, "bj_nd_precision")) *value = pa_bj_nd_precision();
   else return 1;
   return 0;
 }

@@ -291,13 +291,14 @@ int pa_k_bj_apply(const pa_bj_plan_t* pl, int ts, const double* in, double* out)
 
 /* ---- sparse block solve for large diagonal blocks (nd.c) --------------------------------- */
 /* Supernodes of a nested-dissection Cholesky factor, all blocks of the process in one numbering.
- * Supernode s: n[s] pivot columns, m[s] rows below, panel P = [T ; -G] (see kernels.hip) twice:
+ * Supernode s: n[s] pivot columns, m[s] rows below, panel P = [T ; -G] (see nd_apply.hip) twice:
  * F + offF[s] column major with leading dimension ld[s] >= n + m, B + offB[s] row major with row
  * length PA_ND_LD(n); only the entries below the diagonal are read.  rows[rows_off[s] + r] =
  * local panel row of front row r; src[2 (rows_off[s] + r) + c] = where front row r finds the
  * contribution of child c (row of its vector, -1: none), that vector starting at row
  * ccoff[2 s + c] of `contrib`; this supernode's own contribution starts at row coff[s].
- * dinv[local row] = 1 / L(row, row).  Y: scratch panel for the forward result (local rows). */
+ * dinv[local row] = 1 / L(row, row).  Y: scratch panel for the forward result (local rows).
+ * Kernels: nd_apply.hip. */
 /* leading dimensions of both copies: multiples of 128 bytes, so that the 512-byte segment a
  * wavefront loads never straddles an extra cache line */
 #define PA_ND_LD(x) (((x) + 15) & ~15)
@@ -305,6 +306,7 @@ typedef struct {
   const int* n; const int* m; const int* ld; const long long* offF; const long long* offB; const int* rows_off;
   const int* coff; const int* ccoff; const int* rows; const int* src; const double* dinv;
   const double* F; const double* B; double* contrib; double* Y;
+  const float* F32; const float* B32;   /* non-NULL: the same two copies rounded to fp32 (F / B released), read instead */
   int nlevel;                  /* levels of the forest, bottom-up; host arrays of device pointers: */
   const int* f_count; const int* const* f_front; const int* const* f_row0;   /* forward: (front, first front row) per workgroup */
   const int* b_count; const int* const* b_front; const int* const* b_col0;   /* backward: (front, first pivot column) per workgroup */
@@ -341,6 +343,8 @@ int pa_k_ndf_check(const pa_ndf_args_t* a, const int* fronts, int nfronts, int n
 int pa_nd_chunk_rows(void);           /* front rows per forward workgroup */
 int pa_nd_block_cols(void);           /* pivot columns per backward workgroup */
 int pa_k_nd_apply(const pa_nd_plan_t* pl, int ts, const double* in, double* out);
+/* dst[i] = src[i] rounded to the nearest float, i < n (nd_apply.hip) */
+int pa_k_nd_round(const double* src, float* dst, size_t n);
 
 #ifdef __cplusplus
 }

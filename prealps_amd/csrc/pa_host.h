@@ -94,20 +94,22 @@ int pa_nd_order(int n, const int* rp, const int* ci, int leaf_rows, pa_nd_tree_t
 void pa_nd_tree_free(pa_nd_tree_t* t);
 
 /* sparse block solve for large blocks (nd.c); returns 0, 1 (error reported) or 2 (*fail_row = local
- * panel row of a non-positive pivot) */
+ * panel row of a non-positive pivot).  bits: 64 or 32 = storage of the factor panels */
 int pa_nd_create(const CPLM_Mat_CSR_t* A, int nblk, const int* blocks, const int* row0, const int* nrows,
-                 const int* grow0, int m_local, int* fail_row);
+                 const int* grow0, int m_local, int bits, int* fail_row);
 int pa_nd_apply(int ts, const double* in, double* out);
 void pa_nd_free(void);
 double pa_nd_factor_bytes(void);
 double pa_nd_inverse_deviation(void);   /* largest |T (I + Lhat) - I| over the fronts of the last pa_nd_create */
 int pa_nd_active(void);
+int pa_nd_precision(void);              /* 64 / 32: storage of the factor panels, 0: no factor */
 
 double pa_bj_factor_bytes(void);
 int pa_bj_max_bandwidth(void);
 double pa_bj_setup_seconds(int which);   /* 0: ordering + band Cholesky, 1: sweep layouts + upload */
 int pa_bj_nparts(void);
 int pa_bj_nd_blocks(void);
+int pa_bj_nd_precision(void);       /* storage of the sparse factors (64 / 32), 0 if no block has one */
 int pa_bj_gram_blocks(void);       /* blocks of an apply that can leave [in | prev]^T out behind (0: cannot) */
 double pa_bj_g4_bytes(void);        /* bytes of the one-copy records of bj_g4.hip, 0 if absent */
 double pa_bj_pairs_bytes(void);     /* bytes of the paired sweep records (both sweeps), 0 if absent */

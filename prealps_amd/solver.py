@@ -261,10 +261,23 @@ class EcgProblem:
         return part
 
     # -- pieces of the driver --------------------------------------------------
-    def create_block_jacobi(self):
-        check(self.L.preAlps_BlockJacobiCreate(C.byref(self.A), self._rowpos_ptr, self._rowpos_n,
-                                               self._colpos_ptr, self._colpos_n),
-              "preAlps_BlockJacobiCreate")
+    def create_block_jacobi(self, nd_precision=None):
+        """nd_precision: storage of the sparse factors of large blocks -- None follows
+        PREALPS_BJ_ND_PRECISION, "double" / "single" select it for this create (band blocks stay fp64).
+        With a value, the library's setting (preAlps_hip_set_nd_precision) is 0 again afterwards: a value
+        set earlier through the C entry is not restored."""
+        bits = {None: 0, "double": 64, "single": 32}.get(nd_precision)
+        if bits is None:
+            raise ValueError("nd_precision must be None, 'double' or 'single', not %r" % (nd_precision,))
+        if bits:
+            check(self.L.preAlps_hip_set_nd_precision(bits), "preAlps_hip_set_nd_precision")
+        try:
+            check(self.L.preAlps_BlockJacobiCreate(C.byref(self.A), self._rowpos_ptr, self._rowpos_n,
+                                                   self._colpos_ptr, self._colpos_n),
+                  "preAlps_BlockJacobiCreate")
+        finally:
+            if bits:
+                self.L.preAlps_hip_set_nd_precision(0)
         self.has_precond = True
 
     def reference_rhs(self):

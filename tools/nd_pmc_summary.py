@@ -7,7 +7,7 @@ for r in csv.DictReader(open(sys.argv[1])):
     if r["Counter_Name"] != "FETCH_SIZE":
         continue
     k = re.sub(r"\(.*$", "", r["Kernel_Name"].replace("void ", "").replace("(anonymous namespace)::", ""))
-    if not k.startswith("k_nd_"):
+    if not k.startswith("k_nd_") or k == "k_nd_round":      # (k_nd_round: set-up, not part of an apply)
         continue
     acc[k][0] += 1
     acc[k][1] += float(r["Counter_Value"])
