@@ -127,6 +127,15 @@ void preAlps_hip_graphs(int on);
  * PREALPS_BJ_ND_PRECISION (`double`, the default, or `single`; any other value makes the create fail).  Band
  * blocks -- every block without the sparse factor -- stay fp64 either way.  Other values are refused; needs no GPU. */
 int preAlps_hip_set_nd_precision(int bits);
+/* Storage of the one-copy band records (the factor that the block solve of panels of up to 4 columns, and of 5 to 8
+ * columns when PREALPS_BJ_G4_WIDE allows, reads in both sweeps), from the next preAlps_BlockJacobiCreate on:
+ * 64 = fp64; 32 = fp32 (the strictly lower part of L D^-1 rounded once, D^-2 and every operation of the apply in
+ * fp64: both sweeps read the same record, so the block solve stays exactly symmetric positive definite; half the
+ * bytes those launches stream); 0 (default) = follow PREALPS_BJ_BAND_PRECISION (`double`, the default, or `single`;
+ * any other value makes the create fail).  Independent of preAlps_hip_set_nd_precision.  The plain fp64 records
+ * that the kernels for 9 to 16 columns and for wide bands read are not touched: those applies keep the fp64 bits.
+ * Other values are refused; needs no GPU. */
+int preAlps_hip_set_band_precision(int bits);
 /* 1: the two driver loops run an Orthodir iteration of a solver described by the arguments with the block solve
  * before the update of X and R (one finish and one row pass per iteration; bitwise the same results), 0: in the
  * order of preAlps_ECGIterate.  PREALPS_ECG_SOLVE_FIRST=0 (read here as a solver reads it when it is reset) keeps
@@ -166,7 +175,11 @@ int preAlps_hip_panel_permute_solve(const CPLM_Mat_Dense_t* Z, CPLM_Mat_Dense_t*
  * stored: the sparse ones at 4 bytes per entry in single precision), "bj_max_bandwidth", "bj_parts_local",
  * "bj_nd_blocks" (blocks with the sparse factor), "bj_nd_inverse_dev" (largest deviation of its inverted
  * pivot triangles), "bj_nd_precision" (64 / 32: storage of the sparse factors, 0: no block has one; band
- * blocks are always fp64), ...  Returns non-zero for unknown keys. */
+ * blocks are always fp64 under that switch), "bj_band_precision" (64 / 32: storage of the one-copy band records,
+ * 0: no class has them, e.g. PREALPS_BJ_G4=0), "bj_g4_bytes" (bytes of those records as stored: half in single
+ * precision; "bj_factor_bytes" does not count them), "bj_g4_last_ring" / "bj_g4_last_bits" /
+ * "bj_g4_last_pipelined" (the last launch that read them: LDS ring depth, storage bits of the records, 1 = the
+ * pipelined few-blocks chain), ...  Returns non-zero for unknown keys. */
 int preAlps_hip_get_stat(const char* key, double* value);
 /* A stopwatch made of two hipEvents on the library stream: start records the
  * first, stop records the second, waits for it and returns the device time

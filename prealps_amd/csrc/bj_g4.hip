@@ -57,6 +57,9 @@
 extern "C" {
 extern const double* pa_g4_gram_prev;
 extern double* pa_g4_gram_part;
+// what the last launch was: ring depth, storage bits of the records, 1 = the pipelined few-blocks chain
+// (preAlps_hip_get_stat "bj_g4_last_ring" / "bj_g4_last_bits" / "bj_g4_last_pipelined")
+extern int pa_g4_last[3];
 }
 
 namespace {
@@ -74,15 +77,17 @@ inline hipStream_t cur_stream() { return (hipStream_t)pa_rt_stream(); }
 //   position  w            zeros (where every row outside the record is sent);
 //   positions w+1 .. w+3   rows 1 .. 3 of the strictly lower corner Lt(g, g) (zero on and above the
 //                          diagonal), negated as well.
-// Chunks of two groups; the groups a block does not have are zero.
+// Chunks of two groups; the groups a block does not have are zero.  RT = storage type of the records: double, or
+// float (PREALPS_BJ_BAND_PRECISION=single) -- the same fp64 value rounded once, at the same position.
+template <typename RT>
 __global__ __launch_bounds__(256) void k_bj_g4_setup(const int* __restrict__ list, const int* __restrict__ nrows,
                                                       const int* __restrict__ bw, const long long* __restrict__ off,
                                                       const long long* __restrict__ off2,
-                                                      const double* __restrict__ L, double* __restrict__ Lg4) {
+                                                      const double* __restrict__ L, RT* __restrict__ Lg4) {
   const int p = list[blockIdx.x];
   const int b = nrows[p], w = bw[p], wr = (w + 2) & ~1, nr = w + 4;
   const double* __restrict__ rec = L + off[p];
-  double* __restrict__ dst = Lg4 + off2[p];
+  RT* __restrict__ dst = Lg4 + off2[p];
   const int ngrp = 2 * ((b + 7) / 8);
   for (int e = threadIdx.x; e < ngrp * nr * 4; e += blockDim.x) {
     const int g = e / (4 * nr), r = e - g * 4 * nr, pos = r >> 2, pv = r & 3;
@@ -93,12 +98,14 @@ __global__ __launch_bounds__(256) void k_bj_g4_setup(const int* __restrict__ lis
       const int row = 4 * g + rho, d = row - piv;
       if (row < b && piv < b && d >= 1 && d <= w) v = -rec[(size_t)piv * wr + d - 1];
     }
-    dst[e] = v;
+    dst[e] = (RT)v;
   }
 }
 
 // ----------------------------------------------------------------------------------- apply ----
-__device__ __forceinline__ void g4_issue_chunk(const double* __restrict__ rec, int chunk_doubles, int chunk,
+// (chunk_doubles: the bytes of a chunk / 8, whatever the storage type of the records -- the LDS is counted in doubles)
+template <typename RT>
+__device__ __forceinline__ void g4_issue_chunk(const RT* __restrict__ rec, int chunk_doubles, int chunk,
                                                double* lbuf, int lane) {
   const int nbytes = chunk_doubles * 8;
   const char* g = reinterpret_cast<const char*>(rec) + (size_t)chunk * nbytes + lane * 16;
@@ -166,8 +173,9 @@ __device__ __forceinline__ double row_ror(double v) {
 }
 
 // s_waitcnt lgkmcnt(0) that the compiler sees as the producer of everything read before it
-template <int DQ>
-__device__ __forceinline__ void g4_wait_cf(double (&cf)[DQ], double& c0, double& c1, double& c2) {
+// (RT = double or float: the registers the ds_read_b64 / ds_read_b32 before it wrote)
+template <int DQ, typename RT>
+__device__ __forceinline__ void g4_wait_cf(RT (&cf)[DQ], RT& c0, RT& c1, RT& c2) {
   if constexpr (DQ == 3) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(cf[0]), "+v"(cf[1]), "+v"(cf[2]));
   else if constexpr (DQ == 4) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(cf[0]), "+v"(cf[1]), "+v"(cf[2]), "+v"(cf[3]));
   else if constexpr (DQ == 5) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(cf[0]), "+v"(cf[1]), "+v"(cf[2]), "+v"(cf[3]), "+v"(cf[4]));
@@ -201,6 +209,13 @@ __device__ __forceinline__ double g4_quad_bcast(double x) {      // quad GQ of e
 //          operand of the substitution: forward Lt(lo, hi) (row lo, column hi), backward Lt(hi, lo)
 struct g4_lane { int cX; unsigned aX; unsigned cg; int hi, blk; };
 
+// One record entry out of the LDS: fp64 records with ds_read_b64, fp32 records with ds_read_b32 (widened by the
+// caller in plain C++ behind g4_wait_cf, so that the compiler's hazard recogniser sees the conversion).
+// A record row is four pivots: G4_ROWB bytes.
+__device__ __forceinline__ void g4_lds_read(double& v, unsigned ad) { asm volatile("ds_read_b64 %0, %1" : "=v"(v) : "v"(ad)); }
+__device__ __forceinline__ void g4_lds_read(float& v, unsigned ad) { asm volatile("ds_read_b32 %0, %1" : "=v"(v) : "v"(ad)); }
+template <typename RT> constexpr unsigned g4_rowb() { return 4u * (unsigned)sizeof(RT); }
+
 // The 4 x 4 substitution on the matrix cores, in place in the pivot tile: step k adds (column k of the
 // negated strictly lower corner) x (row k of the group) to the group's rows -- a 4 x 4 x 4 product whose A
 // operand is zero but for that column, and zero altogether in the three blocks that do not hold the group,
@@ -221,82 +236,90 @@ __device__ __forceinline__ void g4_corner_solve(double (&T)[NC * NT], double a0,
 // One group of four pivots, forward: Q = tile of the pivots, GQ = their block inside it, `cur` = LDS
 // byte address of the group's record.  NC = sets of four panel columns the wavefront carries (1, or 2
 // for 8-column panels: the record is read once for both), set c in T[c * NT ..].
-template <int NC, int NT, int DQ, int Q, int GQ>
+template <typename RT, int NC, int NT, int DQ, int Q, int GQ>
 __device__ __forceinline__ void g4_fwd_group(double (&T)[NC * NT], unsigned cur, int w, g4_lane ln) {
   // (opaque copy: without it the compiler keeps the clamped index of every (tile offset, group) pair
   // of the unrolled sweeps alive in registers and spills)
   asm volatile("" : "+v"(ln.cX));
-  const unsigned zero_ad = cur + (unsigned)w * 32u, mine = zero_ad + ln.cg;
+  constexpr unsigned RB = g4_rowb<RT>();
+  const unsigned zero_ad = cur + (unsigned)w * RB, mine = zero_ad + ln.cg;
   const bool here = ln.blk == GQ;
-  double a0, a1, a2;          // steps 0, 1, 2: column k of the corner lives in the lanes hi == k
+  RT a0, a1, a2;              // steps 0, 1, 2: column k of the corner lives in the lanes hi == k
   {
     const unsigned ad0 = (here && ln.hi == 0) ? mine : zero_ad;
     const unsigned ad1 = (here && ln.hi == 1) ? mine : zero_ad;
     const unsigned ad2 = (here && ln.hi == 2) ? mine : zero_ad;
-    asm volatile("ds_read_b64 %0, %1" : "=v"(a0) : "v"(ad0));
-    asm volatile("ds_read_b64 %0, %1" : "=v"(a1) : "v"(ad1));
-    asm volatile("ds_read_b64 %0, %1" : "=v"(a2) : "v"(ad2));
+    g4_lds_read(a0, ad0);
+    g4_lds_read(a1, ad1);
+    g4_lds_read(a2, ad2);
   }
-  double cf[DQ];
+  RT cf[DQ];
 #pragma unroll
   for (int dq = 0; dq < DQ; ++dq) {
-    cf[dq] = 0.0;
+    cf[dq] = RT(0);
     if (Q + dq < NT) {
       const unsigned s = min((unsigned)(ln.cX - (16 * dq - 4 * GQ)), (unsigned)w);
-      const unsigned ad = cur + s * 32u + ln.aX;
-      asm volatile("ds_read_b64 %0, %1" : "=v"(cf[dq]) : "v"(ad));
+      const unsigned ad = cur + s * RB + ln.aX;
+      g4_lds_read(cf[dq], ad);
     }
   }
   g4_wait_cf<DQ>(cf, a0, a1, a2);
-  g4_corner_solve<NC, NT, Q>(T, a0, a1, a2);            // y_g = Lt(g, g)^-1 x_g, in place
+  double cw[DQ];              // (fp32 records: widened here, behind the wait, once for all column sets)
+#pragma unroll
+  for (int dq = 0; dq < DQ; ++dq) cw[dq] = (double)cf[dq];
+  g4_corner_solve<NC, NT, Q>(T, (double)a0, (double)a1, (double)a2);            // y_g = Lt(g, g)^-1 x_g, in place
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     const double yg = g4_quad_bcast<GQ>(T[c * NT + Q]);  // B operand: the group's rows in every block
 #pragma unroll
     for (int dq = 0; dq < DQ; ++dq)
-      if (Q + dq < NT) T[c * NT + Q + dq] = __builtin_amdgcn_mfma_f64_4x4x4f64(cf[dq], yg, T[c * NT + Q + dq], 0, 0, 0);
+      if (Q + dq < NT) T[c * NT + Q + dq] = __builtin_amdgcn_mfma_f64_4x4x4f64(cw[dq], yg, T[c * NT + Q + dq], 0, 0, 0);
   }
 }
 
 // The same group, backward: r = y_g - Lt(below, g)^T z(below), then z_g = Lt(g, g)^-T r.
-template <int NC, int NT, int DQ, int Q, int GQ>
+template <typename RT, int NC, int NT, int DQ, int Q, int GQ>
 __device__ __forceinline__ void g4_bwd_group(double (&T)[NC * NT], unsigned cur, int w, g4_lane ln) {
   asm volatile("" : "+v"(ln.cX));
-  const unsigned zero_ad = cur + (unsigned)w * 32u, mine = zero_ad + ln.cg;
+  constexpr unsigned RB = g4_rowb<RT>();
+  const unsigned zero_ad = cur + (unsigned)w * RB, mine = zero_ad + ln.cg;
   const bool here = ln.blk == GQ;
-  double a3, a2, a1;          // steps 3, 2, 1: row k of the corner, transposed, lives in the lanes hi == k
+  RT a3, a2, a1;              // steps 3, 2, 1: row k of the corner, transposed, lives in the lanes hi == k
   {
     const unsigned ad3 = (here && ln.hi == 3) ? mine : zero_ad;
     const unsigned ad2 = (here && ln.hi == 2) ? mine : zero_ad;
     const unsigned ad1 = (here && ln.hi == 1) ? mine : zero_ad;
-    asm volatile("ds_read_b64 %0, %1" : "=v"(a3) : "v"(ad3));
-    asm volatile("ds_read_b64 %0, %1" : "=v"(a2) : "v"(ad2));
-    asm volatile("ds_read_b64 %0, %1" : "=v"(a1) : "v"(ad1));
+    g4_lds_read(a3, ad3);
+    g4_lds_read(a2, ad2);
+    g4_lds_read(a1, ad1);
   }
-  double cf[DQ];
+  RT cf[DQ];
 #pragma unroll
   for (int dq = 0; dq < DQ; ++dq) {
-    cf[dq] = 0.0;
+    cf[dq] = RT(0);
     if (Q + dq < NT) {
       const unsigned s = min((unsigned)(ln.cX - (16 * dq - 4 * GQ)), (unsigned)w);
-      const unsigned ad = cur + s * 32u + ln.aX;
-      asm volatile("ds_read_b64 %0, %1" : "=v"(cf[dq]) : "v"(ad));
+      const unsigned ad = cur + s * RB + ln.aX;
+      g4_lds_read(cf[dq], ad);
     }
   }
   g4_wait_cf<DQ>(cf, a3, a2, a1);
+  double cw[DQ];
+#pragma unroll
+  for (int dq = 0; dq < DQ; ++dq) cw[dq] = (double)cf[dq];
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     double acc = 0.0;
 #pragma unroll
     for (int dq = 0; dq < DQ; ++dq)
-      if (Q + dq < NT) acc = __builtin_amdgcn_mfma_f64_4x4x4f64(cf[dq], T[c * NT + Q + dq], acc, 0, 0, 0);
+      if (Q + dq < NT) acc = __builtin_amdgcn_mfma_f64_4x4x4f64(cw[dq], T[c * NT + Q + dq], acc, 0, 0, 0);
     // every block of the accumulator holds the sum over ITS four rows of each tile: add the four
     // blocks (rotations by 4 and 8 lanes inside the 16-lane rows); the group's lanes take the total
     acc += row_ror<4>(acc);
     acc += row_ror<8>(acc);
     T[c * NT + Q] += here ? acc : 0.0;
   }
-  g4_corner_solve<NC, NT, Q>(T, a3, a2, a1);
+  g4_corner_solve<NC, NT, Q>(T, (double)a3, (double)a2, (double)a1);
 }
 
 // The chunks of a sweep (two groups each) go through a ring of `ring` LDS buffers (a power of two, lstride
@@ -305,8 +328,8 @@ __device__ __forceinline__ void g4_bwd_group(double (&T)[NC * NT], unsigned cur,
 // after chunk c's own -- ring - 1 chunks are in flight while it computes.  What a lone block pays per
 // chunk is then its arithmetic, not the memory latency: it decides how long the blocks of the last,
 // partly filled round take, and everything when a GPU holds fewer blocks than it has SIMDs.
-template <int NC, int NT, int DQ, int Q, int H>
-__device__ __forceinline__ void g4_fwd_chunk(double (&T)[NC * NT], int b, int w, const double* __restrict__ rec,
+template <typename RT, int NC, int NT, int DQ, int Q, int H>
+__device__ __forceinline__ void g4_fwd_chunk(double (&T)[NC * NT], int b, int w, const RT* __restrict__ rec,
                                              int chunk_doubles, double* lds0, int lstride, int lane, g4_lane ln,
                                              int ring) {
   constexpr int C = 2 * Q + H;
@@ -315,19 +338,19 @@ __device__ __forceinline__ void g4_fwd_chunk(double (&T)[NC * NT], int b, int w,
   if (cn < nch) g4_issue_chunk(rec, chunk_doubles, cn, lds0 + (cn & (ring - 1)) * lstride, lane);
   g4_wait_vm(min(ring - 1, nch - 1 - C) * nld);
   const unsigned cur = (unsigned)(uintptr_t)(lds_ptr)(lds0 + (C & (ring - 1)) * lstride);
-  g4_fwd_group<NC, NT, DQ, Q, 2 * H>(T, cur, w, ln);
-  g4_fwd_group<NC, NT, DQ, Q, 2 * H + 1>(T, cur + (unsigned)(w + 4) * 32u, w, ln);
+  g4_fwd_group<RT, NC, NT, DQ, Q, 2 * H>(T, cur, w, ln);
+  g4_fwd_group<RT, NC, NT, DQ, Q, 2 * H + 1>(T, cur + (unsigned)(w + 4) * g4_rowb<RT>(), w, ln);
   asm volatile("" ::: "memory");
 }
-template <int NC, int NT, int DQ, int Q>
-__device__ __forceinline__ void g4_fwd_tiles(double (&T)[NC * NT], int b, int w, const double* __restrict__ rec,
+template <typename RT, int NC, int NT, int DQ, int Q>
+__device__ __forceinline__ void g4_fwd_tiles(double (&T)[NC * NT], int b, int w, const RT* __restrict__ rec,
                                              int chunk_doubles, double* lds0, int lstride, int lane, g4_lane ln,
                                              int ring) {
   if constexpr (Q < NT) {
     if (16 * Q < b) {
-      g4_fwd_chunk<NC, NT, DQ, Q, 0>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, ln, ring);
-      if (16 * Q + 8 < b) g4_fwd_chunk<NC, NT, DQ, Q, 1>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, ln, ring);
-      g4_fwd_tiles<NC, NT, DQ, Q + 1>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, ln, ring);
+      g4_fwd_chunk<RT, NC, NT, DQ, Q, 0>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, ln, ring);
+      if (16 * Q + 8 < b) g4_fwd_chunk<RT, NC, NT, DQ, Q, 1>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, ln, ring);
+      g4_fwd_tiles<RT, NC, NT, DQ, Q + 1>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, ln, ring);
     }
   }
 }
@@ -344,8 +367,13 @@ __device__ __forceinline__ void g4_fwd_tiles(double (&T)[NC * NT], int b, int w,
 // older than ITS chunk request, takes the product.  One register pair in flight; tile 0 is taken behind the sweep.
 struct g4_gram { const double* prev; unsigned base, xs; double ap, gp; };     // prev + (base + map * xs): the lane's entry of a row
 
-template <int NC, int NT, int DQ, int Q, int H, bool GP>
-__device__ __forceinline__ void g4_bwd_chunk(double (&T)[NC * NT], int b, int w, const double* __restrict__ rec,
+//
+// fp32 records (RT = float): with ring >= 4 the wait of chunk (Q - 1, 1) allows ring - 1 chunk requests to be
+// outstanding, and the load of gr.ap sits among the youngest of them (behind the request of chunk (Q, 0), in front
+// of this chunk's own) -- it is waited for explicitly before the product reads it: everything but this chunk's own
+// request, if it made one.  (ring 2: the wait above already says exactly that.)
+template <typename RT, int NC, int NT, int DQ, int Q, int H, bool GP>
+__device__ __forceinline__ void g4_bwd_chunk(double (&T)[NC * NT], int b, int w, const RT* __restrict__ rec,
                                              int chunk_doubles, double* lds0, int lstride, int lane, g4_lane ln,
                                              int ring, g4_gram& gr, int trow, const unsigned (&mpk)[(NT + 3) / 4]) {
   constexpr int C = 2 * Q + H;
@@ -365,26 +393,27 @@ __device__ __forceinline__ void g4_bwd_chunk(double (&T)[NC * NT], int b, int w,
   }
   if constexpr (GP && H == 1 && Q + 1 < NT) {
     if (16 * (Q + 1) < b) {             // the rows of tile Q + 1 are here (requested before this chunk's own request)
+      if constexpr (sizeof(RT) == 4) g4_wait_vm(cn >= 0 && C < nch - 1 ? nld : 0);
       asm volatile("" : "+v"(gr.ap));
       const double z = 16 * (Q + 1) + trow < b ? T[Q + 1] : 0.0;
       gr.gp = __builtin_amdgcn_mfma_f64_4x4x4f64(gr.ap, z, gr.gp, 0, 0, 0);
     }
   }
   const unsigned cur = (unsigned)(uintptr_t)(lds_ptr)(lds0 + (C & (ring - 1)) * lstride);
-  g4_bwd_group<NC, NT, DQ, Q, 2 * H + 1>(T, cur + (unsigned)(w + 4) * 32u, w, ln);
-  g4_bwd_group<NC, NT, DQ, Q, 2 * H>(T, cur, w, ln);
+  g4_bwd_group<RT, NC, NT, DQ, Q, 2 * H + 1>(T, cur + (unsigned)(w + 4) * g4_rowb<RT>(), w, ln);
+  g4_bwd_group<RT, NC, NT, DQ, Q, 2 * H>(T, cur, w, ln);
   asm volatile("" ::: "memory");
 }
-template <int NC, int NT, int DQ, int Q, bool GP>
-__device__ __forceinline__ void g4_bwd_tiles(double (&T)[NC * NT], int b, int w, const double* __restrict__ rec,
+template <typename RT, int NC, int NT, int DQ, int Q, bool GP>
+__device__ __forceinline__ void g4_bwd_tiles(double (&T)[NC * NT], int b, int w, const RT* __restrict__ rec,
                                              int chunk_doubles, double* lds0, int lstride, int lane, g4_lane ln,
                                              int ring, g4_gram& gr, int trow, const unsigned (&mpk)[(NT + 3) / 4]) {
   if constexpr (Q >= 0) {
     if (16 * Q < b) {
-      if (16 * Q + 8 < b) g4_bwd_chunk<NC, NT, DQ, Q, 1, GP>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, ln, ring, gr, trow, mpk);
-      g4_bwd_chunk<NC, NT, DQ, Q, 0, GP>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, ln, ring, gr, trow, mpk);
+      if (16 * Q + 8 < b) g4_bwd_chunk<RT, NC, NT, DQ, Q, 1, GP>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, ln, ring, gr, trow, mpk);
+      g4_bwd_chunk<RT, NC, NT, DQ, Q, 0, GP>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, ln, ring, gr, trow, mpk);
     }
-    g4_bwd_tiles<NC, NT, DQ, Q - 1, GP>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, ln, ring, gr, trow, mpk);
+    g4_bwd_tiles<RT, NC, NT, DQ, Q - 1, GP>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, ln, ring, gr, trow, mpk);
   }
 }
 
@@ -563,13 +592,16 @@ __device__ __forceinline__ void g4_bwd_tiles_p(double (&T)[NT], int b, const dou
 // One wavefront per block.  NT tiles of 16 rows (b <= 16 NT), DQ = tiles a group's record reaches
 // (w + 15 < 16 DQ).  `xs` = row stride of the panels in doubles (2, 4; 8 / 16 when the kernel is
 // launched on a 4-column slice of a wider panel), `ncol` <= 4 columns starting at `in` / `out`.
-template <int NC, int NT, int DQ, int OCC, bool GP, bool PIPE = false>
+// RT = storage type of the records (double; float = PREALPS_BJ_BAND_PRECISION=single: a record row is 16 bytes, a
+// chunk 32 (w + 4) bytes, every entry widened to fp64 before the matrix cores see it; the plain chain only).
+template <int NC, int NT, int DQ, int OCC, bool GP, bool PIPE = false, typename RT = double>
 __global__ __launch_bounds__(256, OCC) void k_bj_g4(
     const int* __restrict__ list, int count, const int* __restrict__ row0, const int* __restrict__ nrows,
     const int* __restrict__ bw, const long long* __restrict__ off2, const int* __restrict__ map_f,
-    const double* __restrict__ Lg4, const double* __restrict__ invd_f, int lds_per_wave, int ring, int xs, int ncol,
+    const RT* __restrict__ Lg4, const double* __restrict__ invd_f, int lds_per_wave, int ring, int xs, int ncol,
     const double* __restrict__ in, double* __restrict__ out, const double* __restrict__ gprev,
     double* __restrict__ gpart) {
+  static_assert(!PIPE || sizeof(RT) == 8, "the pipelined chain reads fp64 records");
   extern __shared__ double smem[];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int pi = blockIdx.x * (blockDim.x >> 6) + wave;
@@ -581,18 +613,18 @@ __global__ __launch_bounds__(256, OCC) void k_bj_g4(
   const long long o64 = off2[p];
   const size_t o = ((size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(o64 >> 32)) << 32) |
                    (unsigned)__builtin_amdgcn_readfirstlane((int)o64);
-  const double* __restrict__ rec = Lg4 + o;
+  const RT* __restrict__ rec = Lg4 + o;
   double* lds0 = smem + (size_t)wave * lds_per_wave;
   const int lstride = ((lds_per_wave / ring) >> 7) << 7;      // (whole KiB: the launcher may pad lds_per_wave)
-  const int chunk_doubles = 8 * (w + 4);
+  const int chunk_doubles = (int)sizeof(RT) * (w + 4);        // two groups of (w + 4) rows x 4 pivots, in units of 8 bytes
   const int hi = lane >> 4, blk = (lane >> 2) & 3, lo = lane & 3;
   // tile layout (D / B operand): row 4 blk + hi of the tile, column lo
   const int trow = 4 * blk + hi;
   // A operand, forward: row 4 blk + lo of the tile against pivot hi; backward: row 4 blk + hi against pivot lo
   g4_lane lf;
   lf.cX = w + 3 - (4 * blk + lo);
-  lf.aX = (unsigned)hi * 8u;
-  lf.cg = (unsigned)lo * 32u + (unsigned)hi * 8u;      // Lt(lo, hi): row lo of the corner, column hi
+  lf.aX = (unsigned)hi * (unsigned)sizeof(RT);
+  lf.cg = (unsigned)lo * g4_rowb<RT>() + (unsigned)hi * (unsigned)sizeof(RT);      // Lt(lo, hi): row lo of the corner, column hi
   lf.hi = hi;
   lf.blk = blk;
 
@@ -649,7 +681,7 @@ __global__ __launch_bounds__(256, OCC) void k_bj_g4(
     g4_ops_wait<DQ>(opA);
     g4_fwd_tiles_p<NT, DQ, 0>(T, b, rec, chunk_doubles, lds0, lane, pf, opA, opB);
   } else {
-    g4_fwd_tiles<NC, NT, DQ, 0>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, lf, ring);
+    g4_fwd_tiles<RT, NC, NT, DQ, 0>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, lf, ring);
   }
 
   // y = D^-2 a
@@ -683,8 +715,8 @@ __global__ __launch_bounds__(256, OCC) void k_bj_g4(
     const int hi2 = l2 >> 4, blk2 = (l2 >> 2) & 3, lo2 = l2 & 3;
     g4_lane lb;
     lb.cX = w + 3 - (4 * blk2 + hi2);
-    lb.aX = (unsigned)lo2 * 8u;
-    lb.cg = (unsigned)hi2 * 32u + (unsigned)lo2 * 8u;    // Lt(hi, lo): the transposed corner
+    lb.aX = (unsigned)lo2 * (unsigned)sizeof(RT);
+    lb.cg = (unsigned)hi2 * g4_rowb<RT>() + (unsigned)lo2 * (unsigned)sizeof(RT);    // Lt(hi, lo): the transposed corner
     lb.hi = hi2;
     lb.blk = blk2;
     gr.base = (unsigned)r0 * (unsigned)xs + (unsigned)lo2;
@@ -711,7 +743,7 @@ __global__ __launch_bounds__(256, OCC) void k_bj_g4(
         gr.ap = apv[0];          // (tile 0 is taken below, like the spread-out variant's last request)
       }
     } else {
-      g4_bwd_tiles<NC, NT, DQ, NT - 1, GP>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, lb, ring, gr, 4 * blk2 + hi2, mpk);
+      g4_bwd_tiles<RT, NC, NT, DQ, NT - 1, GP>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, lb, ring, gr, 4 * blk2 + hi2, mpk);
     }
   }
 
@@ -761,10 +793,13 @@ int kfail(const char* what) {
   return 1;
 }
 
-template <int NC, int NT, int DQ, int OCC>
+template <typename RT, int NC, int NT, int DQ, int OCC>
 int launch_occ(const int* list, int count, const pa_bj_plan_t* pl, int wmax, int xs, int ncol, const double* in, double* out) {
-  const int cbuf = (8 * (wmax + 4) + 127) & ~127;        // doubles per ring buffer, a multiple of 1 KiB
-  const int nld = cbuf >> 7;
+  // a chunk is two groups of (wmax + 4) rows x 4 pivots of RT: sizeof(RT) (wmax + 4) doubles' worth of bytes
+  const int cbuf = ((int)sizeof(RT) * (wmax + 4) + 127) & ~127;        // doubles per ring buffer, a multiple of 1 KiB
+  const int nld = cbuf >> 7;                                            // LDS-DMA pieces (1 KiB each) per chunk
+  constexpr bool F64 = sizeof(RT) == 8;
+  const RT* Lg4 = static_cast<const RT*>(pl->Lg4);
   // Ring depth.  Many blocks (the chip is filled several wavefronts deep): two buffers, the LDS then
   // allows six wavefronts per SIMD.  Few blocks (fewer than two per SIMD: a shard of a multi-GPU run):
   // a lone wavefront cannot hide the memory latency behind other wavefronts, so up to eight chunks in
@@ -783,15 +818,18 @@ int launch_occ(const int* list, int count, const pa_bj_plan_t* pl, int wmax, int
   const size_t lds = (size_t)waves * per_wave * 8;
   static size_t configured = 0;
   if (lds > 64 * 1024 && lds > configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bj_g4<NC, NT, DQ, OCC, false>),
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bj_g4<NC, NT, DQ, OCC, false, false, RT>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-        (NC == 1 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bj_g4<NC, NT, DQ, OCC, NC == 1>),
+        (NC == 1 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bj_g4<NC, NT, DQ, OCC, NC == 1, false, RT>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess))
       return kfail("hipFuncSetAttribute(k_bj_g4)");
     configured = lds;
   }
   const int blocks = (count + waves - 1) / waves;
-  if constexpr (NC == 1 && NT == 12 && DQ <= 5) {
+  pa_g4_last[0] = ring; pa_g4_last[1] = 8 * (int)sizeof(RT); pa_g4_last[2] = 0;
+  // (fp32 records: no pipelined chain -- few blocks take the plain chain with the deep ring below, as the classes
+  // outside NT == 12 && DQ <= 5 do)
+  if constexpr (F64 && NC == 1 && NT == 12 && DQ <= 5) {
     // few blocks (fewer than two per SIMD): the software-pipelined group chain with its compile-time ring
     // (G4F_RING buffers of DQ KiB and the spare one per wavefront)
     if (ring >= 4) {
@@ -811,34 +849,41 @@ int launch_occ(const int* list, int count, const pa_bj_plan_t* pl, int wmax, int
         configured_p = lds_f;
       }
       const int blocks_f = (count + waves_f - 1) / waves_f;
+      pa_g4_last[0] = G4F_RING; pa_g4_last[2] = 1;
       if (pa_g4_gram_part && xs == 4 && ncol == 4)
         PA_LAUNCH((k_bj_g4<NC, NT, DQ, 1, true, true>), dim3(blocks_f), dim3(64 * waves_f), lds_f, cur_stream(), list, count, pl->row0,
-                  pl->nrows, pl->bw, pl->off2, pl->map_f, pl->Lg4, pl->invd_f, per_wave_f, G4F_RING, xs, ncol, in, out,
+                  pl->nrows, pl->bw, pl->off2, pl->map_f, Lg4, pl->invd_f, per_wave_f, G4F_RING, xs, ncol, in, out,
                   pa_g4_gram_prev, pa_g4_gram_part);
       else
         PA_LAUNCH((k_bj_g4<NC, NT, DQ, 1, false, true>), dim3(blocks_f), dim3(64 * waves_f), lds_f, cur_stream(), list, count, pl->row0,
-                  pl->nrows, pl->bw, pl->off2, pl->map_f, pl->Lg4, pl->invd_f, per_wave_f, G4F_RING, xs, ncol, in, out,
+                  pl->nrows, pl->bw, pl->off2, pl->map_f, Lg4, pl->invd_f, per_wave_f, G4F_RING, xs, ncol, in, out,
                   (const double*)nullptr, (double*)nullptr);
       return kfail("k_bj_g4");
     }
   }
   if constexpr (NC == 1) {
     if (pa_g4_gram_part && xs == 4 && ncol == 4) {
-      PA_LAUNCH((k_bj_g4<NC, NT, DQ, OCC, true>), dim3(blocks), dim3(64 * waves), lds, cur_stream(), list, count, pl->row0,
-                pl->nrows, pl->bw, pl->off2, pl->map_f, pl->Lg4, pl->invd_f, per_wave, ring, xs, ncol, in, out,
+      PA_LAUNCH((k_bj_g4<NC, NT, DQ, OCC, true, false, RT>), dim3(blocks), dim3(64 * waves), lds, cur_stream(), list, count, pl->row0,
+                pl->nrows, pl->bw, pl->off2, pl->map_f, Lg4, pl->invd_f, per_wave, ring, xs, ncol, in, out,
                 pa_g4_gram_prev, pa_g4_gram_part);
       return kfail("k_bj_g4");
     }
   }
-  PA_LAUNCH((k_bj_g4<NC, NT, DQ, OCC, false>), dim3(blocks), dim3(64 * waves), lds, cur_stream(), list, count, pl->row0,
-            pl->nrows, pl->bw, pl->off2, pl->map_f, pl->Lg4, pl->invd_f, per_wave, ring, xs, ncol, in, out,
+  PA_LAUNCH((k_bj_g4<NC, NT, DQ, OCC, false, false, RT>), dim3(blocks), dim3(64 * waves), lds, cur_stream(), list, count, pl->row0,
+            pl->nrows, pl->bw, pl->off2, pl->map_f, Lg4, pl->invd_f, per_wave, ring, xs, ncol, in, out,
             (const double*)nullptr, (double*)nullptr);
   return kfail("k_bj_g4");
 }
 
+#ifdef G4_F32
+typedef float g4_rec_t;       /* this translation unit: the kernels that read fp32 records (bj_g4_f32*.hip) */
+#else
+typedef double g4_rec_t;
+#endif
+
 template <int NC, int NT, int DQ>
 int launch(const int* list, int count, const pa_bj_plan_t* pl, int wmax, int xs, int ncol, const double* in, double* out) {
-  return launch_occ<NC, NT, DQ, (NC == 1 && NT <= 12 && DQ <= 5) ? 5 : (NC == 1 ? 4 : 3)>(list, count, pl, wmax, xs, ncol, in, out);
+  return launch_occ<g4_rec_t, NC, NT, DQ, (NC == 1 && NT <= 12 && DQ <= 5) ? 5 : (NC == 1 ? 4 : 3)>(list, count, pl, wmax, xs, ncol, in, out);
 }
 
 template <int NC, int NT>
@@ -859,9 +904,43 @@ int launch_dq(const int* list, int count, const pa_bj_plan_t* pl, int wmax, int 
 
 extern "C" {
 
+#ifdef G4_F32
+/* ---- fp32 records: the same three units again (bj_g4_f32.hip, bj_g4_f32_nt14.hip, bj_g4_f32_nt16.hip) ---- */
 #if G4_NT == 12
+int pa_k_bj_g4_setup_f32(const int* list, int count, const int* nrows, const int* bw, const long long* off,
+                          const long long* off2, const double* L, float* Lg4) {
+  if (count <= 0) return 0;
+  PA_LAUNCH(k_bj_g4_setup<float>, dim3(count), dim3(256), 0, cur_stream(), list, nrows, bw, off, off2, L, Lg4);
+  return kfail("k_bj_g4_setup<float>");
+}
+
+int pa_k_bj_g4_f32_nt14(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int xs, int ncol, const double* in, double* out);
+int pa_k_bj_g4_f32_nt16(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int xs, int ncol, const double* in, double* out);
+
+/* pa_k_bj_g4 for a plan whose records are fp32 (pl->g4_bits == 32; called from there) */
+int pa_k_bj_g4_f32(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int bmax, int xs, int ncol,
+                   const double* in, double* out) {
+  if (bmax > 224) return pa_k_bj_g4_f32_nt16(pl, list, count, wmax, xs, ncol, in, out);
+  if (bmax > 192) return pa_k_bj_g4_f32_nt14(pl, list, count, wmax, xs, ncol, in, out);
+  return ncol > 4 ? launch_dq<2, 12>(list, count, pl, wmax, xs, ncol, in, out)
+                  : launch_dq<1, 12>(list, count, pl, wmax, xs, ncol, in, out);
+}
+#elif G4_NT == 14
+int pa_k_bj_g4_f32_nt14(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int xs, int ncol, const double* in, double* out) {
+  return ncol > 4 ? launch_dq<2, 14>(list, count, pl, wmax, xs, ncol, in, out)
+                  : launch_dq<1, 14>(list, count, pl, wmax, xs, ncol, in, out);
+}
+#else
+int pa_k_bj_g4_f32_nt16(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int xs, int ncol, const double* in, double* out) {
+  return ncol > 4 ? launch_dq<2, 16>(list, count, pl, wmax, xs, ncol, in, out)
+                  : launch_dq<1, 16>(list, count, pl, wmax, xs, ncol, in, out);
+}
+#endif
+#elif G4_NT == 12
 const double* pa_g4_gram_prev = nullptr;
 double* pa_g4_gram_part = nullptr;
+int pa_g4_last[3] = {0, 0, 0};
+int pa_bj_g4_last(int which) { return which >= 0 && which < 3 ? pa_g4_last[which] : 0; }
 /* The next pa_k_bj_g4 on a 4-column panel also leaves, per block (in the order of `list`), the 8 x 4 block
  * [in | prev]^T out in part (32 doubles each).  Cleared by that call. */
 void pa_k_bj_g4_gram(const double* prev, double* part) { pa_g4_gram_prev = prev; pa_g4_gram_part = part; }
@@ -873,22 +952,26 @@ int pa_bj_g4_max_band8(void) { return 80; }     /* panels of 5 .. 8 columns (two
 int pa_k_bj_g4_setup(const int* list, int count, const int* nrows, const int* bw, const long long* off,
                       const long long* off2, const double* L, double* Lg4) {
   if (count <= 0) return 0;
-  PA_LAUNCH(k_bj_g4_setup, dim3(count), dim3(256), 0, cur_stream(), list, nrows, bw, off, off2, L, Lg4);
+  PA_LAUNCH(k_bj_g4_setup<double>, dim3(count), dim3(256), 0, cur_stream(), list, nrows, bw, off, off2, L, Lg4);
   return kfail("k_bj_g4_setup");
 }
 
 int pa_k_bj_g4_nt14(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int xs, int ncol, const double* in, double* out);
 int pa_k_bj_g4_nt16(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int xs, int ncol, const double* in, double* out);
+int pa_k_bj_g4_f32(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int bmax, int xs, int ncol,
+                   const double* in, double* out);
 
 /* One class of blocks (all with at most bmax rows and bands up to wmax) on a panel of row stride xs:
  * the ncol <= 8 columns starting at `in` / `out` (more than 4: bands up to pa_bj_g4_max_band8()).  The
  * kernels for 12 / 14 / 16 register tiles are compiled in three translation units (bj_g4.hip,
- * bj_g4_nt14.hip, bj_g4_nt16.hip: the same source, G4_NT set) so that they build in parallel. */
+ * bj_g4_nt14.hip, bj_g4_nt16.hip: the same source, G4_NT set) so that they build in parallel; those that read
+ * fp32 records (PREALPS_BJ_BAND_PRECISION=single) in three more (bj_g4_f32*.hip: G4_F32 set as well). */
 int pa_k_bj_g4(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int bmax, int xs, int ncol,
                const double* in, double* out) {
   if (count <= 0) return 0;
   int rc;
-  if (bmax > 224) rc = pa_k_bj_g4_nt16(pl, list, count, wmax, xs, ncol, in, out);
+  if (pl->g4_bits == 32) rc = pa_k_bj_g4_f32(pl, list, count, wmax, bmax, xs, ncol, in, out);     /* fp32 records */
+  else if (bmax > 224) rc = pa_k_bj_g4_nt16(pl, list, count, wmax, xs, ncol, in, out);
   else if (bmax > 192) rc = pa_k_bj_g4_nt14(pl, list, count, wmax, xs, ncol, in, out);
   else rc = ncol > 4 ? launch_dq<2, 12>(list, count, pl, wmax, xs, ncol, in, out)
                      : launch_dq<1, 12>(list, count, pl, wmax, xs, ncol, in, out);

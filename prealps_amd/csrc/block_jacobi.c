@@ -36,7 +36,7 @@ typedef struct {
   double* d_Lf; double* d_Lb; double* d_invd_f; double* d_invd_b;
   double* d_Lf2; double* d_Lb2; long long* d_off2;     /* paired records of the narrow classes (optional) */
   double pairs_bytes;
-  double* d_Lg4; double g4_bytes;                      /* one-copy records of bj_g4.hip (optional) */
+  void* d_Lg4; int g4_bits; double g4_bytes;                   /* one-copy records of bj_g4.hip (optional) */
   int class_g4[16]; int class_bmax[16];
   /* classes by register sets */
   int nclass; int class_R[16]; int class_count[16]; int class_wmax[16]; int* class_list[16];
@@ -76,6 +76,18 @@ int preAlps_hip_set_nd_precision(int bits) {
   if (bits != 0 && bits != 32 && bits != 64)
     return PA_FAIL("precision %d refused: 64 (double), 32 (single) or 0 (follow PREALPS_BJ_ND_PRECISION)", bits);
   g_nd_bits = bits;
+  return 0;
+}
+/* storage of the one-copy band records of bj_g4.hip (64 / 32), 0 if no class has them */
+int pa_bj_band_precision(void) { return g_bj.created && g_bj.d_Lg4 ? g_bj.g4_bits : 0; }
+
+/* Storage of the one-copy band records of the next creates: 64 / 32 bits, 0 = PREALPS_BJ_BAND_PRECISION.
+ * Independent of preAlps_hip_set_nd_precision. */
+static int g_band_bits = 0;
+int preAlps_hip_set_band_precision(int bits) {
+  if (bits != 0 && bits != 32 && bits != 64)
+    return PA_FAIL("precision %d refused: 64 (double), 32 (single) or 0 (follow PREALPS_BJ_BAND_PRECISION)", bits);
+  g_band_bits = bits;
   return 0;
 }
 double pa_bj_pairs_bytes(void) { return g_bj.created ? g_bj.pairs_bytes : 0.0; }
@@ -175,6 +187,14 @@ int preAlps_BlockJacobiCreate(CPLM_Mat_CSR_t* A, int* rowPos, int sizeRowPos, in
     if (!pe || !*pe || !strcmp(pe, "double")) nd_bits = 64;
     else if (!strcmp(pe, "single")) nd_bits = 32;
     else return PA_FAIL("PREALPS_BJ_ND_PRECISION=%s: expected double or single (storage of the sparse block factors)", pe);
+  }
+  /* storage of the one-copy band records (bj_g4.hip): preAlps_hip_set_band_precision, else the switch */
+  int band_bits = g_band_bits;
+  if (!band_bits) {
+    const char* pe = getenv("PREALPS_BJ_BAND_PRECISION");
+    if (!pe || !*pe || !strcmp(pe, "double")) band_bits = 64;
+    else if (!strcmp(pe, "single")) band_bits = 32;
+    else return PA_FAIL("PREALPS_BJ_BAND_PRECISION=%s: expected double or single (storage of the one-copy band records)", pe);
   }
   if (g_bj.created) preAlps_BlockJacobiFree();
   pa_bj_t* s = &g_bj;
@@ -604,14 +624,22 @@ int preAlps_BlockJacobiCreate(CPLM_Mat_CSR_t* A, int* rowPos, int sizeRowPos, in
       if (!s->d_off2 || pa_rt_h2d(s->d_off2, off2, ((size_t)np + 1) * sizeof(long long)))
         rc = PA_FAIL("allocating the second sweep records failed: %s", pa_rt_error());
       if (!rc && any_g4) {
-        s->d_Lg4 = (double*)pa_rt_malloc(((size_t)tot2 + 1024) * sizeof(double));
-        if (!s->d_Lg4 || pa_rt_memset(s->d_Lg4, 0, ((size_t)tot2 + 1024) * sizeof(double)))
+        /* tot2 elements of 8 or 4 bytes (off2 counts elements: every offset a multiple of 8 of them, so a block
+         * starts 32-byte aligned in fp32 too), and 8 KiB of zeroed slack: a request of the apply reads whole KiB
+         * from a chunk's start, up to 1 KiB beyond the end of the last block's last chunk */
+        const size_t esz = band_bits == 32 ? sizeof(float) : sizeof(double);
+        const size_t g4_alloc = (size_t)tot2 * esz + 8192;
+        s->g4_bits = band_bits;
+        s->d_Lg4 = pa_rt_malloc(g4_alloc);
+        if (!s->d_Lg4 || pa_rt_memset(s->d_Lg4, 0, g4_alloc))
           rc = PA_FAIL("allocating the one-copy sweep records failed: %s", pa_rt_error());
         for (int c = 0; c < s->nclass && !rc; ++c)
           if (s->class_g4[c] &&
-              pa_k_bj_g4_setup(s->class_list[c], s->class_count[c], s->d_nrows, s->d_bw, s->d_off, s->d_off2, s->d_Lf, s->d_Lg4))
+              (band_bits == 32
+                 ? pa_k_bj_g4_setup_f32(s->class_list[c], s->class_count[c], s->d_nrows, s->d_bw, s->d_off, s->d_off2, s->d_Lf, (float*)s->d_Lg4)
+                 : pa_k_bj_g4_setup(s->class_list[c], s->class_count[c], s->d_nrows, s->d_bw, s->d_off, s->d_off2, s->d_Lf, (double*)s->d_Lg4)))
             rc = PA_FAIL("k_bj_g4_setup failed");
-        if (!rc) s->g4_bytes = 8.0 * (double)tot2;
+        if (!rc) s->g4_bytes = (double)esz * (double)tot2;
       }
       if (!rc && any_pairs) {
         s->d_Lf2 = (double*)pa_rt_malloc(((size_t)tot2 + 1024) * sizeof(double));
@@ -641,7 +669,7 @@ int preAlps_BlockJacobiCreate(CPLM_Mat_CSR_t* A, int* rowPos, int sizeRowPos, in
   pl->map_f = s->d_map_f; pl->map_b = s->d_map_b; pl->Lf = s->d_Lf; pl->Lb = s->d_Lb;
   pl->invd_f = s->d_invd_f; pl->invd_b = s->d_invd_b;
   pl->Lf2 = s->d_Lf2; pl->Lb2 = s->d_Lb2; pl->off2 = s->d_off2;
-  pl->Lg4 = s->d_Lg4; pl->class_g4 = s->class_g4; pl->class_bmax = s->class_bmax;
+  pl->Lg4 = s->d_Lg4; pl->g4_bits = s->d_Lg4 ? s->g4_bits : 0; pl->class_g4 = s->class_g4; pl->class_bmax = s->class_bmax;
   pl->nclass = s->nclass; pl->class_R = s->class_R; pl->class_count = s->class_count;
   pl->class_wmax = s->class_wmax;
   pl->class_list = s->class_list_c;

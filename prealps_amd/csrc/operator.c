@@ -1418,6 +1418,10 @@ int preAlps_hip_get_stat(const char* key, double* value) {
   else if (!strcmp(key, "bj_g4_bytes")) *value = pa_bj_g4_bytes();
   else if (!strcmp(key, "bj_nd_inverse_dev")) *value = pa_nd_inverse_deviation();
   else if (!strcmp(key, "bj_nd_precision")) *value = pa_bj_nd_precision();
+  else if (!strcmp(key, "bj_band_precision")) *value = pa_bj_band_precision();
+  else if (!strcmp(key, "bj_g4_last_ring")) *value = pa_bj_g4_last(0);
+  else if (!strcmp(key, "bj_g4_last_bits")) *value = pa_bj_g4_last(1);
+  else if (!strcmp(key, "bj_g4_last_pipelined")) *value = pa_bj_g4_last(2);
   else return 1;
   return 0;
 }

@@ -243,7 +243,8 @@ typedef struct {
   /* optional (NULL: absent): ONE copy of the factor for both sweeps of panels of up to 4 columns, in
    * selective-inversion form by groups of four pivots (bj_g4.hip), block p at off2[p]: per group
    * (w + 4) rows x 4 pivots of M = [T - I ; -G], eligible classes flagged in class_g4 */
-  const double* Lg4;
+  const void* Lg4;        /* records of g4_bits bits: double, or float (PREALPS_BJ_BAND_PRECISION=single); off2 counts elements */
+  int g4_bits;            /* 64 / 32; 0 when Lg4 is absent */
   const int* class_g4;    /* host array, nclass: 1 = every block of the class has a record in Lg4 */
   const int* class_bmax;   /* host array, nclass: most rows of a block in the class */
   const double* invd_f;    /* 1 / L(j,j) in forward step order (m entries) */
@@ -270,6 +271,12 @@ int pa_bj_g4_max_band(void);
 int pa_bj_g4_max_band8(void);
 int pa_k_bj_g4_setup(const int* list, int count, const int* nrows, const int* bw, const long long* off,
                       const long long* off2, const double* L, double* Lg4);
+/* the same records rounded to fp32: (float)v of the same fp64 value at the same position */
+int pa_k_bj_g4_setup_f32(const int* list, int count, const int* nrows, const int* bw, const long long* off,
+                          const long long* off2, const double* L, float* Lg4);
+/* the last launch of pa_k_bj_g4: 0 = ring depth, 1 = storage bits of the records it read, 2 = 1 if it was the
+ * pipelined few-blocks chain */
+int pa_bj_g4_last(int which);
 /* Band Cholesky on the device for blocks with bandwidth <= pa_bj_factor_wmax(): `band` holds
  * each listed block's rows in factor order, (w+1) doubles per row (A(i, i-d) at d), at offset
  * boff[part]; writes the forward / backward sweep records and 1/L(j,j) straight into Lf, Lb

@@ -111,7 +111,8 @@ int pa_bj_nparts(void);
 int pa_bj_nd_blocks(void);
 int pa_bj_nd_precision(void);       /* storage of the sparse factors (64 / 32), 0 if no block has one */
 int pa_bj_gram_blocks(void);       /* blocks of an apply that can leave [in | prev]^T out behind (0: cannot) */
-double pa_bj_g4_bytes(void);        /* bytes of the one-copy records of bj_g4.hip, 0 if absent */
+double pa_bj_g4_bytes(void);        /* bytes of the one-copy records of bj_g4.hip as stored (fp64 / fp32), 0 if absent */
+int pa_bj_band_precision(void);     /* storage of those records (64 / 32), 0 if absent */
 double pa_bj_pairs_bytes(void);     /* bytes of the paired sweep records (both sweeps), 0 if absent */
 
 #endif

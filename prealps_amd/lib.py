@@ -79,7 +79,7 @@ EXPORTS = [
     "preAlps_hip_panel_gram", "preAlps_hip_panel_update", "preAlps_hip_panel_trsm_update",
     "preAlps_hip_panel_permute_solve",
     "preAlps_hip_nd_selfcheck", "preAlps_hip_loopback", "preAlps_hip_graphs", "preAlps_hip_ecg_solve_first",
-    "preAlps_hip_set_nd_precision",
+    "preAlps_hip_set_nd_precision", "preAlps_hip_set_band_precision",
 ]
 
 _lib = None
@@ -151,6 +151,7 @@ def load():
     L.preAlps_hip_timing.restype = None
     L.preAlps_hip_graphs.restype = None
     L.preAlps_hip_set_nd_precision.argtypes = [C.c_int]
+    L.preAlps_hip_set_band_precision.argtypes = [C.c_int]
     L.preAlps_hip_timing_reset.restype = None
     L.preAlps_hip_shutdown.restype = None
     L.preAlps_hip_set_abort_mode.restype = None

@@ -261,23 +261,32 @@ class EcgProblem:
         return part
 
     # -- pieces of the driver --------------------------------------------------
-    def create_block_jacobi(self, nd_precision=None):
+    def create_block_jacobi(self, nd_precision=None, band_precision=None):
         """nd_precision: storage of the sparse factors of large blocks -- None follows
         PREALPS_BJ_ND_PRECISION, "double" / "single" select it for this create (band blocks stay fp64).
         With a value, the library's setting (preAlps_hip_set_nd_precision) is 0 again afterwards: a value
-        set earlier through the C entry is not restored."""
+        set earlier through the C entry is not restored.
+        band_precision: the same for the one-copy band records that panels of up to 4 (8) columns read
+        (PREALPS_BJ_BAND_PRECISION, preAlps_hip_set_band_precision); the two are independent."""
         bits = {None: 0, "double": 64, "single": 32}.get(nd_precision)
         if bits is None:
             raise ValueError("nd_precision must be None, 'double' or 'single', not %r" % (nd_precision,))
+        bbits = {None: 0, "double": 64, "single": 32}.get(band_precision)
+        if bbits is None:
+            raise ValueError("band_precision must be None, 'double' or 'single', not %r" % (band_precision,))
         if bits:
             check(self.L.preAlps_hip_set_nd_precision(bits), "preAlps_hip_set_nd_precision")
         try:
+            if bbits:
+                check(self.L.preAlps_hip_set_band_precision(bbits), "preAlps_hip_set_band_precision")
             check(self.L.preAlps_BlockJacobiCreate(C.byref(self.A), self._rowpos_ptr, self._rowpos_n,
                                                    self._colpos_ptr, self._colpos_n),
                   "preAlps_BlockJacobiCreate")
         finally:
             if bits:
                 self.L.preAlps_hip_set_nd_precision(0)
+            if bbits:
+                self.L.preAlps_hip_set_band_precision(0)
         self.has_precond = True
 
     def reference_rhs(self):
