@@ -2,7 +2,7 @@
 // copy of the factor (block_jacobi.c:93-109 of the reference: PARDISO phase 33 on every diagonal
 // block; here Z = blockdiag(A)^-1 X with the band Cholesky factors of block_jacobi.c / k_bj_factor).
 //
-// The register recurrence (k_bj_apply_pairs, kernels.hip) streams two copies of the band -- columns of
+// The register recurrence (k_bj_apply_pairs, bj_band.hip) streams two copies of the band -- columns of
 // L for the forward sweep, rows for the backward one -- and spends ~20 wave instructions per pivot.
 // Here both sweeps read the same records, blocked by groups of FOUR pivots:
 //
@@ -70,7 +70,7 @@ typedef const __attribute__((address_space(1))) void* glb_ptr;
 inline hipStream_t cur_stream() { return (hipStream_t)pa_rt_stream(); }
 
 // ---------------------------------------------------------------------------------- set-up ----
-// Records from the plain forward records of kernels.hip (rec[j * wr + d - 1] = L(j+d, j) / L(j, j)):
+// Records from the plain forward records of bj_band.hip (rec[j * wr + d - 1] = L(j+d, j) / L(j, j)):
 // group g of block p at Lg4[off2[p] + g * 4 (w + 4)], four doubles [position][pivot]:
 //   positions 0 .. w-1     rows rho = w+3 .. 4 of the group (row 4g + rho of the block), NEGATED: the
 //                          product adds them;

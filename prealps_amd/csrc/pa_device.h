@@ -1,6 +1,7 @@
 /*
  * pa_device.h -- the thin C-ABI shim between the C host code (ecg.c,
- * operator.c, block_jacobi.c) and the HIP side (runtime.hip, kernels.hip).
+ * operator.c, block_jacobi.c) and the HIP side (runtime.hip, kernels.hip,
+ * bj_band.hip, ...).
  * Host code never includes a HIP header; device code never sees a preAlps
  * struct.  Panels are row-interleaved: element (i, j) at p[i * ts + j].
  */
@@ -233,7 +234,7 @@ typedef struct {
   /* Narrow bands: one record of wr = (w+1 rounded up to even) doubles per step:
    * forward  Lf[off + j*wr + d-1] = L(j+d, j) / L(j,j),                 d = 1..w, then a zero
    * backward Lb[off + j*wr + d-1] = L(b-1-j, b-1-j-d) / L(b-1-j, b-1-j).
-   * Wide bands: records of W = bjw_window(w) doubles, the value for target row i at i mod W.
+   * Wide bands: records of W = pa_bj_wide_window(w) doubles, the value for target row i at i mod W.
    * Arrays are padded by 2 KiB at the end. */
   const double* Lf;
   const double* Lb;
@@ -255,6 +256,21 @@ typedef struct {
   const int* class_wmax;   /* host array: widest band in the class (sizes the LDS chunks) */
   const int* const* class_list; /* host array of device pointers to part ids */
 } pa_bj_plan_t;
+/* Window of a wide block (rows in flight = record length, >= w + 64) for bandwidth w: a multiple of the
+ * 64 / 128 / 256 rows that 1 / 2 / 4 register sets per lane hold across a wavefront.  The one rule for the
+ * host layout (block_jacobi.c) and the kernels (bj_band.hip). */
+#ifdef __HIPCC__
+#define PA_HOST_DEVICE __host__ __device__
+#else
+#define PA_HOST_DEVICE
+#endif
+static inline PA_HOST_DEVICE int pa_bj_wide_window(int w) {
+  int W = (w + 64 + 63) & ~63;
+  if (W <= 1024) return W;
+  W = (w + 64 + 127) & ~127;
+  if (W <= 2048) return W;
+  return (w + 64 + 255) & ~255;
+}
 int pa_k_bj_g4(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int bmax, int xs, int ncol,
                 const double* in, double* out);
 /* One-shot: the next pa_k_bj_g4 on a 4-column panel also leaves the 8 x 4 block [in | prev]^T out of every
