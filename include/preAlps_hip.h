@@ -117,6 +117,38 @@ int preAlps_hip_reference_rhs(double* rhs_local);
  * examples/test_ecg_bench_fused.c:243-259). res_hist may be NULL. */
 int preAlps_ECGSolve(preAlps_ECG_t* ecg, double* rhs, double* sol,
                      double* res_hist, int* bs_hist, int max_hist, int* n_hist);
+/* ---- several right-hand sides on one operator ---------------------------------------------------------------
+ * The ECG iteration is block CG on an m x enlFac panel, so started from R0 = [b_1 | ... | b_k] it solves k systems
+ * in one pass over the matrix and the block factors per iteration.  nrhs = k >= 1; ecg->enlFac must be a multiple of
+ * k and s = enlFac / k is the enlarging factor of each system: system j owns the columns j*s .. j*s + s - 1 of X, R,
+ * P ..., and a row of part p puts b_j into column j*s + (p % s) (k = 1: the split of preAlps_ECGInitialize).  rhs:
+ * the local rows, column major, ldrhs >= m.  Every system converges in the block Krylov space of all of them.
+ *   Iteration: that of one system at the same ortho_alg, bs_red and enlFac, launch for launch, plus one small launch
+ * per iteration that sums the residual columns of each system.  A solver started here runs under the caller's own
+ * loop of preAlps_ECGIterate / preAlps_BlockOperator / preAlps_BlockJacobiApply / preAlps_ECGStoppingCriterion.
+ *   Stopping: g_j = Frobenius norm of the columns of R that belong to system j, normb_j = ||b_j||_2; the iteration
+ * goes on while g_j > tol * normb_j for some j (and iter < maxIter, bs > 0; a NaN stops it).  Systems that have
+ * converged keep iterating with the rest (no deflation).  ecg->res stays the Frobenius norm of all of R,
+ * ecg->normb = ||B||_F.  With k = 1 this is the test of preAlps_ECGStoppingCriterion as it always was.
+ *   Finish: x_j = the sum of the columns of system j of X, written to sol[i + j*ldsol], ldsol >= m.
+ *   Accuracy: the true residual of system j is the sum of its s columns of R, so in exact arithmetic
+ * ||b_j - A x_j|| <= sqrt(s) * g_j (Cauchy-Schwarz); s = 1: they are equal.
+ *   Refused (non-zero / abort, the message names the entry point): nrhs < 1 or enlFac % nrhs != 0; s larger than
+ * the number of parts; ldrhs or ldsol < m; a right-hand side of norm zero (its columns of R0 would be empty);
+ * ORTHODIR_FUSED (it decides inside preAlps_ECGIterate on one sum); more than one process and
+ * preAlps_hip_loopback shards; preAlps_ECGFinalize and preAlps_ECGAdvance on a solver that holds more than one
+ * system.  HIP graphs (preAlps_hip_graphs, PREALPS_ECG_GRAPH) and PREALPS_ECG_POLL are off for such a solver.
+ *   Linearly dependent right-hand sides (a repeated load case, say) make P^T A P singular: keeping them apart is the
+ * caller's business; bs_red = ADAPT_BS drops the directions that have become dependent. */
+int preAlps_ECGInitializeMulti(preAlps_ECG_t* ecg, int nrhs, const double* rhs, int ldrhs, int* rci_request);
+/* after a stopping test: g_j and normb_j of every system (either pointer may be NULL) */
+int preAlps_ECGSystemResiduals(preAlps_ECG_t* ecg, double* sys_res, double* sys_normb);
+int preAlps_ECGFinalizeMulti(preAlps_ECG_t* ecg, double* sol, int ldsol);
+/* the library's own loop: res_hist / bs_hist as preAlps_ECGSolve; sys_hist (may be NULL) receives
+ * g_j of iteration i at sys_hist[i + j * max_hist]; sys_normb (may be NULL): nrhs values */
+int preAlps_ECGSolveMulti(preAlps_ECG_t* ecg, int nrhs, const double* rhs, int ldrhs, double* sol, int ldsol,
+                          double* res_hist, int* bs_hist, double* sys_hist, double* sys_normb,
+                          int max_hist, int* n_hist);
 /* 1 / 0: the two driver loops above and below replay each half of an iteration from a HIP graph
  * captured on its first passes (default: off, or PREALPS_ECG_GRAPH; plain launches measured faster). */
 void preAlps_hip_graphs(int on);

@@ -105,6 +105,14 @@ typedef struct {
   int phase;          /* iterations since the last reset, mod 6 */
   void* graph[2][6];
   unsigned char seen[2][6];
+  /* Several right-hand sides (preAlps_ECGInitializeMulti): nrhs systems of sgrp = enlFac / nrhs columns each, system
+   * j in the columns j*sgrp .. j*sgrp + sgrp - 1.  nrhs <= 1: one system, nothing below is used.  Every launch that
+   * leaves the column sums of R^2 in d_rtr_part is followed by pa_k_group_norms (queue_group_norms), which leaves
+   * g_j^2 in d_grp and in the pinned words h_grp[0..nrhs); they are complete when the scalar norm is, because that
+   * reaches the host through a later launch or event of the same stream.  h_grp[16..]: the start's ||b_j||^2. */
+  int nrhs, sgrp;
+  double* d_grp; double* h_grp;
+  double sys_res[16], sys_normb[16];
 } ecg_priv_t;
 
 static ecg_priv_t* priv_of(preAlps_ECG_t* ecg) {
@@ -179,6 +187,7 @@ int _preAlps_ECGMalloc(preAlps_ECG_t* ecg) {
   /* ... and the library's block solve beta = [AP | AP_prev]^T Z while Z is still in its registers (Orthodir) */
   pv->bj_cap = (T == 4 && ts == 4 && ecg->ortho_alg == ORTHODIR && pa_env_flag("PREALPS_BJ_GRAM", 1)) ? pa_bj_gram_blocks() : 0;
   if (pv->bj_cap) parts += ((size_t)pv->bj_cap + pa_finish32_scratch_blocks()) * 32;
+  parts += 32;   /* d_grp: the per-system sums of several right-hand sides */
   pv->pool_doubles = (2 * nv + 3) * panel + small + parts;
   ecg->work = (double*)pa_rt_malloc(pv->pool_doubles * sizeof(double));
   if (!ecg->work) return PA_FAIL("device pool of %zu doubles: %s", pv->pool_doubles, pa_rt_error());
@@ -200,12 +209,15 @@ int _preAlps_ECGMalloc(preAlps_ECG_t* ecg) {
   pv->d_spmm_parts = pv->spmm_cap ? w : NULL;
   if (pv->spmm_cap) w += ((size_t)pv->spmm_cap + pa_finish32_scratch_blocks()) * 32;
   pv->d_bj_parts = pv->bj_cap ? w : NULL;
+  if (pv->bj_cap) w += ((size_t)pv->bj_cap + pa_finish32_scratch_blocks()) * 32;
+  pv->d_grp = w;
   pv->d_info = (int*)pa_rt_malloc((8 + T) * sizeof(int));
   if (!pv->d_info) return PA_FAIL("device allocation failed: %s", pa_rt_error());
   pv->d_piv = pv->d_info + 8;
   pv->h_pin = (double*)pa_rt_host_alloc_coherent((16 + 4 * (size_t)T * T) * sizeof(double));
   pv->h_pin_i = (int*)pa_rt_host_alloc((8 + T) * sizeof(int));
-  if (!pv->h_pin || !pv->h_pin_i) return PA_FAIL("pinned allocation failed: %s", pa_rt_error());
+  pv->h_grp = (double*)pa_rt_host_alloc_coherent(32 * sizeof(double));
+  if (!pv->h_pin || !pv->h_pin_i || !pv->h_grp) return PA_FAIL("pinned allocation failed: %s", pa_rt_error());
   pv->ev_res = pa_rt_event_create();
   pv->ev_alpha = pa_rt_event_create();
   if (!pv->ev_res || !pv->ev_alpha) return PA_FAIL("hipEventCreate failed");
@@ -225,12 +237,10 @@ static void request_gram_from_spmm(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
 }
 
 /* ------------------------------------------------------------- reset ---- */
-int _preAlps_ECGReset(preAlps_ECG_t* ecg, double* rhs, int* rci_request) {
-  ecg_priv_t* pv = priv_of(ecg);
-  if (!pv) return PA_FAIL("solver memory not allocated (_preAlps_ECGMalloc)");
-  const pa_operator_info_t* op = pa_operator_info();
-  if (!op) return PA_FAIL("the operator must be built before the solver");
-  if (ecg->locPbSize != op->m) return PA_FAIL("locPbSize %d differs from the operator's %d rows", ecg->locPbSize, op->m);
+/* Everything of a reset but R0 and the norm of the right-hand side: timers, pointer order, the switches, the
+ * descriptors, the zeroed pool.  nrhs: the systems the solver will hold (1 from _preAlps_ECGReset). */
+static int reset_state(preAlps_ECG_t* ecg, ecg_priv_t* pv, int nrhs) {
+  pv->nrhs = nrhs; pv->sgrp = ecg->enlFac / nrhs;
   ecg->tot_t = ecg->comm_t = ecg->trsm_t = ecg->gemm_t = ecg->potrf_t = ecg->pstrf_t = 0.0;
   ecg->lapmt_t = ecg->gesvd_t = ecg->geqrf_t = ecg->ormqr_t = ecg->copy_t = 0.0;
   int M = ecg->globPbSize, m = ecg->locPbSize, t = ecg->enlFac, ts = pv->ts;
@@ -272,6 +282,7 @@ int _preAlps_ECGReset(preAlps_ECG_t* ecg, double* rhs, int* rci_request) {
   {
     const char* ge = getenv("PREALPS_ECG_GRAPH");
     int want = g_graphs >= 0 ? g_graphs : (ge ? atoi(ge) : 0);
+    if (nrhs > 1) want = 0;      /* (several systems: the group launch is not part of the captured segments) */
     int group_ok = pa_world_size() == 1 || pa_comm_is_loopback() || want == 2;
     pv->use_graphs = want && group_ok && pv->rotate && pv->fuse && ecg->ortho_alg != ORTHODIR_FUSED &&
                      !pa_timing_enabled();
@@ -284,7 +295,10 @@ int _preAlps_ECGReset(preAlps_ECG_t* ecg, double* rhs, int* rci_request) {
    * rehearsal: 112.5 against 117.8 us); one process: no difference (the 6 us bubble the event leaves
    * behind k_trace_finish reappears behind the block solve), so the event stays.  PREALPS_ECG_POLL=0 / 1
    * forces; graphs replay fixed arguments and keep the event. */
-  { const char* f = getenv("PREALPS_ECG_POLL"); pv->poll = (f ? atoi(f) : pa_world_size() > 1) && !pv->use_graphs; }
+  { const char* f = getenv("PREALPS_ECG_POLL"); pv->poll = (f ? atoi(f) : pa_world_size() > 1) && !pv->use_graphs;
+    /* several systems: the per-system sums may be queued behind the launch that writes the polled word, so the
+     * host waits for the event behind both */
+    if (nrhs > 1) pv->poll = 0; }
   pv->sent_seq = pv->wait_seq = 0.0;
   if (pv->h_pin) pv->h_pin[2] = 0.0;
   pa_set_desc(ecg->X, M, t, m, t, ts);
@@ -310,6 +324,24 @@ int _preAlps_ECGReset(preAlps_ECG_t* ecg, double* rhs, int* rci_request) {
     for (int k = 0; k < 2; ++k) for (int i = 0; i < t; ++i) eye[(size_t)k * t * t + i + (size_t)t * i] = 1.0;
     PA_CHECK(pa_rt_h2d(pv->d_uu, eye, 2 * (size_t)t * t * sizeof(double)));
   }
+  return 0;
+}
+static void reset_done(preAlps_ECG_t* ecg, ecg_priv_t* pv, int* rci_request) {
+  ecg->res = 1.0; ecg->iter = 0; ecg->bs = ecg->enlFac; ecg->kbs = ecg->V->info.n;
+  pv->rtr_valid = 0;
+  *rci_request = 0;
+  request_gram_from_spmm(ecg, pv);
+}
+
+int _preAlps_ECGReset(preAlps_ECG_t* ecg, double* rhs, int* rci_request) {
+  ecg_priv_t* pv = priv_of(ecg);
+  if (!pv) return PA_FAIL("solver memory not allocated (_preAlps_ECGMalloc)");
+  const pa_operator_info_t* op = pa_operator_info();
+  if (!op) return PA_FAIL("the operator must be built before the solver");
+  if (ecg->locPbSize != op->m) return PA_FAIL("locPbSize %d differs from the operator's %d rows", ecg->locPbSize, op->m);
+  if (pv->nrhs > 1) return PA_FAIL("the solver holds %d systems: restart it with preAlps_ECGInitializeMulti", pv->nrhs);
+  if (reset_state(ecg, pv, 1)) return 1;
+  int m = ecg->locPbSize, t = ecg->enlFac, ts = pv->ts;
   /* normb and R0: column (rank % t) of every reference rank = part */
   double nb2 = 0.0;
   double* r0 = (double*)calloc((size_t)(m > 0 ? m : 1) * ts, sizeof(double));
@@ -333,10 +365,7 @@ int _preAlps_ECGReset(preAlps_ECG_t* ecg, double* rhs, int* rci_request) {
     TAC(PA_T_COMM, comm_t);
   }
   ecg->normb = sqrt(nb2);
-  ecg->res = 1.0; ecg->iter = 0; ecg->bs = t; ecg->kbs = ecg->V->info.n;
-  pv->rtr_valid = 0;
-  *rci_request = 0;
-  request_gram_from_spmm(ecg, pv);
+  reset_done(ecg, pv, rci_request);
   return 0;
 }
 
@@ -350,6 +379,124 @@ int preAlps_ECGInitialize(preAlps_ECG_t* ecg, double* rhs, int* rci_request) {
   int rc = _preAlps_ECGMalloc(ecg);
   if (rc) return rc;
   return _preAlps_ECGReset(ecg, rhs, rci_request);
+}
+
+/* ---- several right-hand sides --------------------------------------------------------------------------------
+ * The block iteration started from R0 = [b_1 | ... | b_k]: nrhs = k systems, s = enlFac / k columns each, system j in
+ * the columns j*s .. j*s + s - 1, a row of part p puts b_j into column j*s + (p % s).  The iteration itself is the
+ * one of a single system at the same enlarging factor, launch for launch; what differs is the start (on the device:
+ * pa_k_multi_start), the stopping test (every system against its own right-hand side, from the sums
+ * pa_k_group_norms leaves behind each update) and the finish (pa_k_rowsum_groups).  nrhs = 1 is
+ * preAlps_ECGInitialize. */
+int preAlps_ECGInitializeMulti(preAlps_ECG_t* ecg, int nrhs, const double* rhs, int ldrhs, int* rci_request) {
+  const pa_operator_info_t* op = pa_operator_info();
+  if (!op) return PA_FAIL("the operator must be built before the solver");
+  if (!ecg || !rhs || !rci_request) return PA_FAIL(" wrong test 'ecg != NULL && rhs != NULL && rci_request != NULL'");
+  if (nrhs < 1) return PA_FAIL("nrhs = %d: at least one right-hand side is needed", nrhs);
+  if (ecg->enlFac < 1 || ecg->enlFac % nrhs != 0)
+    return PA_FAIL("the enlarging factor %d is not a multiple of nrhs = %d", ecg->enlFac, nrhs);
+  const int k = nrhs, s = ecg->enlFac / nrhs, m = op->m;
+  if (op->nparts < s)
+    return PA_FAIL("Enlarging factor per system must be lower than the number of processors"
+                   " in the MPI communicator! size: %d ; enlarging factor per system: %d", op->nparts, s);
+  if (ldrhs < m) return PA_FAIL("ldrhs = %d is smaller than the %d local rows", ldrhs, m);
+  if (ecg->ortho_alg == ORTHODIR_FUSED)
+    return PA_FAIL("ORTHODIR_FUSED decides inside preAlps_ECGIterate on one sum: no per-system stopping test");
+  if (pa_world_size() > 1 || pa_comm_is_loopback())
+    return PA_FAIL("several right-hand sides need a single process (%d processes%s)", pa_world_size(),
+                   pa_comm_is_loopback() ? ", preAlps_hip_loopback shard" : "");
+  if (_preAlps_ECGMalloc(ecg)) return 1;
+  ecg_priv_t* pv = priv_of(ecg);
+  if (k == 1) {
+    if (_preAlps_ECGReset(ecg, (double*)rhs, rci_request)) { _preAlps_ECGFree(ecg); return 1; }
+    if (!(ecg->normb > 0.0)) {
+      _preAlps_ECGFree(ecg);
+      return PA_FAIL("right-hand side 0 has norm zero: its column of R0 would be empty");
+    }
+    return 0;
+  }
+  if (ecg->locPbSize != m) {
+    _preAlps_ECGFree(ecg);
+    return PA_FAIL("locPbSize %d differs from the operator's %d rows", ecg->locPbSize, m);
+  }
+  if (reset_state(ecg, pv, k)) { _preAlps_ECGFree(ecg); return 1; }
+  /* B goes up once (m*k doubles) with p % s of every row; the kernel writes R0 and leaves the k sums of squares */
+  const size_t mm = (size_t)(m > 0 ? m : 1);
+  int* pcol = (int*)malloc(mm * sizeof(int));
+  double* d_B = (double*)pa_rt_malloc(mm * k * sizeof(double) + mm * sizeof(int));
+  int rc = 0, nblk = 0;
+  if (!pcol || !d_B) rc = PA_FAIL("staging %d right-hand sides: %s", k, pcol ? pa_rt_error() : "out of host memory");
+  if (!rc) {
+    int* d_pcol = (int*)(d_B + mm * k);
+    for (int p = op->part0; p < op->part1; ++p) {
+      int base = op->rowPos[p] - op->row_off, l = op->rowPos[p + 1] - op->rowPos[p];
+      for (int i = 0; i < l; ++i) pcol[base + i] = p % s;
+    }
+    rc = pa_rt_h2d(d_pcol, pcol, (size_t)m * sizeof(int));
+    if (ldrhs == m) rc = rc || pa_rt_h2d(d_B, rhs, (size_t)m * k * sizeof(double));
+    else for (int j = 0; j < k && !rc; ++j) rc = pa_rt_h2d(d_B + (size_t)j * m, rhs + (size_t)j * ldrhs, (size_t)m * sizeof(double));
+    rc = rc || pa_k_multi_start(m, pv->ts, k, s, d_B, m, d_pcol, pv->d_R, pv->d_rtr_part, &nblk) ||
+         pa_k_group_norms(pv->d_rtr_part, nblk, pv->ts, k, 1, pv->d_grp + 16, pv->h_grp + 16) || pa_rt_sync();
+    if (rc) rc = PA_FAIL("%s", pa_rt_error());
+  }
+  pa_rt_free(d_B);
+  free(pcol);
+  if (!rc) {
+    double nb2 = 0.0;
+    for (int j = 0; j < k && !rc; ++j) {
+      const double b2 = pv->h_grp[16 + j];
+      if (!(b2 > 0.0)) rc = PA_FAIL("right-hand side %d has norm zero: its column of R0 would be empty", j);
+      pv->sys_normb[j] = sqrt(b2);
+      pv->sys_res[j] = pv->sys_normb[j];
+      nb2 += b2;
+    }
+    ecg->normb = sqrt(nb2);
+  }
+  if (rc) { _preAlps_ECGFree(ecg); return 1; }
+  reset_done(ecg, pv, rci_request);
+  return 0;
+}
+
+int preAlps_ECGSystemResiduals(preAlps_ECG_t* ecg, double* sys_res, double* sys_normb) {
+  ecg_priv_t* pv = priv_of(ecg);
+  if (!pv) return PA_FAIL("solver not initialised");
+  if (pv->nrhs > 1) {
+    for (int j = 0; j < pv->nrhs; ++j) {
+      if (sys_res) sys_res[j] = pv->sys_res[j];
+      if (sys_normb) sys_normb[j] = pv->sys_normb[j];
+    }
+  } else {
+    if (sys_res) sys_res[0] = ecg->res;
+    if (sys_normb) sys_normb[0] = ecg->normb;
+  }
+  return 0;
+}
+
+int preAlps_ECGFinalizeMulti(preAlps_ECG_t* ecg, double* sol, int ldsol) {
+  ecg_priv_t* pv = priv_of(ecg);
+  if (!pv) return PA_FAIL("solver not initialised");
+  if (!sol) return PA_FAIL(" wrong test 'sol != NULL'");
+  if (ldsol < pv->m) return PA_FAIL("ldsol = %d is smaller than the %d local rows", ldsol, pv->m);
+  if (pv->nrhs <= 1) return preAlps_ECGFinalize(ecg, sol);
+  /* one pass over X, k sums per row, one copy to the host */
+  const int m = pv->m, k = pv->nrhs;
+  const size_t need = (size_t)m * k, room = (size_t)pa_gram_max_blocks() * 2 * pv->ts * pv->ts;
+  double* d_sol = pv->d_partials;
+  double* tmp = NULL;
+  double* h_tmp = NULL;
+  int rc = 0;
+  if (need > room) { tmp = (double*)pa_rt_malloc(need * sizeof(double)); d_sol = tmp; }
+  if (ldsol != m && need > 0) h_tmp = (double*)malloc(need * sizeof(double));
+  if ((need > room && !tmp) || (ldsol != m && need > 0 && !h_tmp)) rc = PA_FAIL("buffers for %d solutions", k);
+  if (!rc && (pa_k_rowsum_groups(m, pv->ts, k, pv->sgrp, pv->d_X, d_sol, m) ||
+              pa_rt_d2h(h_tmp ? h_tmp : sol, d_sol, need * sizeof(double))))
+    rc = PA_FAIL("%s", pa_rt_error());
+  if (!rc && h_tmp)
+    for (int j = 0; j < k; ++j) memcpy(sol + (size_t)j * ldsol, h_tmp + (size_t)j * m, (size_t)m * sizeof(double));
+  free(h_tmp);
+  pa_rt_free(tmp);
+  _preAlps_ECGFree(ecg);
+  return rc;
 }
 
 int _preAlps_ECGSplit(double* x, CPLM_Mat_Dense_t* XSplit, int colIndex) {
@@ -372,12 +519,20 @@ int _preAlps_ECGSplit(double* x, CPLM_Mat_Dense_t* XSplit, int colIndex) {
  * `begin` (the preconditioner apply of the same iteration) keeps the GPU busy
  * while the host reads the norm. */
 static int stopping_end(preAlps_ECG_t* ecg, ecg_priv_t* pv, int* stop);
+/* Several systems: the per-system sums, right behind the launch that left the column sums in d_rtr_part (rtr_nblk
+ * blocks) and so ahead of whatever carries the scalar norm to the host. */
+static int queue_group_norms(ecg_priv_t* pv) {
+  if (pv->nrhs > 1)
+    PA_CHECK(pa_k_group_norms(pv->d_rtr_part, pv->rtr_nblk, pv->ts, pv->nrhs, pv->sgrp, pv->d_grp, pv->h_grp));
+  return 0;
+}
 static int stopping_queue(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
   int T = ecg->enlFac;
   int single = pa_world_size() == 1;
   if (pv->rtr_valid < 2) {
     if (!pv->rtr_valid) {
       PA_CHECK(pa_k_colnorm2(pv->m, pv->ts, pv->d_R, pv->d_rtr_part, &pv->rtr_nblk));
+      if (queue_group_norms(pv)) return 1;
     }
     if (single && pv->rtr_valid == 1) {
       /* column sums left by the update kernel (lazy stopping test), one process: the sum goes straight to
@@ -481,6 +636,18 @@ static int stopping_end(preAlps_ECG_t* ecg, ecg_priv_t* pv, int* stop) {
   int info = (int)pv->h_pin[1];
   if (info != 0 && ecg->ortho_alg == ORTHOMIN) return PA_FAIL("ACHQR: dpotrf:\n ERROR: P^tAP is not spd!");
   ecg->res = sqrt(res2);
+  if (pv->nrhs > 1) {
+    /* every system against its own right-hand side: on while one of them is above its threshold; a NaN stops */
+    int above = 0, nan = !(ecg->res == ecg->res);
+    for (int j = 0; j < pv->nrhs; ++j) {
+      const double g = sqrt(pv->h_grp[j]);
+      pv->sys_res[j] = g;
+      if (g > pv->sys_normb[j] * ecg->tol) above = 1;
+      if (!(g == g)) nan = 1;
+    }
+    *stop = (above && !nan && ecg->iter < ecg->maxIter && ecg->bs > 0) ? 0 : 1;
+    return 0;
+  }
   /* !(a > b) also stops on NaN, like the reference's comparison */
   if (ecg->res > ecg->normb * ecg->tol && ecg->iter < ecg->maxIter && ecg->bs > 0) *stop = 0;
   else *stop = 1;
@@ -593,6 +760,7 @@ static int fused_update(preAlps_ECG_t* ecg, ecg_priv_t* pv, int t, const double*
                             pv->lazy_ptr ? pv->lazy_ptr : pv->d_res2, pv->d_info, single ? pv->h_pin : NULL,
                             gram, pv->lazy_norm ? pv->d_uu + (size_t)pv->uu_cur * T * T : NULL));
   pv->rtr_nblk = nb;
+  if (queue_group_norms(pv)) return 1;
   TAC(PA_T_UPDATE, trsm_t);
   pv->rtr_valid = defer ? 1 : 2;
   return 0;
@@ -607,6 +775,7 @@ static int update_iterate(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
   PA_CHECK(pa_k_update_xr(pv->m, pv->ts, ecg->P->info.n, ecg->X->info.n, pv->d_alpha, ecg->P->val,
                           ecg->AP->val, pv->d_X, pv->d_R, pv->d_rtr_part, &pv->rtr_nblk, ecg->enlFac,
                           pv->d_res2, pv->d_info, pa_world_size() == 1 ? pv->h_pin : NULL));
+  if (queue_group_norms(pv)) return 1;
   TAC(PA_T_UPDATE, gemm_t);
   pv->rtr_valid = 2;
   pv->lazy_ptr = NULL;
@@ -997,6 +1166,7 @@ void _preAlps_ECGFree(preAlps_ECG_t* ecg) {
     pa_rt_free(pv->d_info);
     pa_rt_host_free(pv->h_pin);
     pa_rt_host_free(pv->h_pin_i);
+    pa_rt_host_free(pv->h_grp);
     pa_rt_event_destroy(pv->ev_res);
     pa_rt_event_destroy(pv->ev_alpha);
     for (int a = 0; a < 2; ++a) for (int b = 0; b < 6; ++b) pa_rt_graph_free(pv->graph[a][b]);
@@ -1010,6 +1180,10 @@ void _preAlps_ECGFree(preAlps_ECG_t* ecg) {
 }
 
 int preAlps_ECGFinalize(preAlps_ECG_t* ecg, double* solution) {
+  ecg_priv_t* pv = priv_of(ecg);
+  if (pv && pv->nrhs > 1)
+    return PA_FAIL("the solver holds %d systems and one sum over the columns of X would add their solutions: "
+                   "use preAlps_ECGFinalizeMulti", pv->nrhs);
   int rc = _preAlps_ECGWrapUp(ecg, solution);
   _preAlps_ECGFree(ecg);
   return rc;
@@ -1106,6 +1280,7 @@ static int solve_first_step(preAlps_ECG_t* ecg, ecg_priv_t* pv, int ahead, int* 
                            ecg->beta->info.lda, pv->d_uu + (size_t)(1 - pv->uu_cur) * T * T));
   TAC(PA_T_UPDATE, trsm_t);
   pv->rtr_nblk = nb;
+  if (queue_group_norms(pv)) return 1;
   pv->uu_cur ^= 1;
   ecg->iter++;
   /* the norm of the new residual (and the Cholesky status) straight to the pinned words the host reads */
@@ -1124,36 +1299,69 @@ static int solve_first_step(preAlps_ECG_t* ecg, ecg_priv_t* pv, int ahead, int* 
 
 /* The driver loop of examples/test_ecg_prealps_op.c:203-223 (fused:
  * examples/test_ecg_bench_fused.c:243-259). */
+typedef struct {      /* what preAlps_ECGSolveMulti adds to the arguments of preAlps_ECGSolve; nrhs = 0: the latter */
+  int nrhs, ldrhs, ldsol;
+  double* sys_hist; double* sys_normb;
+} multi_args_t;
 static int ecg_solve_loop(preAlps_ECG_t* ecg, double* rhs, double* sol, double* res_hist, int* bs_hist,
-                          int max_hist, int* n_hist);
+                          int max_hist, int* n_hist, const multi_args_t* mu);
 static void leave_own_loop(void) {
   if (--g_own_loop == 0) { pa_k_spmm_gram_disarm(NULL); pa_k_bj_gram_disarm(NULL); }
 }
 int preAlps_ECGSolve(preAlps_ECG_t* ecg, double* rhs, double* sol, double* res_hist, int* bs_hist,
                      int max_hist, int* n_hist) {
   ++g_own_loop;
-  int rc = ecg_solve_loop(ecg, rhs, sol, res_hist, bs_hist, max_hist, n_hist);
+  const multi_args_t one = {0, 0, 0, NULL, NULL};
+  int rc = ecg_solve_loop(ecg, rhs, sol, res_hist, bs_hist, max_hist, n_hist, &one);
   leave_own_loop();
   return rc;
 }
-static int ecg_solve_loop(preAlps_ECG_t* ecg, double* rhs, double* sol, double* res_hist, int* bs_hist,
+/* preAlps_ECGInitializeMulti, the loop of preAlps_ECGSolve (the same body, so the same branch of it for the same
+ * settings), preAlps_ECGFinalizeMulti. */
+int preAlps_ECGSolveMulti(preAlps_ECG_t* ecg, int nrhs, const double* rhs, int ldrhs, double* sol, int ldsol,
+                          double* res_hist, int* bs_hist, double* sys_hist, double* sys_normb,
                           int max_hist, int* n_hist) {
+  const pa_operator_info_t* op = pa_operator_info();
+  if (nrhs < 1) return PA_FAIL("nrhs = %d: at least one right-hand side is needed", nrhs);
+  if (sol && op && ldsol < op->m) return PA_FAIL("ldsol = %d is smaller than the %d local rows", ldsol, op->m);
+  const multi_args_t mu = {nrhs, ldrhs, ldsol, sys_hist, sys_normb};
+  ++g_own_loop;
+  int rc = ecg_solve_loop(ecg, (double*)rhs, sol, res_hist, bs_hist, max_hist, n_hist, &mu);
+  leave_own_loop();
+  return rc;
+}
+/* one entry of the histories after a stopping test */
+static void record_hist(preAlps_ECG_t* ecg, const multi_args_t* mu, double* res_hist, int* bs_hist, int max_hist,
+                        int nh) {
+  if (nh >= max_hist) return;
+  if (res_hist) { res_hist[nh] = ecg->res; if (bs_hist) bs_hist[nh] = ecg->bs; }
+  if (mu->nrhs > 0 && mu->sys_hist) {
+    ecg_priv_t* pv = priv_of(ecg);
+    for (int j = 0; j < mu->nrhs; ++j)
+      mu->sys_hist[nh + (size_t)j * max_hist] = (pv && pv->nrhs > 1) ? pv->sys_res[j] : ecg->res;
+  }
+}
+static int ecg_solve_loop(preAlps_ECG_t* ecg, double* rhs, double* sol, double* res_hist, int* bs_hist,
+                          int max_hist, int* n_hist, const multi_args_t* mu) {
   int rci = 0, stop = 0, nh = 0;
-  if (preAlps_ECGInitialize(ecg, rhs, &rci)) return 1;
+  if (mu->nrhs > 0) {
+    if (preAlps_ECGInitializeMulti(ecg, mu->nrhs, rhs, mu->ldrhs, &rci)) return 1;
+    if (mu->sys_normb && preAlps_ECGSystemResiduals(ecg, NULL, mu->sys_normb)) return 1;
+  } else if (preAlps_ECGInitialize(ecg, rhs, &rci)) return 1;
   if (preAlps_BlockJacobiApply(ecg->R, ecg->P)) return 1;
   ecg_priv_t* pvg = priv_of(ecg);
   if (pvg && pvg->use_graphs) {
     if (preAlps_BlockOperator(ecg->P, ecg->AP)) return 1;
     while (stop != 1) {
       if (graph_iteration(ecg, pvg, &rci, &stop)) return 1;
-      if (res_hist && nh < max_hist) { res_hist[nh] = ecg->res; if (bs_hist) bs_hist[nh] = ecg->bs; }
+      record_hist(ecg, mu, res_hist, bs_hist, max_hist, nh);
       ++nh;
     }
   } else if (pvg && ecg->ortho_alg != ORTHODIR_FUSED && solve_first_applies(ecg, pvg)) {
     if (preAlps_BlockOperator(ecg->P, ecg->AP)) return 1;
     while (stop != 1) {
       if (solve_first_step(ecg, pvg, 1, &stop)) return 1;
-      if (res_hist && nh < max_hist) { res_hist[nh] = ecg->res; if (bs_hist) bs_hist[nh] = ecg->bs; }
+      record_hist(ecg, mu, res_hist, bs_hist, max_hist, nh);
       ++nh;
     }
   } else if (ecg->ortho_alg != ORTHODIR_FUSED) {
@@ -1187,7 +1395,7 @@ static int ecg_solve_loop(preAlps_ECG_t* ecg, double* rhs, double* sol, double* 
           else if (preAlps_BlockJacobiApply(ecg->AP, ecg->Z)) return 1;
         }
         if (stopping_end(ecg, pv, &stop)) return 1;
-        if (res_hist && nh < max_hist) { res_hist[nh] = ecg->res; if (bs_hist) bs_hist[nh] = ecg->bs; }
+        record_hist(ecg, mu, res_hist, bs_hist, max_hist, nh);
         ++nh;
         if (stop == 1) break;
       }
@@ -1197,12 +1405,12 @@ static int ecg_solve_loop(preAlps_ECG_t* ecg, double* rhs, double* sol, double* 
       if (preAlps_BlockOperator(ecg->P, ecg->AP)) return 1;
       if (preAlps_BlockJacobiApply(ecg->AP, ecg->Z)) return 1;
       if (preAlps_ECGIterate(ecg, &rci)) return 1;
-      if (res_hist && nh < max_hist) { res_hist[nh] = ecg->res; if (bs_hist) bs_hist[nh] = ecg->bs; }
+      record_hist(ecg, mu, res_hist, bs_hist, max_hist, nh);
       ++nh;
     }
   }
   if (n_hist) *n_hist = nh < max_hist ? nh : max_hist;
-  if (sol) return preAlps_ECGFinalize(ecg, sol);
+  if (sol) return mu->nrhs > 0 ? preAlps_ECGFinalizeMulti(ecg, sol, mu->ldsol) : preAlps_ECGFinalize(ecg, sol);
   return 0;
 }
 
@@ -1213,6 +1421,10 @@ static int ecg_advance_loop(preAlps_ECG_t* ecg, double* rhs, int* rci_request, i
                             int* last_iters, double* last_res);
 int preAlps_ECGAdvance(preAlps_ECG_t* ecg, double* rhs, int* rci_request, int nsteps, int* restarts,
                        int* last_iters, double* last_res) {
+  ecg_priv_t* pvm = priv_of(ecg);
+  if (pvm && pvm->nrhs > 1)
+    return PA_FAIL("the solver holds %d systems: restarts from one right-hand side are not defined for it "
+                   "(use preAlps_ECGSolveMulti or the caller's own loop)", pvm->nrhs);
   ++g_own_loop;
   int rc = ecg_advance_loop(ecg, rhs, rci_request, nsteps, restarts, last_iters, last_res);
   leave_own_loop();

@@ -1737,6 +1737,82 @@ __global__ __launch_bounds__(WG) void k_rowsum(int m, int nc, const double* __re
   }
 }
 
+// ---- several right-hand sides (preAlps_ECGInitializeMulti / FinalizeMulti) ----
+// The start: system j owns the columns j*s .. j*s + s - 1 of the panel, and a row of part p puts B(row, j) into
+// column j*s + (p % s) (pcol[row] = p % s); every other entry of R0 is zero.  Each workgroup leaves the sums of
+// B(:, j)^2 over its rows in sums[blk*TS + j], the layout of k_colnorm2, for k_group_norms.
+template <int TS>
+__global__ __launch_bounds__(WG) void k_multi_start(int m, int k, int s, const double* __restrict__ B, size_t ldb,
+                                                    const int* __restrict__ pcol, double* __restrict__ R,
+                                                    double* __restrict__ sums) {
+  double acc[TS];
+#pragma unroll
+  for (int j = 0; j < TS; ++j) acc[j] = 0.0;
+  const int nc = k * s;
+  const size_t stride = (size_t)gridDim.x * WG;
+  for (size_t row = (size_t)blockIdx.x * WG + threadIdx.x; row < (size_t)m; row += stride) {
+    const int pc = pcol[row];
+    double r[TS];
+#pragma unroll
+    for (int c = 0; c < TS; ++c) {
+      const int j = c / s;
+      r[c] = (c < nc && c - j * s == pc) ? B[row + (size_t)j * ldb] : 0.0;
+    }
+    store_row<TS>(R, row, r);
+#pragma unroll
+    for (int j = 0; j < TS; ++j)
+      if (j < k) { const double v = B[row + (size_t)j * ldb]; acc[j] = fma(v, v, acc[j]); }
+  }
+  block_sum_cols<TS>(acc, sums + (size_t)blockIdx.x * TS);
+}
+
+// The per-system sums of the stopping test: out[j] = sum over the s columns of system j (ascending) of the sum over
+// the blocks of rtr[blk*ts + c] (the column sums of R^2 an update kernel or k_colnorm2 left).  One workgroup; 16
+// threads per column take the blocks b = l, l + 16, ... in turn and are folded by a fixed tree, so the k values are
+// reproducible.  The values go to device memory and to pinned host words, which the host reads once the launch or
+// event behind this one has completed (it keys on nothing this kernel writes).
+__global__ __launch_bounds__(WG) void k_group_norms(const double* __restrict__ rtr, int nblk, int ts, int k, int s,
+                                                    double* __restrict__ out, double* host) {
+  __shared__ double red[WG];
+  const int c = threadIdx.x >> 4, l = threadIdx.x & 15;
+  double v = 0.0;
+  if (c < k * s)
+    for (int b = l; b < nblk; b += 16) v += rtr[(size_t)b * ts + c];
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int off = 8; off > 0; off >>= 1) {
+    if (l < off) red[threadIdx.x] += red[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x < k) {
+    double g = 0.0;
+    for (int q = 0; q < s; ++q) g += red[(threadIdx.x * s + q) << 4];
+    out[threadIdx.x] = g;
+    if (host) __hip_atomic_store(host + threadIdx.x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  __threadfence_system();
+}
+
+// The finish: sol[row + j*ld] = sum of X(row, c) over the columns of system j, added in ascending c as k_rowsum does.
+template <int TS>
+__global__ __launch_bounds__(WG) void k_rowsum_groups(int m, int k, int s, const double* __restrict__ X,
+                                                      double* __restrict__ sol, size_t ld) {
+  const int nc = k * s;
+  const size_t stride = (size_t)gridDim.x * WG;
+  for (size_t row = (size_t)blockIdx.x * WG + threadIdx.x; row < (size_t)m; row += stride) {
+    double x[TS];
+    load_row<TS>(X, row, x);
+    double acc = 0.0;
+    int j = 0, cnt = 0;
+#pragma unroll
+    for (int c = 0; c < TS; ++c)
+      if (c < nc) {
+        acc += x[c];
+        if (++cnt == s) { sol[row + (size_t)j * ld] = acc; acc = 0.0; cnt = 0; ++j; }
+      }
+  }
+}
+
 inline int grid_rows(int m, int per_thread_rows = 1) {
   long long blocks = ((long long)m + (long long)WG * per_thread_rows - 1) / ((long long)WG * per_thread_rows);
   if (blocks < 1) blocks = 1;
@@ -2087,6 +2163,36 @@ int pa_k_rowsum(int m, int ts, int nc, const double* X, double* sol) {
   TS_DISPATCH(ts, PA_LAUNCH((k_rowsum<TS_>), dim3(grid_rows(m, 2)), dim3(WG), 0,
                                      cur_stream(), m, nc, X, sol));
   return kfail("k_rowsum");
+}
+
+static int multi_args_bad(const char* what, int ts, int k, int s) {
+  if (k >= 1 && s >= 1 && k * s <= ts && ts <= 16) return 0;
+  snprintf(g_kerr, sizeof(g_kerr), "%s: %d systems of %d columns do not fit a panel of stride %d", what, k, s, ts);
+  return 1;
+}
+
+int pa_k_multi_start(int m, int ts, int k, int s, const double* B, int ldb, const int* pcol, double* R,
+                     double* sums, int* nblk) {
+  if (multi_args_bad("pa_k_multi_start", ts, k, s)) return 1;
+  int blocks = grid_rows(m, 4);
+  if (blocks > GRAM_MAX_BLOCKS) blocks = GRAM_MAX_BLOCKS;
+  *nblk = blocks;
+  TS_DISPATCH(ts, PA_LAUNCH((k_multi_start<TS_>), dim3(blocks), dim3(WG), 0, cur_stream(), m, k, s, B, (size_t)ldb,
+                            pcol, R, sums));
+  return kfail("k_multi_start");
+}
+
+int pa_k_group_norms(const double* rtr_partials, int nblk, int ts, int k, int s, double* out, double* host) {
+  if (multi_args_bad("pa_k_group_norms", ts, k, s)) return 1;
+  PA_LAUNCH(k_group_norms, dim3(1), dim3(WG), 0, cur_stream(), rtr_partials, nblk, ts, k, s, out, host);
+  return kfail("k_group_norms");
+}
+
+int pa_k_rowsum_groups(int m, int ts, int k, int s, const double* X, double* sol, int ld) {
+  if (multi_args_bad("pa_k_rowsum_groups", ts, k, s)) return 1;
+  TS_DISPATCH(ts, PA_LAUNCH((k_rowsum_groups<TS_>), dim3(grid_rows(m, 2)), dim3(WG), 0, cur_stream(), m, k, s, X,
+                            sol, (size_t)ld));
+  return kfail("k_rowsum_groups");
 }
 
 }  // extern "C"

@@ -221,6 +221,16 @@ int pa_k_permute_trsm(int m, int ts, int n, const int* piv, int t, const double*
 int pa_k_permute_cols(int m, int ts, int n, const int* piv, double* A);
 /* sol[i] = sum_j X[i][j], j < nc (ecg.c:674). */
 int pa_k_rowsum(int m, int ts, int nc, const double* X, double* sol);
+/* Several right-hand sides: system j of k owns the columns j*s .. j*s + s - 1 (k*s <= ts).
+ * R0 (m x ts, zero-filled) with B(row, j) in column j*s + pcol[row]; sums[blk*ts + j] = the block's share of
+ * sum B(:, j)^2 (*nblk blocks, the layout of pa_k_colnorm2).  B: device, column major, ldb >= m; pcol: m ints. */
+int pa_k_multi_start(int m, int ts, int k, int s, const double* B, int ldb, const int* pcol, double* R,
+                     double* sums, int* nblk);
+/* out[j] = sum over the columns of system j (ascending) of the sum over the blocks of rtr_partials[blk*ts + c],
+ * one workgroup, fixed order; host (pinned, device-visible, may be NULL) receives the same k values. */
+int pa_k_group_norms(const double* rtr_partials, int nblk, int ts, int k, int s, double* out, double* host);
+/* sol[i + j*ld] = sum of X[i][c] over the columns of system j, ascending c (pa_k_rowsum per system). */
+int pa_k_rowsum_groups(int m, int ts, int k, int s, const double* X, double* sol, int ld);
 
 /* ---- block-Jacobi apply (block_jacobi.c:93-109, K8) --------------------- */
 typedef struct {

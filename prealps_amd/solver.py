@@ -32,6 +32,10 @@ class EcgResult:
     normb: float
     seconds: float = 0.0
     timers: dict = field(default_factory=dict)
+    # solve_multi only: g_j at the stop, ||b_j||, and g_j after every stopping test (iterations x systems)
+    sys_res: np.ndarray = None
+    sys_normb: np.ndarray = None
+    sys_hist: np.ndarray = None
 
 
 class DistributedHooks:
@@ -337,6 +341,48 @@ class EcgProblem:
         timers = {k: getattr(e, k) for k in ("tot_t", "comm_t", "trsm_t", "gemm_t", "potrf_t", "copy_t")}
         return EcgResult(x=sol, iters=e.iter, res=res[:nh.value].copy(), bs=bs[:nh.value].copy(),
                          final_res=e.res, final_bs=e.bs, normb=e.normb, seconds=dt, timers=timers)
+
+    def solve_multi(self, B, t, ortho_alg=ORTHODIR, bs_red=NO_BS_RED, tol=1e-5, max_iter=1000):
+        """preAlps_ECGSolveMulti: the k columns of B (m x k) as k systems solved by one block iteration of
+        enlarging factor t, a multiple of k; system j owns the columns j*t/k .. (j+1)*t/k - 1 of the panels.
+        Returns an EcgResult with x of shape (m, k), res / bs as solve() (the Frobenius norm of all of R) and
+        sys_res, sys_normb (k values) and sys_hist (iterations x k): the per-system residual norms the
+        stopping test uses.  ||b_j - A x_j|| <= sqrt(t / k) * sys_res[j] in exact arithmetic."""
+        Bs = np.shape(B)
+        if len(Bs) != 2:
+            raise ValueError("B must be two-dimensional (m x k), not of shape %r" % (Bs,))
+        if Bs[0] != self.m:
+            raise ValueError("B has %d rows, the operator has %d local rows" % (Bs[0], self.m))
+        k = int(Bs[1])
+        if k < 1 or int(t) % k != 0:
+            raise ValueError("the enlarging factor t = %d is not a multiple of the %d right-hand sides" % (t, k))
+        if not self.has_precond:
+            self.create_block_jacobi()
+        import time
+        L = self.L
+        check(L.preAlps_hip_prepare_operator(int(t)), "preAlps_hip_prepare_operator")
+        e = self.new_ecg(t, ortho_alg, bs_red, tol, max_iter)
+        B = np.asfortranarray(B, dtype=np.float64)
+        ld = max(self.m, 1)
+        sol = np.zeros((self.m, k), order="F")
+        cap = max_iter + 2
+        res = np.zeros(cap)
+        bs = np.zeros(cap, dtype=np.int32)
+        sys_hist = np.zeros((cap, k), order="F")
+        sys_normb = np.zeros(k)
+        sys_res = np.zeros(k)
+        nh = C.c_int()
+        t0 = time.perf_counter()
+        check(L.preAlps_ECGSolveMulti(C.byref(e), k, _pd(B), ld, _pd(sol), ld, _pd(res), _pi(bs), _pd(sys_hist),
+                                      _pd(sys_normb), cap, C.byref(nh)), "preAlps_ECGSolveMulti")
+        dt = time.perf_counter() - t0
+        n = nh.value
+        if n:
+            sys_res = sys_hist[n - 1].copy()
+        timers = {k_: getattr(e, k_) for k_ in ("tot_t", "comm_t", "trsm_t", "gemm_t", "potrf_t", "copy_t")}
+        return EcgResult(x=sol, iters=e.iter, res=res[:n].copy(), bs=bs[:n].copy(), final_res=e.res,
+                         final_bs=e.bs, normb=e.normb, seconds=dt, timers=timers, sys_res=sys_res,
+                         sys_normb=sys_normb, sys_hist=np.ascontiguousarray(sys_hist[:n]))
 
     # -- single operations, for tests and micro-benchmarks -----------------------
     def panel(self, ncols, t):
