@@ -149,6 +149,49 @@ int preAlps_ECGFinalizeMulti(preAlps_ECG_t* ecg, double* sol, int ldsol);
 int preAlps_ECGSolveMulti(preAlps_ECG_t* ecg, int nrhs, const double* rhs, int ldrhs, double* sol, int ldsol,
                           double* res_hist, int* bs_hist, double* sys_hist, double* sys_normb,
                           int max_hist, int* n_hist);
+/* ---- a start from an initial guess, for one and several systems -------------------------------------------------
+ * preAlps_ECGInitializeMulti / preAlps_ECGSolveMulti with a starting value x0 for every system: the local rows,
+ * column major, nrhs columns, ldx0 >= m.  x0 == NULL: those two entries themselves, the same code path and the same
+ * bits (sys_res0, if given, then receives ||b_j||).  Every existing entry keeps its behaviour and its bits.
+ *   Start: the iteration needs nothing new.  The solution of system j is the sum of its s columns of X and its
+ * residual the sum of its columns of R, so X0 is written by the placement rule above -- a row of part p puts x0_j into
+ * column j*s + (p % s), zero elsewhere, and the sum of the columns is x0_j bit for bit -- and R0 is the same split of
+ * r0_j = b_j - (the sum of system j's columns of A X0, added in ascending column order); every later update keeps
+ * sum_c R(:, c) = b_j - A sum_c X(:, c).  A X0 is one product of the library's own SpMM at the solver's width (the
+ * path of preAlps_BlockOperator, no new plan, no Gram block asked of it); the panel it is written to is zeroed again.
+ *   Norms and stopping: sys_normb[j] = ||b_j|| and ecg->normb = ||B||_F as without a guess -- the test stays relative
+ * to the right-hand side, not to r0.  g0_j = the Frobenius norm of system j's columns of R0, formed on the device.
+ * After the initialise preAlps_ECGSystemResiduals returns g0_j and ecg->res is ||R0||_F.  preAlps_ECGInitializeGuess
+ * followed by preAlps_ECGSystemResiduals (and preAlps_ECGFinalizeMulti to release the solver) is therefore also the
+ * library's answer to "what is ||b - A x|| for this x", in fp64 from the iterate: a residual refresh after a long
+ * run or after a solve with the opt-in fp32 factors (s = 1: exactly that norm; s > 1: the norm of its split, which
+ * bounds it by sqrt(s)).
+ *   Already converged: if g0_j <= tol * ||b_j|| for every j, preAlps_ECGSolveGuess does no iteration: *n_hist = 0,
+ * ecg->iter = 0, sol receives x0 bit for bit, and nothing of the iteration is queued, neither the block solve nor
+ * the product.
+ *   Refused (the message names the entry point): everything preAlps_ECGInitializeMulti refuses (nrhs, divisibility,
+ * s against the number of parts, ldrhs, a right-hand side of norm zero, ORTHODIR_FUSED, more than one process, a
+ * preAlps_hip_loopback shard); ldx0 < m; a start residual that is not finite (NaN or Inf in x0), which reports the
+ * system; and a system whose r0_j is exactly zero beside one whose is not ("system %d starts with a zero residual
+ * ..."): its columns of the block would be empty and P^T A P singular, as with a zero right-hand side.  A small but
+ * nonzero start residual is no error: a system that starts at 1e-8 ||b_j|| iterates beside systems that start at
+ * ||b_j|| (the Cholesky factorisation is invariant to the scaling of the columns) and stays converged.  With
+ * bs_red = ADAPT_BS it is not known whether the reduction's threshold drops the columns of such a system; as with
+ * linearly dependent right-hand sides above, that combination is the caller's business.
+ *   Afterwards: preAlps_ECGAdvance is refused on a solver started from a guess, because it restarts from rhs alone
+ * and would drop x0.  preAlps_ECGFinalize (one system) and preAlps_ECGFinalizeMulti work unchanged;
+ * _preAlps_ECGReset makes the solver a cold one again; the caller's own loop of preAlps_ECGIterate /
+ * preAlps_BlockOperator / preAlps_BlockJacobiApply / preAlps_ECGStoppingCriterion works as after
+ * preAlps_ECGInitializeMulti.  HIP graphs and PREALPS_ECG_POLL are off for such a solver, as for several systems;
+ * the order of the iteration (solve first, lazy normalisation, lazy stopping test) is decided by the solver's
+ * description as always: the start is outside the loop. */
+int preAlps_ECGInitializeGuess(preAlps_ECG_t* ecg, int nrhs, const double* rhs, int ldrhs,
+                               const double* x0, int ldx0, int* rci_request);
+/* preAlps_ECGSolveMulti around that start; sys_res0 (may be NULL): the nrhs start residuals g0_j */
+int preAlps_ECGSolveGuess(preAlps_ECG_t* ecg, int nrhs, const double* rhs, int ldrhs,
+                          const double* x0, int ldx0, double* sol, int ldsol,
+                          double* res_hist, int* bs_hist, double* sys_hist, double* sys_normb,
+                          double* sys_res0, int max_hist, int* n_hist);
 /* 1 / 0: the two driver loops above and below replay each half of an iteration from a HIP graph
  * captured on its first passes (default: off, or PREALPS_ECG_GRAPH; plain launches measured faster). */
 void preAlps_hip_graphs(int on);

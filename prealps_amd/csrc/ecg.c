@@ -113,6 +113,10 @@ typedef struct {
   int nrhs, sgrp;
   double* d_grp; double* h_grp;
   double sys_res[16], sys_normb[16];
+  /* 1: started from an initial guess (preAlps_ECGInitializeGuess): X0 is in X and R0 = split(B - A X0).  The
+   * iteration is unchanged; graphs and polling are off, and preAlps_ECGAdvance, which restarts from the right-hand
+   * side alone, is refused.  _preAlps_ECGReset makes the solver a cold one again. */
+  int guess;
 } ecg_priv_t;
 
 static ecg_priv_t* priv_of(preAlps_ECG_t* ecg) {
@@ -238,9 +242,10 @@ static void request_gram_from_spmm(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
 
 /* ------------------------------------------------------------- reset ---- */
 /* Everything of a reset but R0 and the norm of the right-hand side: timers, pointer order, the switches, the
- * descriptors, the zeroed pool.  nrhs: the systems the solver will hold (1 from _preAlps_ECGReset). */
-static int reset_state(preAlps_ECG_t* ecg, ecg_priv_t* pv, int nrhs) {
-  pv->nrhs = nrhs; pv->sgrp = ecg->enlFac / nrhs;
+ * descriptors, the zeroed pool.  nrhs: the systems the solver will hold (1 from _preAlps_ECGReset); guess: it starts
+ * from an initial guess. */
+static int reset_state(preAlps_ECG_t* ecg, ecg_priv_t* pv, int nrhs, int guess) {
+  pv->nrhs = nrhs; pv->sgrp = ecg->enlFac / nrhs; pv->guess = guess;
   ecg->tot_t = ecg->comm_t = ecg->trsm_t = ecg->gemm_t = ecg->potrf_t = ecg->pstrf_t = 0.0;
   ecg->lapmt_t = ecg->gesvd_t = ecg->geqrf_t = ecg->ormqr_t = ecg->copy_t = 0.0;
   int M = ecg->globPbSize, m = ecg->locPbSize, t = ecg->enlFac, ts = pv->ts;
@@ -283,6 +288,7 @@ static int reset_state(preAlps_ECG_t* ecg, ecg_priv_t* pv, int nrhs) {
     const char* ge = getenv("PREALPS_ECG_GRAPH");
     int want = g_graphs >= 0 ? g_graphs : (ge ? atoi(ge) : 0);
     if (nrhs > 1) want = 0;      /* (several systems: the group launch is not part of the captured segments) */
+    if (guess) want = 0;         /* (a start from a guess: as for several systems, whatever nrhs) */
     int group_ok = pa_world_size() == 1 || pa_comm_is_loopback() || want == 2;
     pv->use_graphs = want && group_ok && pv->rotate && pv->fuse && ecg->ortho_alg != ORTHODIR_FUSED &&
                      !pa_timing_enabled();
@@ -298,7 +304,7 @@ static int reset_state(preAlps_ECG_t* ecg, ecg_priv_t* pv, int nrhs) {
   { const char* f = getenv("PREALPS_ECG_POLL"); pv->poll = (f ? atoi(f) : pa_world_size() > 1) && !pv->use_graphs;
     /* several systems: the per-system sums may be queued behind the launch that writes the polled word, so the
      * host waits for the event behind both */
-    if (nrhs > 1) pv->poll = 0; }
+    if (nrhs > 1 || guess) pv->poll = 0; }
   pv->sent_seq = pv->wait_seq = 0.0;
   if (pv->h_pin) pv->h_pin[2] = 0.0;
   pa_set_desc(ecg->X, M, t, m, t, ts);
@@ -340,7 +346,7 @@ int _preAlps_ECGReset(preAlps_ECG_t* ecg, double* rhs, int* rci_request) {
   if (!op) return PA_FAIL("the operator must be built before the solver");
   if (ecg->locPbSize != op->m) return PA_FAIL("locPbSize %d differs from the operator's %d rows", ecg->locPbSize, op->m);
   if (pv->nrhs > 1) return PA_FAIL("the solver holds %d systems: restart it with preAlps_ECGInitializeMulti", pv->nrhs);
-  if (reset_state(ecg, pv, 1)) return 1;
+  if (reset_state(ecg, pv, 1, 0)) return 1;
   int m = ecg->locPbSize, t = ecg->enlFac, ts = pv->ts;
   /* normb and R0: column (rank % t) of every reference rank = part */
   double nb2 = 0.0;
@@ -387,47 +393,59 @@ int preAlps_ECGInitialize(preAlps_ECG_t* ecg, double* rhs, int* rci_request) {
  * one of a single system at the same enlarging factor, launch for launch; what differs is the start (on the device:
  * pa_k_multi_start), the stopping test (every system against its own right-hand side, from the sums
  * pa_k_group_norms leaves behind each update) and the finish (pa_k_rowsum_groups).  nrhs = 1 is
- * preAlps_ECGInitialize. */
-int preAlps_ECGInitializeMulti(preAlps_ECG_t* ecg, int nrhs, const double* rhs, int ldrhs, int* rci_request) {
+ * preAlps_ECGInitialize.
+ *   With an initial guess (x0 != NULL, preAlps_ECGInitializeGuess) only the start differs again: X0 goes into X by the
+ * same placement rule (pa_k_guess_split), so the sum of a system's columns is x0_j bit for bit; A X0 is one plain
+ * product of the library at the solver's width into the Z panel, issued before reset_done so that no Gram block is
+ * asked of it; pa_k_guess_start writes R0 = the split of b_j - (the sum of system j's columns of A X0) and leaves the
+ * sums of b_j^2 and of R0(:, c)^2; the Z panel and the partial sums are zeroed again, so the pool is what reset_state
+ * leaves but for X and R.  Every later update keeps sum_c R(:, c) = b_j - A sum_c X(:, c).  who: the entry point the
+ * refusals name. */
+#define FAIL_AS(who, ...) pa_fail_at(who, __VA_ARGS__)
+static int start_systems(const char* who, preAlps_ECG_t* ecg, int nrhs, const double* rhs, int ldrhs,
+                         const double* x0, int ldx0, int* rci_request) {
   const pa_operator_info_t* op = pa_operator_info();
-  if (!op) return PA_FAIL("the operator must be built before the solver");
-  if (!ecg || !rhs || !rci_request) return PA_FAIL(" wrong test 'ecg != NULL && rhs != NULL && rci_request != NULL'");
-  if (nrhs < 1) return PA_FAIL("nrhs = %d: at least one right-hand side is needed", nrhs);
+  if (!op) return FAIL_AS(who, "the operator must be built before the solver");
+  if (!ecg || !rhs || !rci_request) return FAIL_AS(who, " wrong test 'ecg != NULL && rhs != NULL && rci_request != NULL'");
+  if (nrhs < 1) return FAIL_AS(who, "nrhs = %d: at least one right-hand side is needed", nrhs);
   if (ecg->enlFac < 1 || ecg->enlFac % nrhs != 0)
-    return PA_FAIL("the enlarging factor %d is not a multiple of nrhs = %d", ecg->enlFac, nrhs);
+    return FAIL_AS(who, "the enlarging factor %d is not a multiple of nrhs = %d", ecg->enlFac, nrhs);
   const int k = nrhs, s = ecg->enlFac / nrhs, m = op->m;
   if (op->nparts < s)
-    return PA_FAIL("Enlarging factor per system must be lower than the number of processors"
+    return FAIL_AS(who, "Enlarging factor per system must be lower than the number of processors"
                    " in the MPI communicator! size: %d ; enlarging factor per system: %d", op->nparts, s);
-  if (ldrhs < m) return PA_FAIL("ldrhs = %d is smaller than the %d local rows", ldrhs, m);
+  if (ldrhs < m) return FAIL_AS(who, "ldrhs = %d is smaller than the %d local rows", ldrhs, m);
+  if (x0 && ldx0 < m) return FAIL_AS(who, "ldx0 = %d is smaller than the %d local rows", ldx0, m);
   if (ecg->ortho_alg == ORTHODIR_FUSED)
-    return PA_FAIL("ORTHODIR_FUSED decides inside preAlps_ECGIterate on one sum: no per-system stopping test");
+    return FAIL_AS(who, "ORTHODIR_FUSED decides inside preAlps_ECGIterate on one sum: no per-system stopping test");
   if (pa_world_size() > 1 || pa_comm_is_loopback())
-    return PA_FAIL("several right-hand sides need a single process (%d processes%s)", pa_world_size(),
+    return FAIL_AS(who, "%s need a single process (%d processes%s)",
+                   x0 ? "an initial guess and several right-hand sides" : "several right-hand sides", pa_world_size(),
                    pa_comm_is_loopback() ? ", preAlps_hip_loopback shard" : "");
   if (_preAlps_ECGMalloc(ecg)) return 1;
   ecg_priv_t* pv = priv_of(ecg);
-  if (k == 1) {
+  if (k == 1 && !x0) {
     if (_preAlps_ECGReset(ecg, (double*)rhs, rci_request)) { _preAlps_ECGFree(ecg); return 1; }
     if (!(ecg->normb > 0.0)) {
       _preAlps_ECGFree(ecg);
-      return PA_FAIL("right-hand side 0 has norm zero: its column of R0 would be empty");
+      return FAIL_AS(who, "right-hand side 0 has norm zero: its column of R0 would be empty");
     }
     return 0;
   }
   if (ecg->locPbSize != m) {
     _preAlps_ECGFree(ecg);
-    return PA_FAIL("locPbSize %d differs from the operator's %d rows", ecg->locPbSize, m);
+    return FAIL_AS(who, "locPbSize %d differs from the operator's %d rows", ecg->locPbSize, m);
   }
-  if (reset_state(ecg, pv, k)) { _preAlps_ECGFree(ecg); return 1; }
-  /* B goes up once (m*k doubles) with p % s of every row; the kernel writes R0 and leaves the k sums of squares */
-  const size_t mm = (size_t)(m > 0 ? m : 1);
+  if (reset_state(ecg, pv, k, x0 != NULL)) { _preAlps_ECGFree(ecg); return 1; }
+  /* B (and X0) go up once (m*k doubles each) with p % s of every row; the kernels write R0 (and X0's panel) and leave
+   * the sums of squares */
+  const size_t mm = (size_t)(m > 0 ? m : 1), cols = (size_t)k * (x0 ? 2 : 1);
   int* pcol = (int*)malloc(mm * sizeof(int));
-  double* d_B = (double*)pa_rt_malloc(mm * k * sizeof(double) + mm * sizeof(int));
+  double* d_B = (double*)pa_rt_malloc(mm * cols * sizeof(double) + mm * sizeof(int));
   int rc = 0, nblk = 0;
-  if (!pcol || !d_B) rc = PA_FAIL("staging %d right-hand sides: %s", k, pcol ? pa_rt_error() : "out of host memory");
+  if (!pcol || !d_B) rc = FAIL_AS(who, "staging %d right-hand sides: %s", k, pcol ? pa_rt_error() : "out of host memory");
   if (!rc) {
-    int* d_pcol = (int*)(d_B + mm * k);
+    int* d_pcol = (int*)(d_B + mm * cols);
     for (int p = op->part0; p < op->part1; ++p) {
       int base = op->rowPos[p] - op->row_off, l = op->rowPos[p + 1] - op->rowPos[p];
       for (int i = 0; i < l; ++i) pcol[base + i] = p % s;
@@ -435,26 +453,83 @@ int preAlps_ECGInitializeMulti(preAlps_ECG_t* ecg, int nrhs, const double* rhs, 
     rc = pa_rt_h2d(d_pcol, pcol, (size_t)m * sizeof(int));
     if (ldrhs == m) rc = rc || pa_rt_h2d(d_B, rhs, (size_t)m * k * sizeof(double));
     else for (int j = 0; j < k && !rc; ++j) rc = pa_rt_h2d(d_B + (size_t)j * m, rhs + (size_t)j * ldrhs, (size_t)m * sizeof(double));
-    rc = rc || pa_k_multi_start(m, pv->ts, k, s, d_B, m, d_pcol, pv->d_R, pv->d_rtr_part, &nblk) ||
-         pa_k_group_norms(pv->d_rtr_part, nblk, pv->ts, k, 1, pv->d_grp + 16, pv->h_grp + 16) || pa_rt_sync();
-    if (rc) rc = PA_FAIL("%s", pa_rt_error());
+    if (!x0) {
+      rc = rc || pa_k_multi_start(m, pv->ts, k, s, d_B, m, d_pcol, pv->d_R, pv->d_rtr_part, &nblk) ||
+           pa_k_group_norms(pv->d_rtr_part, nblk, pv->ts, k, 1, pv->d_grp + 16, pv->h_grp + 16) || pa_rt_sync();
+      if (rc) rc = FAIL_AS(who, "%s", pa_rt_error());
+    } else {
+      double* d_X0 = d_B + mm * k;
+      const size_t panel = mm * pv->ts;
+      if (ldx0 == m) rc = rc || pa_rt_h2d(d_X0, x0, (size_t)m * k * sizeof(double));
+      else for (int j = 0; j < k && !rc; ++j) rc = pa_rt_h2d(d_X0 + (size_t)j * m, x0 + (size_t)j * ldx0, (size_t)m * sizeof(double));
+      rc = rc || pa_k_guess_split(m, pv->ts, k, s, d_X0, m, d_pcol, pv->d_X);
+      if (rc) rc = FAIL_AS(who, "%s", pa_rt_error());
+      /* a plain product: nothing is armed for X -> Z, and reset_done has not asked the SpMM for a block yet */
+      if (!rc) rc = preAlps_BlockOperator(ecg->X, ecg->Z);
+      if (!rc) {
+        rc = pa_k_guess_start(m, pv->ts, k, s, d_B, m, d_pcol, pv->buf_z, pv->d_R, pv->d_partials, pv->d_rtr_part, &nblk) ||
+             pa_k_group_norms(pv->d_partials, nblk, pv->ts, k, 1, pv->d_grp + 16, pv->h_grp + 16) ||
+             pa_k_group_norms(pv->d_rtr_part, nblk, pv->ts, k, s, pv->d_grp, pv->h_grp) ||
+             /* the scratch as reset_state left it: the first update relies on empty panels, padding included */
+             pa_rt_memset(pv->buf_z, 0, panel * sizeof(double)) ||
+             pa_rt_memset(pv->d_partials, 0, (size_t)nblk * pv->ts * sizeof(double)) || pa_rt_sync();
+        if (rc) rc = FAIL_AS(who, "%s", pa_rt_error());
+      }
+    }
   }
   pa_rt_free(d_B);
   free(pcol);
+  double r2 = 0.0;
   if (!rc) {
     double nb2 = 0.0;
+    if (k == 1) {   /* one system: the sum of _preAlps_ECGReset, part by part on the host, so ecg->normb has its bits */
+      for (int p = op->part0; p < op->part1; ++p) {
+        int base = op->rowPos[p] - op->row_off, l = op->rowPos[p + 1] - op->rowPos[p];
+        double sp = 0.0;
+        for (int i = 0; i < l; ++i) { double v = rhs[base + i]; sp += v * v; }
+        nb2 += sp;
+      }
+      pv->h_grp[16] = nb2;
+      nb2 = 0.0;
+    }
     for (int j = 0; j < k && !rc; ++j) {
       const double b2 = pv->h_grp[16 + j];
-      if (!(b2 > 0.0)) rc = PA_FAIL("right-hand side %d has norm zero: its column of R0 would be empty", j);
+      if (!(b2 > 0.0)) rc = FAIL_AS(who, "right-hand side %d has norm zero: its column of R0 would be empty", j);
       pv->sys_normb[j] = sqrt(b2);
       pv->sys_res[j] = pv->sys_normb[j];
       nb2 += b2;
     }
     ecg->normb = sqrt(nb2);
   }
+  if (!rc && x0) {
+    int nzero = 0, first_zero = -1;
+    for (int j = 0; j < k && !rc; ++j) {
+      const double g2 = pv->h_grp[j];
+      if (!(g2 - g2 == 0.0))
+        rc = FAIL_AS(who, "system %d starts with a residual that is not finite (NaN or Inf in x0 or in the right-hand side)", j);
+      if (g2 == 0.0) { ++nzero; if (first_zero < 0) first_zero = j; }
+      pv->sys_res[j] = sqrt(g2);
+      r2 += g2;
+    }
+    if (!rc && nzero > 0 && nzero < k)
+      rc = FAIL_AS(who, "system %d starts with a zero residual beside systems that do not: its columns of the block "
+                        "would be empty and P^T A P singular (solve the others without it)", first_zero);
+  }
   if (rc) { _preAlps_ECGFree(ecg); return 1; }
   reset_done(ecg, pv, rci_request);
+  if (x0) ecg->res = sqrt(r2);     /* ||R0||_F; with one system this is what preAlps_ECGSystemResiduals returns */
   return 0;
+}
+
+int preAlps_ECGInitializeMulti(preAlps_ECG_t* ecg, int nrhs, const double* rhs, int ldrhs, int* rci_request) {
+  return start_systems(__func__, ecg, nrhs, rhs, ldrhs, NULL, 0, rci_request);
+}
+
+/* x0 == NULL: preAlps_ECGInitializeMulti, the same path. */
+int preAlps_ECGInitializeGuess(preAlps_ECG_t* ecg, int nrhs, const double* rhs, int ldrhs, const double* x0, int ldx0,
+                               int* rci_request) {
+  if (!x0) return start_systems("preAlps_ECGInitializeMulti", ecg, nrhs, rhs, ldrhs, NULL, 0, rci_request);
+  return start_systems(__func__, ecg, nrhs, rhs, ldrhs, x0, ldx0, rci_request);
 }
 
 int preAlps_ECGSystemResiduals(preAlps_ECG_t* ecg, double* sys_res, double* sys_normb) {
@@ -1302,6 +1377,7 @@ static int solve_first_step(preAlps_ECG_t* ecg, ecg_priv_t* pv, int ahead, int* 
 typedef struct {      /* what preAlps_ECGSolveMulti adds to the arguments of preAlps_ECGSolve; nrhs = 0: the latter */
   int nrhs, ldrhs, ldsol;
   double* sys_hist; double* sys_normb;
+  const double* x0; int ldx0; double* sys_res0;   /* ... and preAlps_ECGSolveGuess to those; x0 = NULL: the former */
 } multi_args_t;
 static int ecg_solve_loop(preAlps_ECG_t* ecg, double* rhs, double* sol, double* res_hist, int* bs_hist,
                           int max_hist, int* n_hist, const multi_args_t* mu);
@@ -1311,7 +1387,7 @@ static void leave_own_loop(void) {
 int preAlps_ECGSolve(preAlps_ECG_t* ecg, double* rhs, double* sol, double* res_hist, int* bs_hist,
                      int max_hist, int* n_hist) {
   ++g_own_loop;
-  const multi_args_t one = {0, 0, 0, NULL, NULL};
+  const multi_args_t one = {0, 0, 0, NULL, NULL, NULL, 0, NULL};
   int rc = ecg_solve_loop(ecg, rhs, sol, res_hist, bs_hist, max_hist, n_hist, &one);
   leave_own_loop();
   return rc;
@@ -1324,7 +1400,21 @@ int preAlps_ECGSolveMulti(preAlps_ECG_t* ecg, int nrhs, const double* rhs, int l
   const pa_operator_info_t* op = pa_operator_info();
   if (nrhs < 1) return PA_FAIL("nrhs = %d: at least one right-hand side is needed", nrhs);
   if (sol && op && ldsol < op->m) return PA_FAIL("ldsol = %d is smaller than the %d local rows", ldsol, op->m);
-  const multi_args_t mu = {nrhs, ldrhs, ldsol, sys_hist, sys_normb};
+  const multi_args_t mu = {nrhs, ldrhs, ldsol, sys_hist, sys_normb, NULL, 0, NULL};
+  ++g_own_loop;
+  int rc = ecg_solve_loop(ecg, (double*)rhs, sol, res_hist, bs_hist, max_hist, n_hist, &mu);
+  leave_own_loop();
+  return rc;
+}
+/* The same around preAlps_ECGInitializeGuess; x0 = NULL: preAlps_ECGSolveMulti (sys_res0 then receives ||b_j||).
+ * A guess under which every system already meets its threshold comes back as the solution, with no iteration. */
+int preAlps_ECGSolveGuess(preAlps_ECG_t* ecg, int nrhs, const double* rhs, int ldrhs, const double* x0, int ldx0,
+                          double* sol, int ldsol, double* res_hist, int* bs_hist, double* sys_hist, double* sys_normb,
+                          double* sys_res0, int max_hist, int* n_hist) {
+  const pa_operator_info_t* op = pa_operator_info();
+  if (nrhs < 1) return PA_FAIL("nrhs = %d: at least one right-hand side is needed", nrhs);
+  if (sol && op && ldsol < op->m) return PA_FAIL("ldsol = %d is smaller than the %d local rows", ldsol, op->m);
+  const multi_args_t mu = {nrhs, ldrhs, ldsol, sys_hist, sys_normb, x0, ldx0, sys_res0};
   ++g_own_loop;
   int rc = ecg_solve_loop(ecg, (double*)rhs, sol, res_hist, bs_hist, max_hist, n_hist, &mu);
   leave_own_loop();
@@ -1344,9 +1434,31 @@ static void record_hist(preAlps_ECG_t* ecg, const multi_args_t* mu, double* res_
 static int ecg_solve_loop(preAlps_ECG_t* ecg, double* rhs, double* sol, double* res_hist, int* bs_hist,
                           int max_hist, int* n_hist, const multi_args_t* mu) {
   int rci = 0, stop = 0, nh = 0;
-  if (mu->nrhs > 0) {
+  if (mu->nrhs > 0 && mu->x0) {
+    double g0[16], nb[16];
+    int live = 0;
+    if (preAlps_ECGInitializeGuess(ecg, mu->nrhs, rhs, mu->ldrhs, mu->x0, mu->ldx0, &rci)) return 1;
+    if (preAlps_ECGSystemResiduals(ecg, g0, nb)) return 1;
+    for (int j = 0; j < mu->nrhs; ++j) {
+      if (mu->sys_normb) mu->sys_normb[j] = nb[j];
+      if (mu->sys_res0) mu->sys_res0[j] = g0[j];
+      if (g0[j] > nb[j] * ecg->tol) live = 1;
+    }
+    if (!live) {
+      /* every system meets its threshold as it stands: x0 is the answer, bit for bit, and nothing is queued */
+      if (n_hist) *n_hist = 0;
+      if (sol) {
+        const size_t m = (size_t)ecg->locPbSize;
+        for (int j = 0; j < mu->nrhs; ++j)
+          memcpy(sol + (size_t)j * mu->ldsol, mu->x0 + (size_t)j * mu->ldx0, m * sizeof(double));
+        _preAlps_ECGFree(ecg);
+      }
+      return 0;
+    }
+  } else if (mu->nrhs > 0) {
     if (preAlps_ECGInitializeMulti(ecg, mu->nrhs, rhs, mu->ldrhs, &rci)) return 1;
     if (mu->sys_normb && preAlps_ECGSystemResiduals(ecg, NULL, mu->sys_normb)) return 1;
+    if (mu->sys_res0 && preAlps_ECGSystemResiduals(ecg, NULL, mu->sys_res0)) return 1;   /* (a cold start: ||b_j||) */
   } else if (preAlps_ECGInitialize(ecg, rhs, &rci)) return 1;
   if (preAlps_BlockJacobiApply(ecg->R, ecg->P)) return 1;
   ecg_priv_t* pvg = priv_of(ecg);
@@ -1422,6 +1534,9 @@ static int ecg_advance_loop(preAlps_ECG_t* ecg, double* rhs, int* rci_request, i
 int preAlps_ECGAdvance(preAlps_ECG_t* ecg, double* rhs, int* rci_request, int nsteps, int* restarts,
                        int* last_iters, double* last_res) {
   ecg_priv_t* pvm = priv_of(ecg);
+  if (pvm && pvm->guess)
+    return PA_FAIL("the solver was started from an initial guess: a restart from the right-hand side alone would drop "
+                   "x0 (use preAlps_ECGSolveGuess or the caller's own loop, or _preAlps_ECGReset for a cold start)");
   if (pvm && pvm->nrhs > 1)
     return PA_FAIL("the solver holds %d systems: restarts from one right-hand side are not defined for it "
                    "(use preAlps_ECGSolveMulti or the caller's own loop)", pvm->nrhs);

@@ -1766,6 +1766,76 @@ __global__ __launch_bounds__(WG) void k_multi_start(int m, int k, int s, const d
   block_sum_cols<TS>(acc, sums + (size_t)blockIdx.x * TS);
 }
 
+// ---- a start from an initial guess (preAlps_ECGInitializeGuess) ----
+// X0 as a panel, by the placement rule of k_multi_start: X(row, j*s + pcol[row]) = X0(row, j), zero elsewhere, so the
+// sum of the columns of system j is X0(row, j) itself.
+template <int TS>
+__global__ __launch_bounds__(WG) void k_guess_split(int m, int k, int s, const double* __restrict__ X0, size_t ld,
+                                                    const int* __restrict__ pcol, double* __restrict__ X) {
+  const int nc = k * s;
+  const size_t stride = (size_t)gridDim.x * WG;
+  for (size_t row = (size_t)blockIdx.x * WG + threadIdx.x; row < (size_t)m; row += stride) {
+    const int pc = pcol[row];
+    double x[TS];
+#pragma unroll
+    for (int c = 0; c < TS; ++c) {
+      const int j = c / s;
+      x[c] = (c < nc && c - j * s == pc) ? X0[row + (size_t)j * ld] : 0.0;
+    }
+    store_row<TS>(X, row, x);
+  }
+}
+
+// R0 from the product AX = A X0 of that panel: r0_j = B(row, j) - (the sum of the columns of system j of AX, added in
+// ascending order), split by the same rule.  Each workgroup leaves the sums of B(:, j)^2 over its rows in
+// bsums[blk*TS + j] (the accumulation and the layout of k_multi_start, so the same bits) and the sums of R0(:, c)^2 in
+// rsums[blk*TS + c] (the layout of k_colnorm2), both for k_group_norms.
+template <int TS>
+__global__ __launch_bounds__(WG) void k_guess_start(int m, int k, int s, const double* __restrict__ B, size_t ldb,
+                                                    const int* __restrict__ pcol, const double* __restrict__ AX,
+                                                    double* __restrict__ R, double* __restrict__ bsums,
+                                                    double* __restrict__ rsums) {
+  double accb[TS], accr[TS];
+#pragma unroll
+  for (int j = 0; j < TS; ++j) { accb[j] = 0.0; accr[j] = 0.0; }
+  const int nc = k * s;
+  const size_t stride = (size_t)gridDim.x * WG;
+  for (size_t row = (size_t)blockIdx.x * WG + threadIdx.x; row < (size_t)m; row += stride) {
+    const int pc = pcol[row];
+    double g[TS], r[TS];
+    load_row<TS>(AX, row, g);
+    // g[c] <- the sum of its system's columns: a running sum up to the last column of each system ...
+    double run = 0.0;
+    int cnt = 0;
+#pragma unroll
+    for (int c = 0; c < TS; ++c)
+      if (c < nc) {
+        run += g[c];
+        g[c] = run;
+        if (++cnt == s) { run = 0.0; cnt = 0; }
+      }
+    // ... handed down to the columns before it
+    double sum = 0.0;
+    cnt = 0;
+#pragma unroll
+    for (int c = TS - 1; c >= 0; --c)
+      if (c < nc) {
+        if (cnt == 0) sum = g[c];
+        if (++cnt == s) cnt = 0;
+        const int j = c / s;
+        r[c] = (c - j * s == pc) ? B[row + (size_t)j * ldb] - sum : 0.0;
+        accr[c] = fma(r[c], r[c], accr[c]);
+      } else r[c] = 0.0;
+    store_row<TS>(R, row, r);
+#pragma unroll
+    for (int j = 0; j < TS; ++j)
+      if (j < k) { const double v = B[row + (size_t)j * ldb]; accb[j] = fma(v, v, accb[j]); }
+  }
+  block_sum_cols<TS>(accb, bsums + (size_t)blockIdx.x * TS);
+  __syncthreads();      // (block_sum_cols keeps one LDS buffer: its readers are done before the second pass writes)
+  block_sum_cols<TS>(accr, rsums + (size_t)blockIdx.x * TS);
+}
+
 // The per-system sums of the stopping test: out[j] = sum over the s columns of system j (ascending) of the sum over
 // the blocks of rtr[blk*ts + c] (the column sums of R^2 an update kernel or k_colnorm2 left).  One workgroup; 16
 // threads per column take the blocks b = l, l + 16, ... in turn and are folded by a fixed tree, so the k values are
@@ -2180,6 +2250,24 @@ int pa_k_multi_start(int m, int ts, int k, int s, const double* B, int ldb, cons
   TS_DISPATCH(ts, PA_LAUNCH((k_multi_start<TS_>), dim3(blocks), dim3(WG), 0, cur_stream(), m, k, s, B, (size_t)ldb,
                             pcol, R, sums));
   return kfail("k_multi_start");
+}
+
+int pa_k_guess_split(int m, int ts, int k, int s, const double* X0, int ld, const int* pcol, double* X) {
+  if (multi_args_bad("pa_k_guess_split", ts, k, s)) return 1;
+  TS_DISPATCH(ts, PA_LAUNCH((k_guess_split<TS_>), dim3(grid_rows(m, 2)), dim3(WG), 0, cur_stream(), m, k, s, X0,
+                            (size_t)ld, pcol, X));
+  return kfail("k_guess_split");
+}
+
+int pa_k_guess_start(int m, int ts, int k, int s, const double* B, int ldb, const int* pcol, const double* AX,
+                     double* R, double* bsums, double* rsums, int* nblk) {
+  if (multi_args_bad("pa_k_guess_start", ts, k, s)) return 1;
+  int blocks = grid_rows(m, 4);      // (the grid of pa_k_multi_start: the same partial sums of B^2)
+  if (blocks > GRAM_MAX_BLOCKS) blocks = GRAM_MAX_BLOCKS;
+  *nblk = blocks;
+  TS_DISPATCH(ts, PA_LAUNCH((k_guess_start<TS_>), dim3(blocks), dim3(WG), 0, cur_stream(), m, k, s, B, (size_t)ldb,
+                            pcol, AX, R, bsums, rsums));
+  return kfail("k_guess_start");
 }
 
 int pa_k_group_norms(const double* rtr_partials, int nblk, int ts, int k, int s, double* out, double* host) {

@@ -226,6 +226,14 @@ int pa_k_rowsum(int m, int ts, int nc, const double* X, double* sol);
  * sum B(:, j)^2 (*nblk blocks, the layout of pa_k_colnorm2).  B: device, column major, ldb >= m; pcol: m ints. */
 int pa_k_multi_start(int m, int ts, int k, int s, const double* B, int ldb, const int* pcol, double* R,
                      double* sums, int* nblk);
+/* A start from an initial guess: X (m x ts) with X0(row, j) in column j*s + pcol[row], zero elsewhere.  X0: device,
+ * column major, ld >= m. */
+int pa_k_guess_split(int m, int ts, int k, int s, const double* X0, int ld, const int* pcol, double* X);
+/* ... and R0 from AX = A X of that panel: B(row, j) - (the sum of the columns of system j of AX, ascending) in column
+ * j*s + pcol[row], zero elsewhere.  bsums[blk*ts + j]: the block's share of sum B(:, j)^2, grid and order of
+ * pa_k_multi_start; rsums[blk*ts + c]: its share of sum R0(:, c)^2, the layout of pa_k_colnorm2 (*nblk blocks each). */
+int pa_k_guess_start(int m, int ts, int k, int s, const double* B, int ldb, const int* pcol, const double* AX,
+                     double* R, double* bsums, double* rsums, int* nblk);
 /* out[j] = sum over the columns of system j (ascending) of the sum over the blocks of rtr_partials[blk*ts + c],
  * one workgroup, fixed order; host (pinned, device-visible, may be NULL) receives the same k values. */
 int pa_k_group_norms(const double* rtr_partials, int nblk, int ts, int k, int s, double* out, double* host);

@@ -81,6 +81,7 @@ EXPORTS = [
     "preAlps_hip_nd_selfcheck", "preAlps_hip_loopback", "preAlps_hip_graphs", "preAlps_hip_ecg_solve_first",
     "preAlps_hip_set_nd_precision", "preAlps_hip_set_band_precision",
     "preAlps_ECGInitializeMulti", "preAlps_ECGSystemResiduals", "preAlps_ECGFinalizeMulti", "preAlps_ECGSolveMulti",
+    "preAlps_ECGInitializeGuess", "preAlps_ECGSolveGuess",
 ]
 
 _lib = None
@@ -118,6 +119,9 @@ def load():
     L.preAlps_ECGSystemResiduals.argtypes = [pe, pd, pd]
     L.preAlps_ECGFinalizeMulti.argtypes = [pe, pd, C.c_int]
     L.preAlps_ECGSolveMulti.argtypes = [pe, C.c_int, pd, C.c_int, pd, C.c_int, pd, pi, pd, pd, C.c_int, pi]
+    L.preAlps_ECGInitializeGuess.argtypes = [pe, C.c_int, pd, C.c_int, pd, C.c_int, pi]
+    L.preAlps_ECGSolveGuess.argtypes = [pe, C.c_int, pd, C.c_int, pd, C.c_int, pd, C.c_int, pd, pi, pd, pd, pd,
+                                        C.c_int, pi]
     L._preAlps_ECGReset.argtypes = [pe, pd, pi]
     L.preAlps_BlockOperator.argtypes = [_PD, _PD]
     L.preAlps_BlockJacobiApply.argtypes = [_PD, _PD]

@@ -36,6 +36,8 @@ class EcgResult:
     sys_res: np.ndarray = None
     sys_normb: np.ndarray = None
     sys_hist: np.ndarray = None
+    # a solve from an initial guess (x0= / X0=): the residual norm every system starts from
+    sys_res0: np.ndarray = None
 
 
 class DistributedHooks:
@@ -320,8 +322,23 @@ class EcgProblem:
         e.ortho_alg, e.bs_red = ortho_alg, bs_red
         return e
 
-    def solve(self, rhs, t, ortho_alg=ORTHODIR, bs_red=NO_BS_RED, tol=1e-5, max_iter=1000):
-        """preAlps_ECGSolve = the reference driver loop, in C."""
+    def solve(self, rhs, t, ortho_alg=ORTHODIR, bs_red=NO_BS_RED, tol=1e-5, max_iter=1000, x0=None):
+        """preAlps_ECGSolve = the reference driver loop, in C.  x0 (m values): start the iteration from it
+        (preAlps_ECGSolveGuess with one system) instead of from zero; the result then carries sys_res0, the norm of
+        the split of b - A x0, and iters = 0 with x = x0 if that already meets tol * ||b||."""
+        if x0 is not None:
+            xs = np.shape(x0)
+            if len(xs) != 1:
+                raise ValueError("x0 must be one-dimensional (m values), not of shape %r" % (xs,))
+            if xs[0] != self.m:
+                raise ValueError("x0 has %d rows, the operator has %d local rows" % (xs[0], self.m))
+            bshape = np.shape(rhs)
+            if len(bshape) != 1 or bshape[0] != self.m:
+                raise ValueError("rhs must hold the %d local rows, not be of shape %r" % (self.m, bshape))
+            got = self.solve_multi(np.asarray(rhs, dtype=np.float64)[:, None], t, ortho_alg, bs_red, tol, max_iter,
+                                   X0=np.asarray(x0, dtype=np.float64)[:, None])
+            got.x = np.ascontiguousarray(got.x[:, 0])
+            return got
         if not self.has_precond:
             self.create_block_jacobi()
         import time
@@ -342,12 +359,15 @@ class EcgProblem:
         return EcgResult(x=sol, iters=e.iter, res=res[:nh.value].copy(), bs=bs[:nh.value].copy(),
                          final_res=e.res, final_bs=e.bs, normb=e.normb, seconds=dt, timers=timers)
 
-    def solve_multi(self, B, t, ortho_alg=ORTHODIR, bs_red=NO_BS_RED, tol=1e-5, max_iter=1000):
+    def solve_multi(self, B, t, ortho_alg=ORTHODIR, bs_red=NO_BS_RED, tol=1e-5, max_iter=1000, X0=None):
         """preAlps_ECGSolveMulti: the k columns of B (m x k) as k systems solved by one block iteration of
         enlarging factor t, a multiple of k; system j owns the columns j*t/k .. (j+1)*t/k - 1 of the panels.
         Returns an EcgResult with x of shape (m, k), res / bs as solve() (the Frobenius norm of all of R) and
         sys_res, sys_normb (k values) and sys_hist (iterations x k): the per-system residual norms the
-        stopping test uses.  ||b_j - A x_j|| <= sqrt(t / k) * sys_res[j] in exact arithmetic."""
+        stopping test uses.  ||b_j - A x_j|| <= sqrt(t / k) * sys_res[j] in exact arithmetic.
+        X0 (m x k): a starting value for every system (preAlps_ECGSolveGuess); sys_res0 then holds the k residual
+        norms the iteration starts from, and a guess that already meets every threshold comes back as x after no
+        iteration.  X0 = None is preAlps_ECGSolveMulti as before."""
         Bs = np.shape(B)
         if len(Bs) != 2:
             raise ValueError("B must be two-dimensional (m x k), not of shape %r" % (Bs,))
@@ -356,6 +376,14 @@ class EcgProblem:
         k = int(Bs[1])
         if k < 1 or int(t) % k != 0:
             raise ValueError("the enlarging factor t = %d is not a multiple of the %d right-hand sides" % (t, k))
+        if X0 is not None:
+            Xs = np.shape(X0)
+            if len(Xs) != 2:
+                raise ValueError("X0 must be two-dimensional (m x k), not of shape %r" % (Xs,))
+            if Xs[0] != self.m:
+                raise ValueError("X0 has %d rows, the operator has %d local rows" % (Xs[0], self.m))
+            if Xs[1] != k:
+                raise ValueError("X0 has %d columns, B has %d right-hand sides" % (Xs[1], k))
         if not self.has_precond:
             self.create_block_jacobi()
         import time
@@ -372,17 +400,28 @@ class EcgProblem:
         sys_normb = np.zeros(k)
         sys_res = np.zeros(k)
         nh = C.c_int()
+        sys_res0 = None
+        if X0 is not None:
+            X0 = np.asfortranarray(X0, dtype=np.float64)
+            sys_res0 = np.zeros(k)
         t0 = time.perf_counter()
-        check(L.preAlps_ECGSolveMulti(C.byref(e), k, _pd(B), ld, _pd(sol), ld, _pd(res), _pi(bs), _pd(sys_hist),
-                                      _pd(sys_normb), cap, C.byref(nh)), "preAlps_ECGSolveMulti")
+        if X0 is None:
+            check(L.preAlps_ECGSolveMulti(C.byref(e), k, _pd(B), ld, _pd(sol), ld, _pd(res), _pi(bs), _pd(sys_hist),
+                                          _pd(sys_normb), cap, C.byref(nh)), "preAlps_ECGSolveMulti")
+        else:
+            check(L.preAlps_ECGSolveGuess(C.byref(e), k, _pd(B), ld, _pd(X0), ld, _pd(sol), ld, _pd(res), _pi(bs),
+                                          _pd(sys_hist), _pd(sys_normb), _pd(sys_res0), cap, C.byref(nh)),
+                  "preAlps_ECGSolveGuess")
         dt = time.perf_counter() - t0
         n = nh.value
         if n:
             sys_res = sys_hist[n - 1].copy()
+        elif sys_res0 is not None:
+            sys_res = sys_res0.copy()
         timers = {k_: getattr(e, k_) for k_ in ("tot_t", "comm_t", "trsm_t", "gemm_t", "potrf_t", "copy_t")}
         return EcgResult(x=sol, iters=e.iter, res=res[:n].copy(), bs=bs[:n].copy(), final_res=e.res,
                          final_bs=e.bs, normb=e.normb, seconds=dt, timers=timers, sys_res=sys_res,
-                         sys_normb=sys_normb, sys_hist=np.ascontiguousarray(sys_hist[:n]))
+                         sys_normb=sys_normb, sys_hist=np.ascontiguousarray(sys_hist[:n]), sys_res0=sys_res0)
 
     # -- single operations, for tests and micro-benchmarks -----------------------
     def panel(self, ncols, t):
