@@ -29,18 +29,15 @@
 #include <strings.h>
 
 #include "pa_host.h"
+#include "spmm_plan.h"
 
 typedef struct {
   pa_operator_info_t info;
-  /* device matrix: SELL-64 slices with local column ids */
-  long long* d_sl_off; int* d_sl_len; int* d_sl_row0; int* d_sl_nrows;
-  int* d_col; double* d_val;
   int lnnz;
-  double sell_entries;   /* stored entries including padding */
-  /* SpMM plan */
+  /* SpMM plan: SELL-64 slices with local column ids + workgroup blocks (spmm_plan.h) */
   pa_spmm_plan_t plan;
-  int* d_blk_slice; int* d_blk_win; int* d_order;
-  unsigned short* d_col16; int* d_blk_ext_off; int* d_ext_rows; int* d_blk_nlow;
+  void* d_plan[PA_PL_COUNT];   /* the device arrays `plan` points into */
+  double sell_entries;   /* stored entries including padding */
   int* lcol;             /* host: local column ids of the panel (own rows < m <= halo slots) */
   int plan_ts;           /* panel stride the current SpMM plan was cut for (0: none) */
   double stream_bytes;   /* bytes of matrix data one SpMM streams */
@@ -70,27 +67,7 @@ static double g_setup_build_s, g_setup_plan_s;   /* host seconds: scale/permute/
 const pa_operator_info_t* pa_operator_info(void) { return g_op.info.built ? &g_op.info : NULL; }
 
 /* ------------------------------------------------------------------ utils */
-/* Large host arrays (hundreds of MB, written once): 2 MiB alignment + a transparent-huge-page
- * hint, so that filling them is not dominated by 4 KiB page faults.  Release with free(). */
-static void* big_alloc(size_t bytes) {
-  void* p = NULL;
-  if (bytes < ((size_t)8 << 20)) return malloc(bytes ? bytes : 1);
-  if (posix_memalign(&p, (size_t)2 << 20, bytes)) return NULL;
-  (void)madvise(p, bytes, MADV_HUGEPAGE);
-  return p;
-}
-
-/* Rows per SpMM workgroup.  The measured optimum on a full GPU is 256 (192 at 8 columns); a process that
- * owns few rows (one shard of a multi-GPU run: 130 k rows are 519 such blocks on 256 CUs) gets smaller
- * blocks, so that every CU has at least four workgroups to hide the staging and streaming latencies. */
-static int env_int(const char* name, int dflt);
-static size_t g_dbg_val_bytes, g_dbg_slot_bytes;
-static int spmm_block_rows(int m, int dflt) {
-  int cus = pa_rt_num_cus() > 0 ? pa_rt_num_cus() : 256;
-  int rows = dflt;
-  while (rows > 64 && (long long)m / rows < 4LL * cus) rows -= 64;
-  return rows;
-}
+static size_t g_dbg_val_bytes, g_dbg_slot_bytes;   /* device bytes of the run plan's values / slots */
 
 static int env_int(const char* name, int dflt) {
   const char* s = getenv(name);
@@ -122,13 +99,7 @@ static int part_of_row(const int* rowPos, int nparts, int row) {
 
 /* --------------------------------------------------------------- free ---- */
 static void free_plan(pa_operator_t* o) {
-  pa_rt_free(o->d_sl_off); pa_rt_free(o->d_sl_len); pa_rt_free(o->d_sl_row0); pa_rt_free(o->d_sl_nrows);
-  pa_rt_free(o->d_col); pa_rt_free(o->d_val);
-  pa_rt_free(o->d_blk_slice); pa_rt_free(o->d_blk_win); pa_rt_free(o->d_order);
-  pa_rt_free(o->d_col16); pa_rt_free(o->d_blk_ext_off); pa_rt_free(o->d_ext_rows); pa_rt_free(o->d_blk_nlow);
-  o->d_blk_nlow = NULL;
-  o->d_sl_off = NULL; o->d_sl_len = o->d_sl_row0 = o->d_sl_nrows = o->d_col = NULL; o->d_val = NULL;
-  o->d_blk_slice = o->d_blk_win = o->d_order = NULL; o->d_col16 = NULL; o->d_blk_ext_off = o->d_ext_rows = NULL;
+  for (int i = 0; i < PA_PL_COUNT; ++i) { pa_rt_free(o->d_plan[i]); o->d_plan[i] = NULL; }
   memset(&o->plan, 0, sizeof(o->plan));
   o->plan_ts = 0;
 }
@@ -149,307 +120,54 @@ void preAlps_OperatorFree(void) {
 }
 
 /* ------------------------------------------------------------ the plan ---- */
-/* Local CSR (local column ids) -> SELL-64 slices + workgroup blocks.  A block
- * is a run of slices of one subdomain (at most spmm_block_rows() rows);
- * its LDS window is the subdomain's own row range, or the 256 rows around the
- * block when the subdomain is larger than that (1024-row windows measured slower). */
-static int build_plan_staged(pa_operator_t* o, int ts);
-static int build_plan_runs(pa_operator_t* o, int ts);
+/* The plan is cut on the host (spmm_plan.c); here it goes to the device: every array of the host
+ * plan into a device array of its own, owned by o->d_plan[], and the pointers into o->plan. */
+static int upload_plan(pa_operator_t* o, const pa_spmm_host_plan_t* hp) {
+  for (int i = 0; i < PA_PL_COUNT; ++i) {
+    const pa_plan_array_t* a = &hp->a[i];
+    if (!a->p) continue;
+    o->d_plan[i] = pa_rt_malloc(a->n_alloc * a->elem);
+    if (!o->d_plan[i] || pa_rt_h2d(o->d_plan[i], a->p, a->n * a->elem)) return 1;
+  }
+  pa_spmm_plan_t* pl = &o->plan;
+  pl->m = hp->m; pl->nslices = hp->nslices; pl->nblk = hp->nblk; pl->n_interior = hp->n_interior;
+  pl->win_cap = hp->win_cap; pl->staged = hp->staged; pl->stage_cap = hp->stage_cap;
+  pl->runs = hp->runs; pl->runs_cols = hp->runs_cols;
+  pl->sl_off = o->d_plan[PA_PL_SL_OFF]; pl->sl_len = o->d_plan[PA_PL_SL_LEN];
+  pl->sl_row0 = o->d_plan[PA_PL_SL_ROW0]; pl->sl_nrows = o->d_plan[PA_PL_SL_NROWS];
+  pl->col = o->d_plan[PA_PL_COL]; pl->col16 = o->d_plan[PA_PL_COL16]; pl->val = o->d_plan[PA_PL_VAL];
+  pl->blk_slice = o->d_plan[PA_PL_BLK_SLICE]; pl->blk_win = o->d_plan[PA_PL_BLK_WIN];
+  pl->blk_ext_off = o->d_plan[PA_PL_BLK_EXT_OFF]; pl->blk_nlow = o->d_plan[PA_PL_BLK_NLOW];
+  pl->ext_rows = o->d_plan[PA_PL_EXT_ROWS]; pl->order = o->d_plan[PA_PL_ORDER];
+  o->sell_entries = hp->sell_entries;
+  o->stream_bytes = hp->stream_bytes;
+  if (hp->runs) {   /* what preAlps_hip_debug_move_plan copies */
+    g_dbg_val_bytes = hp->a[PA_PL_VAL].n_alloc * hp->a[PA_PL_VAL].elem;
+    g_dbg_slot_bytes = hp->a[PA_PL_COL16].n_alloc * hp->a[PA_PL_COL16].elem;
+  }
+  return 0;
+}
 
+/* The switches are read at every build: tests and probes change them between builds in one process. */
 static int build_plan(pa_operator_t* o, int ts) {
   const pa_operator_info_t* in = &o->info;
-  const int* rowptr = in->A.rowPtr;
-  const int* colind = o->lcol;
-  const double* val = in->A.val;
-  int m = in->m;
   free_plan(o);
-  /* -1 (default): stage when the external rows a block copies are small next to its matrix
-   * slice (long rows: elasticity); short rows (7-point stencils) gather through L2 instead */
-  int want = env_int("PREALPS_SPMM_STAGED", -1);
-  if (want != 0 && env_int("PREALPS_SPMM_RUNS", 1)) {
-    /* rows whose nonzeros come in runs of consecutive columns (vector problems: 3 dofs per
-     * node) share one LDS slot per run of three: 8.67 B per nonzero instead of 10 */
-    int rc = build_plan_runs(o, ts);
-    if (rc < 0) return 1;
-    if (rc == 0) { o->plan_ts = ts; return 0; }
-    free_plan(o);
-  }
-  if (want < 0 && ts >= 16) want = 0; /* wide panels: the 128-B X rows gather well from L2 (measured) */
-  if (want != 0) {
-    int rc = build_plan_staged(o, ts);
-    if (rc < 0) return 1;
-    if (rc == 0) {
-      double ext_bytes = (o->stream_bytes - 10.0 * o->sell_entries) / 4.0 * ts * 8.0;
-      /* round 4: at up to 4 columns the staged kernel (batched staging, its Gram block in the epilogue) is worth
-       * it up to external rows of half the matrix slice: 7-point Poisson 100^3 (38 %) 226.6 -> 221.6 us per
-       * iteration against the window kernel, although the plain product alone is 3 us slower
-       * (tools/probe/r4_poisson_plan_ab.py); wider panels keep the quarter */
-      const double thr = ts <= 4 ? 0.5 : 0.25;
-      if (want > 0 || ext_bytes < thr * 10.0 * o->sell_entries) { o->plan_ts = ts; return 0; }
-    }
-    free_plan(o); /* too many rows to stage, or not worth it: use the general kernel */
-  }
-  int win_cap = 256;
-  int blk_rows = spmm_block_rows(m, 256);
-  if (blk_rows < 64) blk_rows = 64;
-  blk_rows &= ~63;
-  int nslices = 0;
-  for (int p = in->part0; p < in->part1; ++p) nslices += (in->rowPos[p + 1] - in->rowPos[p] + 63) / 64;
-  long long* sl_off = (long long*)malloc(((size_t)nslices + 1) * sizeof(long long));
-  int* sl_len = (int*)malloc((nslices ? nslices : 1) * sizeof(int));
-  int* sl_row0 = (int*)malloc((nslices ? nslices : 1) * sizeof(int));
-  int* sl_nrows = (int*)malloc((nslices ? nslices : 1) * sizeof(int));
-  int* sl_part = (int*)malloc((nslices ? nslices : 1) * sizeof(int));
-  int s = 0;
-  sl_off[0] = 0;
-  for (int p = in->part0; p < in->part1; ++p) {
-    int pr0 = in->rowPos[p] - in->row_off, pr1 = in->rowPos[p + 1] - in->row_off;
-    for (int r = pr0; r < pr1; r += 64, ++s) {
-      int nr = pr1 - r < 64 ? pr1 - r : 64, len = 0;
-      for (int i = 0; i < nr; ++i) { int l = rowptr[r + i + 1] - rowptr[r + i]; if (l > len) len = l; }
-      sl_len[s] = len; sl_row0[s] = r; sl_nrows[s] = nr; sl_part[s] = p;
-      sl_off[s + 1] = sl_off[s] + (long long)len * 64;
-    }
-  }
-  size_t tot = (size_t)sl_off[nslices];
-  o->sell_entries = (double)tot;
-  int* scol = (int*)malloc((tot + 64) * sizeof(int));
-  double* sval = (double*)calloc(tot + 64, sizeof(double));
-  if (!scol || !sval) return PA_FAIL("out of host memory for %zu SELL entries", tot);
-  for (int q = 0; q < nslices; ++q) {
-    int r = sl_row0[q], nr = sl_nrows[q], len = sl_len[q];
-    int* c = scol + sl_off[q];
-    double* v = sval + sl_off[q];
-    for (int i = 0; i < 64; ++i) {
-      int row = i < nr ? r + i : r;          /* unused lanes mirror the first row */
-      int l = i < nr ? rowptr[row + 1] - rowptr[row] : 0;
-      for (int k = 0; k < len; ++k) {
-        if (k < l) { c[(size_t)k * 64 + i] = colind[rowptr[row] + k]; v[(size_t)k * 64 + i] = val[rowptr[row] + k]; }
-        else { c[(size_t)k * 64 + i] = row; v[(size_t)k * 64 + i] = 0.0; } /* padding: 0 * x[row] */
-      }
-    }
-  }
-  for (size_t k = tot; k < tot + 64; ++k) scol[k] = 0;
-  /* blocks */
-  int cap_blocks = nslices > 0 ? nslices : 1, nblk = 0;
-  int* blk_slice = (int*)malloc(((size_t)cap_blocks + 1) * sizeof(int));
-  int* blk_win = (int*)malloc((size_t)2 * cap_blocks * sizeof(int));
-  char* needs_halo = (char*)malloc(cap_blocks);
-  int q = 0, max_win = 0;
-  while (q < nslices) {
-    int p = sl_part[q], q1 = q, rows = 0;
-    while (q1 < nslices && sl_part[q1] == p && rows + 64 <= blk_rows) { rows += 64; ++q1; }
-    int pr0 = in->rowPos[p] - in->row_off, pr1 = in->rowPos[p + 1] - in->row_off;
-    int r0 = sl_row0[q], r1 = sl_row0[q1 - 1] + sl_nrows[q1 - 1];
-    int w0, w1;
-    if (win_cap <= 0) { w0 = w1 = r0; }
-    else if (pr1 - pr0 <= win_cap) { w0 = pr0; w1 = pr1; }
-    else {
-      int c = (r0 + r1) / 2;
-      w0 = c - win_cap / 2;
-      if (w0 < pr0) w0 = pr0;
-      w1 = w0 + win_cap;
-      if (w1 > pr1) { w1 = pr1; w0 = w1 - win_cap; }
-    }
-    if (w1 - w0 > max_win) max_win = w1 - w0;
-    char h = 0;
-    for (int k = rowptr[r0]; k < rowptr[r1] && !h; ++k) h = colind[k] >= m;
-    blk_slice[nblk] = q; blk_win[2 * nblk] = w0; blk_win[2 * nblk + 1] = w1; needs_halo[nblk] = h;
-    ++nblk;
-    q = q1;
-  }
-  blk_slice[nblk] = nslices;
-  int* order = (int*)malloc((nblk > 0 ? nblk : 1) * sizeof(int));
-  int ni = 0;
-  for (int b = 0; b < nblk; ++b) if (!needs_halo[b]) order[ni++] = b;
-  int k2 = ni;
-  for (int b = 0; b < nblk; ++b) if (needs_halo[b]) order[k2++] = b;
-  o->d_sl_off = (long long*)pa_rt_malloc(((size_t)nslices + 1) * sizeof(long long));
-  o->d_sl_len = (int*)pa_rt_malloc((nslices ? nslices : 1) * sizeof(int));
-  o->d_sl_row0 = (int*)pa_rt_malloc((nslices ? nslices : 1) * sizeof(int));
-  o->d_sl_nrows = (int*)pa_rt_malloc((nslices ? nslices : 1) * sizeof(int));
-  o->d_col = (int*)pa_rt_malloc((tot + 64) * sizeof(int));
-  o->d_val = (double*)pa_rt_malloc((tot + 64) * sizeof(double));
-  o->d_blk_slice = (int*)pa_rt_malloc(((size_t)nblk + 1) * sizeof(int));
-  o->d_blk_win = (int*)pa_rt_malloc((size_t)2 * (nblk > 0 ? nblk : 1) * sizeof(int));
-  o->d_order = (int*)pa_rt_malloc((nblk > 0 ? nblk : 1) * sizeof(int));
-  int rc = (!o->d_sl_off || !o->d_sl_len || !o->d_sl_row0 || !o->d_sl_nrows || !o->d_col || !o->d_val ||
-            !o->d_blk_slice || !o->d_blk_win || !o->d_order);
-  rc = rc || pa_rt_h2d(o->d_sl_off, sl_off, ((size_t)nslices + 1) * sizeof(long long));
-  rc = rc || pa_rt_h2d(o->d_sl_len, sl_len, nslices * sizeof(int));
-  rc = rc || pa_rt_h2d(o->d_sl_row0, sl_row0, nslices * sizeof(int));
-  rc = rc || pa_rt_h2d(o->d_sl_nrows, sl_nrows, nslices * sizeof(int));
-  rc = rc || pa_rt_h2d(o->d_col, scol, (tot + 64) * sizeof(int));
-  rc = rc || pa_rt_h2d(o->d_val, sval, (tot + 64) * sizeof(double));
-  rc = rc || pa_rt_h2d(o->d_blk_slice, blk_slice, ((size_t)nblk + 1) * sizeof(int));
-  rc = rc || pa_rt_h2d(o->d_blk_win, blk_win, (size_t)2 * nblk * sizeof(int));
-  rc = rc || pa_rt_h2d(o->d_order, order, nblk * sizeof(int));
-  free(sl_off); free(sl_len); free(sl_row0); free(sl_nrows); free(sl_part); free(scol); free(sval);
-  free(blk_slice); free(blk_win); free(needs_halo); free(order);
+  pa_spmm_plan_in_t pin = {
+    .m = in->m, .halo = in->halo, .part0 = in->part0, .part1 = in->part1, .row_off = in->row_off,
+    .rowPos = in->rowPos, .rowPtr = in->A.rowPtr, .lcol = o->lcol, .val = in->A.val,
+    .ts = ts, .cus = pa_rt_num_cus(),
+    .want_staged = env_int("PREALPS_SPMM_STAGED", -1), .want_runs = env_int("PREALPS_SPMM_RUNS", 1)};
+  pa_spmm_host_plan_t hp;
+  if (pa_spmm_plan_build(&pin, &hp))
+    return hp.oom_entries ? PA_FAIL("out of host memory for %zu SELL entries", hp.oom_entries)
+                          : PA_FAIL("out of host memory for the SpMM plan");
+  int rc = upload_plan(o, &hp);
+  pa_spmm_plan_free(&hp);
   if (rc) return PA_FAIL("uploading the SpMM plan failed: %s", pa_rt_error());
-  pa_spmm_plan_t* pl = &o->plan;
-  pl->m = m; pl->nslices = nslices; pl->sl_off = o->d_sl_off; pl->sl_len = o->d_sl_len;
-  pl->sl_row0 = o->d_sl_row0; pl->sl_nrows = o->d_sl_nrows; pl->col = o->d_col; pl->val = o->d_val;
-  pl->nblk = nblk; pl->blk_slice = o->d_blk_slice; pl->blk_win = o->d_blk_win; pl->order = o->d_order;
-  pl->n_interior = ni; pl->win_cap = max_win;
-  o->stream_bytes = 12.0 * (double)tot;
   o->plan_ts = ts;
   return 0;
 }
 
-/* Staged plan for panel stride ts.  Returns 0 on success, -1 on error, 1 when
- * some 64-row slice references more rows than fit the LDS staging area. */
-static int build_plan_staged(pa_operator_t* o, int ts) {
-  const pa_operator_info_t* in = &o->info;
-  const int* rowptr = in->A.rowPtr;
-  const int* colind = o->lcol;
-  const double* val = in->A.val;
-  int m = in->m, ncols = m + in->halo;
-  /* LDS budget of a block: 32 KiB at ts <= 4, 64 KiB at ts = 8 (two workgroups per CU) */
-  int cap_rows = (ts <= 4 ? 32768 : 49152) / (ts * 8);
-  if (cap_rows > 65535) cap_rows = 65535;
-  /* 8-column panels: 192 rows and 48 KiB of staging (three workgroups per CU) measured 7 % faster */
-  int blk_rows = spmm_block_rows(m, ts <= 4 ? 256 : 192);
-  if (blk_rows < 64) blk_rows = 64;
-  blk_rows &= ~63;
-  if (blk_rows > cap_rows) blk_rows = cap_rows & ~63;
-  if (blk_rows < 64) return 1;
-  int nslices = 0;
-  for (int p = in->part0; p < in->part1; ++p) nslices += (in->rowPos[p + 1] - in->rowPos[p] + 63) / 64;
-  long long* sl_off = (long long*)malloc(((size_t)nslices + 1) * sizeof(long long));
-  int* sl_len = (int*)malloc((nslices ? nslices : 1) * sizeof(int));
-  int* sl_row0 = (int*)malloc((nslices ? nslices : 1) * sizeof(int));
-  int* sl_nrows = (int*)malloc((nslices ? nslices : 1) * sizeof(int));
-  int* sl_part = (int*)malloc((nslices ? nslices : 1) * sizeof(int));
-  int s = 0;
-  sl_off[0] = 0;
-  for (int p = in->part0; p < in->part1; ++p) {
-    int pr0 = in->rowPos[p] - in->row_off, pr1 = in->rowPos[p + 1] - in->row_off;
-    for (int r = pr0; r < pr1; r += 64, ++s) {
-      int nr = pr1 - r < 64 ? pr1 - r : 64, len = 0;
-      for (int i = 0; i < nr; ++i) { int l = rowptr[r + i + 1] - rowptr[r + i]; if (l > len) len = l; }
-      sl_len[s] = len; sl_row0[s] = r; sl_nrows[s] = nr; sl_part[s] = p;
-      sl_off[s + 1] = sl_off[s] + (long long)len * 64;
-    }
-  }
-  size_t tot = (size_t)sl_off[nslices];
-  /* blocks: runs of slices of one subdomain; shrink until everything they touch fits */
-  int* blk_slice = (int*)malloc(((size_t)nslices + 1) * sizeof(int));
-  int* blk_ext_off = (int*)malloc(((size_t)nslices + 1) * sizeof(int));
-  char* needs_halo = (char*)malloc(nslices ? nslices : 1);
-  int* stamp = (int*)calloc(ncols ? ncols : 1, sizeof(int));   /* block id + 1 that last saw the column */
-  int* slot_of = (int*)malloc((ncols ? ncols : 1) * sizeof(int));
-  size_t ext_cap = 1024, next_tot = 0;
-  int* ext_rows = (int*)malloc(ext_cap * sizeof(int));
-  unsigned short* c16 = (unsigned short*)malloc((tot + 64) * sizeof(unsigned short));
-  double* sval = (double*)calloc(tot + 64, sizeof(double));
-  int nblk = 0, q = 0, max_stage = 0, overflow = 0, gen = 0;
-  (void)sl_part;
-  if (!c16 || !sval || !stamp || !slot_of) { overflow = -1; }
-  while (q < nslices && !overflow) {
-    /* staged blocks may span consecutive subdomains: fewer external rows per row */
-    int nsl = 0;
-    while (q + nsl < nslices && (nsl + 1) * 64 <= blk_rows) ++nsl;
-    for (;;) {
-      int r0 = sl_row0[q], r1 = sl_row0[q + nsl - 1] + sl_nrows[q + nsl - 1];
-      int nown = r1 - r0, next = 0;
-      size_t mark0 = next_tot;
-      char h = 0;
-      ++gen;
-      for (int k = rowptr[r0]; k < rowptr[r1]; ++k) {
-        int c = colind[k];
-        if (c >= r0 && c < r1) continue;
-        if (stamp[c] != gen) {
-          stamp[c] = gen;
-          if (next_tot == ext_cap) { ext_cap *= 2; ext_rows = (int*)realloc(ext_rows, ext_cap * sizeof(int)); }
-          ext_rows[next_tot++] = c; ++next;
-          if (c >= m) h = 1;
-        }
-      }
-      if (nown + next > cap_rows) {
-        next_tot = mark0;
-        if (nsl == 1) { overflow = 1; break; }
-        nsl = (nsl + 1) / 2;
-        continue;
-      }
-      /* external rows in ascending order (neighbouring rows end up adjacent in LDS and in L2) */
-      int* er = ext_rows + mark0;
-      for (int a = 1; a < next; ++a) { int v = er[a], b2 = a; while (b2 > 0 && er[b2 - 1] > v) { er[b2] = er[b2 - 1]; --b2; } er[b2] = v; }
-      for (int a = 0; a < next; ++a) slot_of[er[a]] = nown + a;
-      for (int sq = q; sq < q + nsl; ++sq) {
-        int r = sl_row0[sq], nr = sl_nrows[sq], len = sl_len[sq];
-        unsigned short* cc = c16 + sl_off[sq];
-        double* vv = sval + sl_off[sq];
-        for (int i = 0; i < 64; ++i) {
-          int row = i < nr ? r + i : r;
-          int l = i < nr ? rowptr[row + 1] - rowptr[row] : 0;
-          for (int k = 0; k < len; ++k) {
-            if (k < l) {
-              int c = colind[rowptr[row] + k];
-              cc[(size_t)k * 64 + i] = (unsigned short)((c >= r0 && c < r1) ? c - r0 : slot_of[c]);
-              vv[(size_t)k * 64 + i] = val[rowptr[row] + k];
-            } else { cc[(size_t)k * 64 + i] = (unsigned short)(row - r0); vv[(size_t)k * 64 + i] = 0.0; }
-          }
-        }
-      }
-      if (nown + next > max_stage) max_stage = nown + next;
-      blk_slice[nblk] = q; blk_ext_off[nblk] = (int)mark0; needs_halo[nblk] = h;
-      ++nblk;
-      q += nsl;
-      break;
-    }
-  }
-  int rc = overflow;
-  if (!rc) {
-    blk_slice[nblk] = nslices; blk_ext_off[nblk] = (int)next_tot;
-    for (size_t k = tot; k < tot + 64; ++k) c16[k] = 0;
-    int* order = (int*)malloc((nblk > 0 ? nblk : 1) * sizeof(int));
-    int ni = 0;
-    for (int b = 0; b < nblk; ++b) if (!needs_halo[b]) order[ni++] = b;
-    int k2 = ni;
-    for (int b = 0; b < nblk; ++b) if (needs_halo[b]) order[k2++] = b;
-    o->d_sl_off = (long long*)pa_rt_malloc(((size_t)nslices + 1) * sizeof(long long));
-    o->d_sl_len = (int*)pa_rt_malloc((nslices ? nslices : 1) * sizeof(int));
-    o->d_sl_row0 = (int*)pa_rt_malloc((nslices ? nslices : 1) * sizeof(int));
-    o->d_sl_nrows = (int*)pa_rt_malloc((nslices ? nslices : 1) * sizeof(int));
-    o->d_col16 = (unsigned short*)pa_rt_malloc((tot + 64) * sizeof(unsigned short));
-    o->d_val = (double*)pa_rt_malloc((tot + 64) * sizeof(double));
-    o->d_blk_slice = (int*)pa_rt_malloc(((size_t)nblk + 1) * sizeof(int));
-    o->d_blk_ext_off = (int*)pa_rt_malloc(((size_t)nblk + 1) * sizeof(int));
-    o->d_ext_rows = (int*)pa_rt_malloc((next_tot + 1) * sizeof(int));   /* one spare entry: k_spmm_runs reads ids unconditionally */
-    o->d_order = (int*)pa_rt_malloc((nblk > 0 ? nblk : 1) * sizeof(int));
-    int bad = (!o->d_sl_off || !o->d_sl_len || !o->d_sl_row0 || !o->d_sl_nrows || !o->d_col16 || !o->d_val ||
-               !o->d_blk_slice || !o->d_blk_ext_off || !o->d_ext_rows || !o->d_order);
-    bad = bad || pa_rt_h2d(o->d_sl_off, sl_off, ((size_t)nslices + 1) * sizeof(long long));
-    bad = bad || pa_rt_h2d(o->d_sl_len, sl_len, nslices * sizeof(int));
-    bad = bad || pa_rt_h2d(o->d_sl_row0, sl_row0, nslices * sizeof(int));
-    bad = bad || pa_rt_h2d(o->d_sl_nrows, sl_nrows, nslices * sizeof(int));
-    bad = bad || pa_rt_h2d(o->d_col16, c16, (tot + 64) * sizeof(unsigned short));
-    bad = bad || pa_rt_h2d(o->d_val, sval, (tot + 64) * sizeof(double));
-    bad = bad || pa_rt_h2d(o->d_blk_slice, blk_slice, ((size_t)nblk + 1) * sizeof(int));
-    bad = bad || pa_rt_h2d(o->d_blk_ext_off, blk_ext_off, ((size_t)nblk + 1) * sizeof(int));
-    bad = bad || pa_rt_h2d(o->d_ext_rows, ext_rows, next_tot * sizeof(int));
-    bad = bad || pa_rt_h2d(o->d_order, order, nblk * sizeof(int));
-    free(order);
-    if (bad) { PA_FAIL("uploading the SpMM plan failed: %s", pa_rt_error()); rc = -1; }
-    else {
-      pa_spmm_plan_t* pl = &o->plan;
-      pl->m = m; pl->nslices = nslices; pl->sl_off = o->d_sl_off; pl->sl_len = o->d_sl_len;
-      pl->sl_row0 = o->d_sl_row0; pl->sl_nrows = o->d_sl_nrows; pl->val = o->d_val;
-      pl->nblk = nblk; pl->blk_slice = o->d_blk_slice; pl->order = o->d_order; pl->n_interior = ni;
-      pl->staged = 1; pl->col16 = o->d_col16; pl->blk_ext_off = o->d_blk_ext_off; pl->ext_rows = o->d_ext_rows;
-      pl->stage_cap = max_stage;
-      o->sell_entries = (double)tot;
-      o->stream_bytes = 10.0 * (double)tot + 4.0 * (double)next_tot;
-    }
-  } else if (rc < 0) {
-    PA_FAIL("out of host memory for the SpMM plan");
-  }
-  free(sl_off); free(sl_len); free(sl_row0); free(sl_nrows); free(sl_part);
-  free(blk_slice); free(blk_ext_off); free(needs_halo); free(stamp); free(slot_of); free(ext_rows);
-  free(c16); free(sval);
-  return rc;
-}
 
 /* -------------------------------------------------------------- build ---- */
 static int g_plan_only = 0;
@@ -551,8 +269,8 @@ static int build_panel(pa_operator_t* o, const int* rp, const int* ci, const dou
   if (lnnz > 2147483000u) return PA_FAIL("local panel has too many nonzeros for int32 indices");
   CPLM_Mat_CSR_t* A = &in->A;
   A->rowPtr = (int*)malloc((size_t)(m + 1) * sizeof(int));
-  A->colInd = (int*)big_alloc((lnnz ? lnnz : 1) * sizeof(int));
-  A->val = (double*)big_alloc((lnnz ? lnnz : 1) * sizeof(double));
+  A->colInd = (int*)pa_big_alloc((lnnz ? lnnz : 1) * sizeof(int));
+  A->val = (double*)pa_big_alloc((lnnz ? lnnz : 1) * sizeof(double));
   if (!A->rowPtr || !A->colInd || !A->val) return PA_FAIL("out of host memory for the row panel (%zu entries)", lnnz);
   A->rowPtr[0] = 0;
   {
@@ -612,7 +330,7 @@ static int build_panel(pa_operator_t* o, const int* rp, const int* ci, const dou
   for (int q = 0; q < halo; ++q)
     recv_by_proc[owner_of_part(part_of_row(in->rowPos, nparts, halo_cols[q]), nparts, size)]++;
   /* device CSR with local column ids */
-  int* lcol = (int*)big_alloc((lnnz + 8) * sizeof(int));
+  int* lcol = (int*)pa_big_alloc((lnnz + 8) * sizeof(int));
   if (!lcol) { free(mark); free(recv_by_proc); return PA_FAIL("out of host memory"); }
 #pragma omp parallel for num_threads(pa_host_threads()) schedule(static)
   for (long long k = 0; k < (long long)lnnz; ++k) { int c = A->colInd[k]; lcol[k] = (c >= lo && c < hi) ? c - lo : m + mark[c] - 1; }
@@ -887,7 +605,7 @@ static int load_mtx(const char* file, int* N_out, int** rp_out, int** ci_out, do
     if (tot > 2147483000LL) { free(hist); free(rp); free(I); free(J); free(V); return PA_FAIL("%s has too many nonzeros for int32 indices", file); }
   }
   rp[M] = (int)tot;
-  mm_ent_t* ent = (mm_ent_t*)big_alloc((size_t)(tot ? tot : 1) * sizeof(mm_ent_t));
+  mm_ent_t* ent = (mm_ent_t*)pa_big_alloc((size_t)(tot ? tot : 1) * sizeof(mm_ent_t));
   if (!ent) { free(hist); free(rp); free(I); free(J); free(V); return PA_FAIL("out of host memory for %lld entries", tot); }
 #pragma omp parallel for num_threads(TH) schedule(static, 1)
   for (int t = 0; t < TH; ++t) {
@@ -932,8 +650,8 @@ static int load_mtx(const char* file, int* N_out, int** rp_out, int** ci_out, do
   int* rp2 = (int*)malloc(((size_t)M + 1) * sizeof(int));
   long long out = 0;
   for (int i = 0; rp2 && i < M; ++i) { rp2[i] = (int)out; out += len[i]; }
-  int* ci = (int*)big_alloc((size_t)(out ? out : 1) * sizeof(int));
-  double* vv = (double*)big_alloc((size_t)(out ? out : 1) * sizeof(double));
+  int* ci = (int*)pa_big_alloc((size_t)(out ? out : 1) * sizeof(int));
+  double* vv = (double*)pa_big_alloc((size_t)(out ? out : 1) * sizeof(double));
   if (!rp2 || !ci || !vv) { free(rp2); free(ci); free(vv); free(len); free(ent); free(rp); return PA_FAIL("out of host memory"); }
   rp2[M] = (int)out;
 #pragma omp parallel for num_threads(pa_host_threads()) schedule(static)
@@ -1052,8 +770,8 @@ static int build_distributed(const char* file, int rank, int size) {
     }
     if (pa_mpi_bcast(nzs, (size_t)size * sizeof(long long), 0)) { free(nzs); return 1; }
     int* bl = (int*)malloc((capm + 1) * sizeof(int));
-    int* bc = (int*)big_alloc((cap + 16) * sizeof(int));
-    double* bv = (double*)big_alloc((cap + 16) * sizeof(double));
+    int* bc = (int*)pa_big_alloc((cap + 16) * sizeof(int));
+    double* bv = (double*)pa_big_alloc((cap + 16) * sizeof(double));
     if (pa_mpi_agree(!bl || !bc || !bv)) { free(bl); free(bc); free(bv); free(nzs); return PA_FAIL("out of host memory for the row panels"); }
     for (int g = 1; g < size; ++g) {
       int p0 = (int)((long long)g * nparts / size), p1 = (int)((long long)(g + 1) * nparts / size);
@@ -1082,8 +800,8 @@ static int build_distributed(const char* file, int rank, int size) {
     if (pa_mpi_bcast(nzs, (size_t)size * sizeof(long long), 0)) { free(nzs); return PA_FAIL("receiving the panel sizes failed"); }
     size_t nz = (size_t)nzs[rank];
     int* lrp = (int*)malloc(((size_t)mg + 1) * sizeof(int));
-    int* lci = (int*)big_alloc((nz ? nz : 1) * sizeof(int));
-    double* lv = (double*)big_alloc((nz ? nz : 1) * sizeof(double));
+    int* lci = (int*)pa_big_alloc((nz ? nz : 1) * sizeof(int));
+    double* lv = (double*)pa_big_alloc((nz ? nz : 1) * sizeof(double));
     if (pa_mpi_agree(!lrp || !lci || !lv)) {      /* (pairs with rank 0's) */
       free(lrp); free(lci); free(lv); free(nzs);
       return PA_FAIL("out of host memory for the row panels (%zu entries here)", nz);
@@ -1294,19 +1012,18 @@ int preAlps_hip_prepare_operator(int enlFac) {
 /* Run-to-run spread study: move the matrix values (which & 1) and / or the slot array
  * (which & 2) of the run plan to freshly allocated device memory; the old arrays stay allocated, so the
  * new ones land on other physical pages. */
-static size_t g_dbg_val_bytes = 0, g_dbg_slot_bytes = 0;
 int preAlps_hip_debug_move_plan(int which) {
   pa_operator_t* o = &g_op;
   if (!o->plan.runs || !g_dbg_val_bytes) return PA_FAIL("no run plan");
   if (which & 1) {
     double* nv = (double*)pa_rt_malloc(g_dbg_val_bytes);
-    if (!nv || pa_rt_d2d(nv, o->d_val, g_dbg_val_bytes) || pa_rt_sync()) return PA_FAIL("%s", pa_rt_error());
-    o->d_val = nv; o->plan.val = nv;
+    if (!nv || pa_rt_d2d(nv, o->plan.val, g_dbg_val_bytes) || pa_rt_sync()) return PA_FAIL("%s", pa_rt_error());
+    o->d_plan[PA_PL_VAL] = nv; o->plan.val = nv;
   }
   if (which & 2) {
     unsigned short* nc = (unsigned short*)pa_rt_malloc(g_dbg_slot_bytes);
-    if (!nc || pa_rt_d2d(nc, o->d_col16, g_dbg_slot_bytes) || pa_rt_sync()) return PA_FAIL("%s", pa_rt_error());
-    o->d_col16 = nc; o->plan.col16 = nc;
+    if (!nc || pa_rt_d2d(nc, o->plan.col16, g_dbg_slot_bytes) || pa_rt_sync()) return PA_FAIL("%s", pa_rt_error());
+    o->d_plan[PA_PL_COL16] = nc; o->plan.col16 = nc;
   }
   return 0;
 }
@@ -1400,8 +1117,8 @@ int preAlps_hip_get_stat(const char* key, double* value) {
   else if (!strcmp(key, "spmm_slices")) *value = o->plan.nslices;
   else if (!strcmp(key, "spmm_stored_entries")) *value = o->sell_entries;
   else if (!strcmp(key, "spmm_stream_bytes")) *value = o->stream_bytes;
-  else if (!strcmp(key, "spmm_val_address")) *value = (double)(uintptr_t)o->d_val;      /* (for the run-to-run spread study) */
-  else if (!strcmp(key, "spmm_slot_address")) *value = (double)(uintptr_t)o->d_col16;
+  else if (!strcmp(key, "spmm_val_address")) *value = (double)(uintptr_t)o->plan.val;      /* (for the run-to-run spread study) */
+  else if (!strcmp(key, "spmm_slot_address")) *value = (double)(uintptr_t)o->plan.col16;
   else if (!strcmp(key, "spmm_staged")) *value = o->plan.staged;
   else if (!strcmp(key, "spmm_runs")) *value = o->plan.runs;
   else if (!strcmp(key, "spmm_stage_rows")) *value = o->plan.stage_cap;
@@ -1452,206 +1169,4 @@ int preAlps_hip_reference_rhs(double* rhs_local) {
   }
   free(stream);
   return 0;
-}
-
-/* Staged plan with one LDS slot per run of up to three consecutive columns.  The staging
- * area lists the external rows below the block's own range, the own range, the external
- * rows above it and two zero rows, so slots ascend with the column and a run never breaks
- * at the edge of the own range.  A run covers slots [s, s+2]; entries of the row that fall
- * inside it fill its three values, the rest are zeros.  Returns 0 on success, 1 when the
- * plan does not pay (zero fill above 6 % of the plain SELL storage, external rows above a
- * quarter of the matrix stream, or a slice that does not fit the staging area), -1 on error. */
-static int build_plan_runs(pa_operator_t* o, int ts) {
-  const pa_operator_info_t* in = &o->info;
-  const int* rowptr = in->A.rowPtr;
-  const int* colind = o->lcol;
-  const double* val = in->A.val;
-  int m = in->m, ncols = m + in->halo;
-  /* panels of 16 columns: the plan is cut for 8 columns and a block is worked twice, once per half of the
-   * panel (spmm.hip; staging area and pay-off test of stride 8).  One workgroup staging all 16 columns was
-   * measured slower: 628 against 371 us, the LDS reads of 128 B per nonzero and lane dominate. */
-  if (ts >= 16) ts /= 2;
-  /* 8 columns: the rows of the staging area are 80 bytes apart (spmm.hip: spmm_row, no LDS bank conflicts) and a
-   * workgroup may stage 80 KiB, two workgroups per CU.  Block rows / staging budget measured with the padded rows
-   * (70^3, iterations/s at 8 | 16 columns): 192 / 60 KiB 1834 | 1038, 256 / 64 KiB 1776 | 977, **256 / 80 KiB
-   * 1849 | 1094**, 320 / 80 KiB 1763 | 998, 320 / 100 KiB 1679 | 912 (before the padding: 192 rows / 48 KiB,
-   * three workgroups per CU, 1832 | 1025). */
-  int cap_rows = (ts <= 4 ? 32768 : 81920) / (ts == 8 ? 80 : ts * 8) - 2;
-  if (cap_rows > 65533) cap_rows = 65533;
-  int blk_rows = spmm_block_rows(m, 256);
-  if (blk_rows < 64) blk_rows = 64;
-  blk_rows &= ~63;
-  if (blk_rows > cap_rows) blk_rows = cap_rows & ~63;
-  if (blk_rows < 64) return 1;
-  int nslices = 0;
-  double plain = 0.0;
-  for (int p = in->part0; p < in->part1; ++p) nslices += (in->rowPos[p + 1] - in->rowPos[p] + 63) / 64;
-  size_t ns1 = (size_t)(nslices ? nslices : 1);
-  long long* sl_off = (long long*)malloc((ns1 + 1) * sizeof(long long));
-  int* sl_len = (int*)malloc(ns1 * sizeof(int));
-  int* sl_row0 = (int*)malloc(ns1 * sizeof(int));
-  int* sl_nrows = (int*)malloc(ns1 * sizeof(int));
-  int s = 0;
-  for (int p = in->part0; p < in->part1; ++p) {
-    int pr0 = in->rowPos[p] - in->row_off, pr1 = in->rowPos[p + 1] - in->row_off;
-    for (int r = pr0; r < pr1; r += 64, ++s) {
-      int nr = pr1 - r < 64 ? pr1 - r : 64, len = 0;
-      for (int i = 0; i < nr; ++i) { int l = rowptr[r + i + 1] - rowptr[r + i]; if (l > len) len = l; }
-      sl_row0[s] = r; sl_nrows[s] = nr;
-      plain += 64.0 * len;
-    }
-  }
-  int* blk_slice = (int*)malloc((ns1 + 1) * sizeof(int));
-  int* blk_ext_off = (int*)malloc((ns1 + 1) * sizeof(int));
-  int* blk_nlow = (int*)malloc(ns1 * sizeof(int));
-  char* needs_halo = (char*)malloc(ns1);
-  int* stamp = (int*)calloc(ncols ? ncols : 1, sizeof(int));
-  int* slot_of = (int*)malloc((ncols ? ncols : 1) * sizeof(int));
-  size_t ext_cap = 1024, next_tot = 0;
-  int* ext_rows = (int*)malloc(ext_cap * sizeof(int));
-  size_t run_cap = (size_t)(plain / 3.0 * 1.1) + 4096, nruns = 0;   /* stored runs (64 per step of a slice) */
-  unsigned short* c16 = (unsigned short*)big_alloc(run_cap * sizeof(unsigned short));
-  double* sval = (double*)big_alloc(run_cap * 3 * sizeof(double));
-  int nblk = 0, q = 0, max_stage = 0, rc = 0, gen = 0;
-  if (!c16 || !sval || !stamp || !slot_of || !ext_rows) rc = -1;
-  sl_off[0] = 0;
-  while (q < nslices && !rc) {
-    int nsl = 0;
-    while (q + nsl < nslices && (nsl + 1) * 64 <= blk_rows) ++nsl;
-    for (;;) {
-      int r0 = sl_row0[q], r1 = sl_row0[q + nsl - 1] + sl_nrows[q + nsl - 1];
-      int nown = r1 - r0, next = 0, nlow = 0;
-      size_t mark0 = next_tot;
-      char h = 0;
-      ++gen;
-      for (int k = rowptr[r0]; k < rowptr[r1]; ++k) {
-        int c = colind[k];
-        if (c >= r0 && c < r1) continue;
-        if (stamp[c] != gen) {
-          stamp[c] = gen;
-          if (next_tot == ext_cap) { ext_cap *= 2; ext_rows = (int*)realloc(ext_rows, ext_cap * sizeof(int)); }
-          ext_rows[next_tot++] = c; ++next;
-          if (c < r0) ++nlow;
-          if (c >= m) h = 1;
-        }
-      }
-      if (nown + next > cap_rows) {
-        next_tot = mark0;
-        if (nsl == 1) { rc = 1; break; }
-        nsl = (nsl + 1) / 2;
-        continue;
-      }
-      int* er = ext_rows + mark0;
-      for (int a = 1; a < next; ++a) { int v = er[a], b2 = a; while (b2 > 0 && er[b2 - 1] > v) { er[b2] = er[b2 - 1]; --b2; } er[b2] = v; }
-      for (int a = 0; a < next; ++a) slot_of[er[a]] = a < nlow ? a : nown + a;
-      for (int sq = q; sq < q + nsl; ++sq) {
-        int r = sl_row0[sq], nr = sl_nrows[sq], len3 = 0;
-        /* pass 1: runs per row */
-        for (int i = 0; i < nr; ++i) {
-          int row = r + i, nrun = 0, last = -4;
-          for (int k = rowptr[row]; k < rowptr[row + 1]; ++k) {
-            int c = colind[k], sl = (c >= r0 && c < r1) ? nlow + c - r0 : slot_of[c];
-            if (sl > last + 2 || sl < last) { last = sl; ++nrun; }
-          }
-          if (nrun > len3) len3 = nrun;
-        }
-        if (nruns + (size_t)len3 * 64 > run_cap) {
-          run_cap = (run_cap + (size_t)len3 * 64) * 3 / 2;
-          c16 = (unsigned short*)realloc(c16, run_cap * sizeof(unsigned short));
-          sval = (double*)realloc(sval, run_cap * 3 * sizeof(double));
-          if (!c16 || !sval) { rc = -1; break; }
-        }
-        unsigned short* cc = c16 + nruns;
-        double* vv = sval + 3 * nruns;
-        for (int i = 0; i < 64; ++i) {
-          int row = i < nr ? r + i : r, own = nlow + row - r0, nrun = 0, last = -4;
-          if (i < nr)
-            for (int k = rowptr[row]; k < rowptr[row + 1]; ++k) {
-              int c = colind[k], sl = (c >= r0 && c < r1) ? nlow + c - r0 : slot_of[c];
-              if (sl > last + 2 || sl < last) {
-                last = sl;
-                cc[(size_t)nrun * 64 + i] = (unsigned short)sl;
-                vv[((size_t)3 * nrun + 0) * 64 + i] = 0.0; vv[((size_t)3 * nrun + 1) * 64 + i] = 0.0;
-                vv[((size_t)3 * nrun + 2) * 64 + i] = 0.0;
-                ++nrun;
-              }
-              vv[((size_t)3 * (nrun - 1) + (sl - last)) * 64 + i] = val[k];
-            }
-          for (int k = nrun; k < len3; ++k) {     /* padding: zeros against the row's own slot */
-            cc[(size_t)k * 64 + i] = (unsigned short)own;
-            vv[((size_t)3 * k + 0) * 64 + i] = 0.0; vv[((size_t)3 * k + 1) * 64 + i] = 0.0;
-            vv[((size_t)3 * k + 2) * 64 + i] = 0.0;
-          }
-        }
-        sl_len[sq] = len3;
-        nruns += (size_t)len3 * 64;
-        sl_off[sq + 1] = (long long)nruns;
-      }
-      if (rc) break;
-      if (nown + next + 2 > max_stage) max_stage = nown + next + 2;
-      blk_slice[nblk] = q; blk_ext_off[nblk] = (int)mark0; blk_nlow[nblk] = nlow; needs_halo[nblk] = h;
-      ++nblk;
-      q += nsl;
-      break;
-    }
-  }
-  if (!rc) {
-    double stream = 26.0 * (double)nruns + 4.0 * (double)next_tot;
-    double ext_bytes = (double)next_tot * ts * 8.0;
-    /* PREALPS_SPMM_RUNS=2 forces the plan (tests on irregular patterns) */
-    if (env_int("PREALPS_SPMM_RUNS", 1) < 2 && (3.0 * (double)nruns > 1.06 * plain || ext_bytes >= 0.25 * 10.0 * plain)) rc = 1;
-    else o->stream_bytes = stream;
-  }
-  if (!rc) {
-    blk_slice[nblk] = nslices; blk_ext_off[nblk] = (int)next_tot;
-    int* order = (int*)malloc((nblk > 0 ? nblk : 1) * sizeof(int));
-    int ni = 0;
-    for (int b = 0; b < nblk; ++b) if (!needs_halo[b]) order[ni++] = b;
-    int k2 = ni;
-    for (int b = 0; b < nblk; ++b) if (needs_halo[b]) order[k2++] = b;
-    size_t nr1 = nruns ? nruns : 1;
-    o->d_sl_off = (long long*)pa_rt_malloc((ns1 + 1) * sizeof(long long));
-    o->d_sl_len = (int*)pa_rt_malloc(ns1 * sizeof(int));
-    o->d_sl_row0 = (int*)pa_rt_malloc(ns1 * sizeof(int));
-    o->d_sl_nrows = (int*)pa_rt_malloc(ns1 * sizeof(int));
-    o->d_col16 = (unsigned short*)pa_rt_malloc(nr1 * sizeof(unsigned short));
-    o->d_val = (double*)pa_rt_malloc(nr1 * 3 * sizeof(double));
-    g_dbg_val_bytes = nr1 * 3 * sizeof(double); g_dbg_slot_bytes = nr1 * sizeof(unsigned short);
-    o->d_blk_slice = (int*)pa_rt_malloc(((size_t)nblk + 1) * sizeof(int));
-    o->d_blk_ext_off = (int*)pa_rt_malloc(((size_t)nblk + 1) * sizeof(int));
-    o->d_blk_nlow = (int*)pa_rt_malloc((size_t)(nblk > 0 ? nblk : 1) * sizeof(int));
-    o->d_ext_rows = (int*)pa_rt_malloc((next_tot + 1) * sizeof(int));   /* one spare entry: k_spmm_runs reads ids unconditionally */
-    o->d_order = (int*)pa_rt_malloc((nblk > 0 ? nblk : 1) * sizeof(int));
-    int bad = (!o->d_sl_off || !o->d_sl_len || !o->d_sl_row0 || !o->d_sl_nrows || !o->d_col16 || !o->d_val ||
-               !o->d_blk_slice || !o->d_blk_ext_off || !o->d_blk_nlow || !o->d_ext_rows || !o->d_order);
-    bad = bad || pa_rt_h2d(o->d_sl_off, sl_off, ((size_t)nslices + 1) * sizeof(long long));
-    bad = bad || pa_rt_h2d(o->d_sl_len, sl_len, nslices * sizeof(int));
-    bad = bad || pa_rt_h2d(o->d_sl_row0, sl_row0, nslices * sizeof(int));
-    bad = bad || pa_rt_h2d(o->d_sl_nrows, sl_nrows, nslices * sizeof(int));
-    bad = bad || pa_rt_h2d(o->d_col16, c16, nruns * sizeof(unsigned short));
-    bad = bad || pa_rt_h2d(o->d_val, sval, nruns * 3 * sizeof(double));
-    bad = bad || pa_rt_h2d(o->d_blk_slice, blk_slice, ((size_t)nblk + 1) * sizeof(int));
-    bad = bad || pa_rt_h2d(o->d_blk_ext_off, blk_ext_off, ((size_t)nblk + 1) * sizeof(int));
-    bad = bad || pa_rt_h2d(o->d_blk_nlow, blk_nlow, (size_t)nblk * sizeof(int));
-    bad = bad || pa_rt_h2d(o->d_ext_rows, ext_rows, next_tot * sizeof(int));
-    bad = bad || pa_rt_h2d(o->d_order, order, nblk * sizeof(int));
-    free(order);
-    if (bad) { PA_FAIL("uploading the SpMM plan failed: %s", pa_rt_error()); rc = -1; }
-    else {
-      pa_spmm_plan_t* pl = &o->plan;
-      pl->m = m; pl->nslices = nslices; pl->sl_off = o->d_sl_off; pl->sl_len = o->d_sl_len;
-      pl->sl_row0 = o->d_sl_row0; pl->sl_nrows = o->d_sl_nrows; pl->val = o->d_val;
-      pl->nblk = nblk; pl->blk_slice = o->d_blk_slice; pl->order = o->d_order; pl->n_interior = ni;
-      pl->staged = 1; pl->runs = 1; pl->runs_cols = ts; pl->col16 = o->d_col16; pl->blk_ext_off = o->d_blk_ext_off;
-      pl->blk_nlow = o->d_blk_nlow; pl->ext_rows = o->d_ext_rows;
-      pl->stage_cap = max_stage;
-      o->sell_entries = 3.0 * (double)nruns;
-    }
-  } else if (rc < 0) {
-    PA_FAIL("out of host memory for the SpMM plan");
-  }
-  free(sl_off); free(sl_len); free(sl_row0); free(sl_nrows);
-  free(blk_slice); free(blk_ext_off); free(blk_nlow); free(needs_halo); free(stamp); free(slot_of); free(ext_rows);
-  free(c16); free(sval);
-  return rc;
 }

@@ -1,6 +1,7 @@
 /*
  * pa_host.h -- internal declarations shared by the C host sources of
- * libprealps_hip.so (context.c, operator.c, block_jacobi.c, ecg.c).
+ * libprealps_hip.so (context.c, operator.c, block_jacobi.c, ecg.c).  spmm_plan.c stands apart: it
+ * includes spmm_plan.h only.
  */
 #ifndef PA_HOST_H
 #define PA_HOST_H

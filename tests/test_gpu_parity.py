@@ -118,6 +118,53 @@ def test_spmm_run_plan_on_irregular_patterns(kind, t, monkeypatch):
         prob.close()
 
 
+_PLAN_STATS = ("spmm_runs", "spmm_staged", "spmm_blocks", "spmm_slices", "spmm_stored_entries",
+               "spmm_stream_bytes", "spmm_stage_rows", "spmm_interior_blocks")
+
+
+@pytest.mark.parametrize("kind,env", [
+    ("poisson", {"PREALPS_SPMM_STAGED": "0"}),
+    ("poisson", {"PREALPS_SPMM_STAGED": "1", "PREALPS_SPMM_RUNS": "0"}),
+    ("elasticity_cut", {}),
+    ("random", {"PREALPS_SPMM_RUNS": "2"}),
+], ids=["poisson-window", "poisson-staged", "elasticity-default", "random-forced-runs"])
+def test_spmm_plan_is_rebuilt_alike_when_the_stride_changes(kind, env, monkeypatch):
+    """One operator, products at strides 4, 16, 8, 4: every change of stride frees the device plan and
+    uploads a new one.  Each product matches the oracle; the second 4-column plan is the first one again
+    (same stats, bitwise the same product); a run plan moved to fresh device memory still gives those bits."""
+    for k in ("PREALPS_SPMM_STAGED", "PREALPS_SPMM_RUNS"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    from oracle import oracle as O
+    from prealps_amd import gen
+    if kind == "random":
+        A, P = _random_spd(1500, 0.004, 11), 7
+    elif kind == "poisson":
+        A, P = O.poisson3d(12), 5
+    else:
+        rp, ci, v = gen.elasticity3d_csr(7)
+        A, P = sp.csr_matrix((v, ci, rp), shape=(3 * 343, 3 * 343)), 8
+    prob, B, rowpos = _problem(A, P)
+    try:
+        got, stats = [], []
+        for t in (4, 16, 8, 4):
+            X = np.random.default_rng(t).standard_normal((B.shape[0], t))
+            ref = O.spmm(B, X)
+            got.append(prob.block_operator(X, t))
+            stats.append({k: prob.stat(k) for k in _PLAN_STATS})
+            np.testing.assert_allclose(got[-1], ref, rtol=1e-12, atol=1e-12 * np.abs(ref).max())
+        assert np.array_equal(got[0], got[3])
+        assert stats[0] == stats[3]
+        if kind != "poisson":             # the run-plan problems
+            assert stats[3]["spmm_runs"] == 1.0
+            assert prob.L.preAlps_hip_debug_move_plan(3) == 0
+            X = np.random.default_rng(4).standard_normal((B.shape[0], 4))
+            assert np.array_equal(prob.block_operator(X, 4), got[0])
+    finally:
+        prob.close()
+
+
 def test_ecg_odir_history_vs_recorded_reference(poisson24, golden):
     prob, B, rowpos = poisson24
     g = golden["poisson24_np8_t4"]
