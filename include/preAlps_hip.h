@@ -75,6 +75,38 @@ int preAlps_hip_comm_selftest(void);
 int preAlps_OperatorBuildFromCSR(int N, const int* rowPtr, const int* colInd,
                                  const double* val, int nparts, const int* part,
                                  int scale);
+/* New values for the operator built by preAlps_OperatorBuildFromCSR, same sparsity pattern, partition and scale
+ * flag: val holds the values of the whole matrix in the order of that build's val (global CSR, rowPtr[N] entries),
+ * and every process passes all of it.  The result is the operator that preAlps_OperatorFree followed by
+ * preAlps_OperatorBuildFromCSR(the same N, rowPtr, colInd, nparts, part, scale; val) would give, bit for bit -- the
+ * host panel seen through preAlps_OperatorGetA and every later preAlps_BlockOperator product -- without the
+ * diagonal check, the ordering, the row sort, the halo and peer lists, the cut of the SpMM plan and its upload.  A
+ * time step or a Newton step with a changed coefficient is the caller this is for.  No communication: any world size.
+ *   Scaling: an operator built with scale gets its scaling vector from the new values, d_i = sqrt(1 / max_j |a_ij|),
+ * and the panel value d_i * a_ij * d_j in that order of multiplication, as at the build; a row whose new values are
+ * all zero gives the build's error ("Impossible to scale the matrix, rcmin=0").
+ *   Addresses stay: the arrays handed out by preAlps_OperatorGetA keep their addresses (A.val shows the new values:
+ * a copy of the struct stays valid), and so do the device arrays of the SpMM plan ("spmm_val_address",
+ * "spmm_slot_address" of preAlps_hip_get_stat), so a HIP graph captured by the driver loops stays valid.
+ *   Plans: with no SpMM plan yet only the host panel changes and the next product cuts its plan from the new values;
+ * an existing plan gets its values rewritten on the device by one kernel, through a map (4 bytes per stored value,
+ * kept on the device, cut at the first update of a plan) from stored value to panel entry.  A later change of the
+ * panel stride cuts the plan from the new host panel as always and drops the map.  Plan-only mode: host part only.
+ *   Ordering: the device work is queued on the library stream, behind earlier products; the entry returns when val
+ * and the host panel are free again and the kernel has finished.  Call it between solves: a solver in the middle of
+ * an iteration would go on with panels of the old matrix.
+ *   The preconditioner is not touched: the block-Jacobi factor of the old values stays in place -- it is still
+ * symmetric positive definite, a lagged preconditioner for the new matrix -- and preAlps_BlockJacobiFree +
+ * preAlps_BlockJacobiCreate on the updated A give the fresh one.  "op_values_epoch" (0 after a build, + 1 per
+ * successful update) against "bj_values_epoch" (that count at the last preAlps_BlockJacobiCreate) tells a lagged
+ * factor; "op_value_map_builds" and "op_value_map_bytes" count the maps cut for this operator and the device bytes
+ * of the current one; "op_update_host_s" / "op_update_copy_s" / "op_update_kernel_s" are the last update's host
+ * seconds (scaling vector and panel), the host seconds of the copy of the panel values to the device and the device
+ * seconds of the kernel, "op_update_map_s" the host seconds the last map took.
+ *   Refused, the operator left as it was (the message names this entry point): no operator built; an operator that
+ * preAlps_OperatorBuild read from a file (the order of its values is not the caller's); val == NULL; the zero row
+ * above; no memory for the scaling vector, the map or the device copy of the panel values. */
+int preAlps_OperatorUpdateValues(const double* val);
 /* k-way partition of the adjacency graph of a square matrix with a structurally symmetric
  * pattern (0-based CSR, diagonal stored) into nparts compact, balanced parts:
  * part[i] in [0, nparts) for every row i.  This is what the library calls in place of the

@@ -56,6 +56,8 @@ static double g_bj_setup_s[2];
 double pa_bj_setup_seconds(int which) { return g_bj_setup_s[which ? 1 : 0]; }
 
 double pa_bj_factor_bytes(void) { return g_bj.created ? g_bj.factor_bytes : 0.0; }
+static int g_bj_values_epoch;   /* pa_operator_values_epoch() at the last create: a smaller one than the operator's means a lagged factor */
+int pa_bj_values_epoch(void) { return g_bj_values_epoch; }
 int pa_bj_max_bandwidth(void) { return g_bj.created ? g_bj.max_bw : 0; }
 int pa_bj_nparts(void) { return g_bj.created ? g_bj.np : 0; }
 int pa_bj_nd_blocks(void) { return g_bj.created ? g_bj.nd_blocks : 0; }
@@ -811,6 +813,7 @@ int preAlps_BlockJacobiCreate(CPLM_Mat_CSR_t* A, int* rowPos, int sizeRowPos, in
   s->nd_blocks = nnd;
   bj_fill_plan(s);
   s->created = 1;
+  g_bj_values_epoch = pa_operator_values_epoch();
   g_bj_setup_s[1] = pa_wtime() - t_setup0;
   return 0;
 }

@@ -59,6 +59,16 @@ typedef struct {
   void* ev_packed;   /* send buffer is packed (main stream) */
   void* ev_halo;     /* halo rows have arrived (side stream) */
   int* colPos_dummy;
+  /* an update of the values in place (preAlps_OperatorUpdateValues); nothing else reads these */
+  int from_csr;        /* built by preAlps_OperatorBuildFromCSR for the caller: the value order is the caller's */
+  int scaled;
+  int* src_rowptr;     /* the caller's rowPtr (N + 1): the rows of the scaling vector */
+  int* src;            /* panel entry -> index into the caller's val (lnnz) */
+  int plan_staged_sw, plan_runs_sw, plan_cus;   /* what build_plan gave the builders for the current plan */
+  size_t plan_val_n;   /* values the upload copied */
+  unsigned* d_vmap;    /* device: stored value -> panel entry + 1, 0 = padding (plan_val_n entries; NULL: not cut yet) */
+  int values_epoch;    /* 0 after a build, + 1 per update */
+  int vmap_builds;     /* value maps cut for this operator */
 } pa_operator_t;
 
 static pa_operator_t g_op;
@@ -74,7 +84,7 @@ static int env_int(const char* name, int dflt) {
   return (s && *s) ? atoi(s) : dflt;
 }
 
-typedef struct { int c; double v; } cv_t;
+typedef struct { int c; int k; double v; } cv_t;   /* k: where the value came from (preAlps_OperatorUpdateValues) */
 static int cmp_cv(const void* a, const void* b) {
   int ca = ((const cv_t*)a)->c, cb = ((const cv_t*)b)->c;
   return (ca > cb) - (ca < cb);
@@ -102,12 +112,14 @@ static void free_plan(pa_operator_t* o) {
   for (int i = 0; i < PA_PL_COUNT; ++i) { pa_rt_free(o->d_plan[i]); o->d_plan[i] = NULL; }
   memset(&o->plan, 0, sizeof(o->plan));
   o->plan_ts = 0;
+  pa_rt_free(o->d_vmap); o->d_vmap = NULL;   /* the value map belongs to the plan */
+  o->plan_val_n = 0;
 }
 
 void preAlps_OperatorFree(void) {
   pa_operator_t* o = &g_op;
   free_plan(o);
-  free(o->lcol);
+  free(o->lcol); free(o->src); free(o->src_rowptr);
   free(o->info.rowPos); free(o->info.perm);
   free(o->info.A.rowPtr); free(o->info.A.colInd); free(o->info.A.val);
   free(o->peers); free(o->send_rows); free(o->recv_rows); free(o->send_cnt); free(o->recv_cnt);
@@ -141,6 +153,7 @@ static int upload_plan(pa_operator_t* o, const pa_spmm_host_plan_t* hp) {
   pl->ext_rows = o->d_plan[PA_PL_EXT_ROWS]; pl->order = o->d_plan[PA_PL_ORDER];
   o->sell_entries = hp->sell_entries;
   o->stream_bytes = hp->stream_bytes;
+  o->plan_val_n = hp->a[PA_PL_VAL].n;
   if (hp->runs) {   /* what preAlps_hip_debug_move_plan copies */
     g_dbg_val_bytes = hp->a[PA_PL_VAL].n_alloc * hp->a[PA_PL_VAL].elem;
     g_dbg_slot_bytes = hp->a[PA_PL_COL16].n_alloc * hp->a[PA_PL_COL16].elem;
@@ -148,15 +161,23 @@ static int upload_plan(pa_operator_t* o, const pa_spmm_host_plan_t* hp) {
   return 0;
 }
 
-/* The switches are read at every build: tests and probes change them between builds in one process. */
-static int build_plan(pa_operator_t* o, int ts) {
+/* What the builders are given for stride ts: the panel and the switches of the current plan. */
+static pa_spmm_plan_in_t plan_input(const pa_operator_t* o, int ts) {
   const pa_operator_info_t* in = &o->info;
-  free_plan(o);
   pa_spmm_plan_in_t pin = {
     .m = in->m, .halo = in->halo, .part0 = in->part0, .part1 = in->part1, .row_off = in->row_off,
     .rowPos = in->rowPos, .rowPtr = in->A.rowPtr, .lcol = o->lcol, .val = in->A.val,
-    .ts = ts, .cus = pa_rt_num_cus(),
-    .want_staged = env_int("PREALPS_SPMM_STAGED", -1), .want_runs = env_int("PREALPS_SPMM_RUNS", 1)};
+    .ts = ts, .cus = o->plan_cus, .want_staged = o->plan_staged_sw, .want_runs = o->plan_runs_sw};
+  return pin;
+}
+
+/* The switches are read at every build: tests and probes change them between builds in one process. */
+static int build_plan(pa_operator_t* o, int ts) {
+  free_plan(o);
+  o->plan_cus = pa_rt_num_cus();
+  o->plan_staged_sw = env_int("PREALPS_SPMM_STAGED", -1);
+  o->plan_runs_sw = env_int("PREALPS_SPMM_RUNS", 1);
+  pa_spmm_plan_in_t pin = plan_input(o, ts);
   pa_spmm_host_plan_t hp;
   if (pa_spmm_plan_build(&pin, &hp))
     return hp.oom_entries ? PA_FAIL("out of host memory for %zu SELL entries", hp.oom_entries)
@@ -252,8 +273,9 @@ static int order_and_scale(int N, const int* rowPtr, const int* colInd, const do
 /* Rows [row_off, row_off + m) of the permuted, scaled matrix from their raw form: row i of the panel
  * is row (whole ? perm[row_off + i] : i) of (rp, ci, v), columns in the ORIGINAL numbering.  Leaves the
  * panel (global permuted column ids, sorted), the halo slots (halo_cols ascending, lcol) and the
- * receive counts per process in `o`; `mark_out` (N ints: halo slot + 1) is handed to the caller. */
-static int build_panel(pa_operator_t* o, const int* rp, const int* ci, const double* v, int whole,
+ * receive counts per process in `o`; `mark_out` (N ints: halo slot + 1) is handed to the caller.
+ * keep_src: also o->src, the index into v of every panel entry -- the sort makes it for nothing. */
+static int build_panel(pa_operator_t* o, const int* rp, const int* ci, const double* v, int whole, int keep_src,
                        const double* d, const int* iperm, long long nnz_global, int** recv_by_proc_out) {
   pa_operator_info_t* in = &o->info;
   TRACE_DECL;
@@ -271,7 +293,9 @@ static int build_panel(pa_operator_t* o, const int* rp, const int* ci, const dou
   A->rowPtr = (int*)malloc((size_t)(m + 1) * sizeof(int));
   A->colInd = (int*)pa_big_alloc((lnnz ? lnnz : 1) * sizeof(int));
   A->val = (double*)pa_big_alloc((lnnz ? lnnz : 1) * sizeof(double));
-  if (!A->rowPtr || !A->colInd || !A->val) return PA_FAIL("out of host memory for the row panel (%zu entries)", lnnz);
+  int* src = keep_src ? (o->src = (int*)pa_big_alloc((lnnz ? lnnz : 1) * sizeof(int))) : NULL;
+  if (!A->rowPtr || !A->colInd || !A->val || (keep_src && !src))
+    return PA_FAIL("out of host memory for the row panel (%zu entries)", lnnz);
   A->rowPtr[0] = 0;
   {
     int maxlen = 0;
@@ -291,6 +315,7 @@ static int build_panel(pa_operator_t* o, const int* rp, const int* ci, const dou
         int l = 0, sorted = 1;
         for (int k = rp[r]; k < rp[r + 1]; ++k, ++l) {
           buf[l].c = iperm[ci[k]];
+          buf[l].k = k;
           buf[l].v = d ? d[old] * v[k] * d[ci[k]] : v[k];
           if (l > 0 && buf[l].c < buf[l - 1].c) sorted = 0;
         }
@@ -298,6 +323,7 @@ static int build_panel(pa_operator_t* o, const int* rp, const int* ci, const dou
         for (int q = 1; q < l; ++q) if (buf[q].c == buf[q - 1].c) dup_row = old;
         int base = A->rowPtr[i];
         for (int q = 0; q < l; ++q) { A->colInd[base + q] = buf[q].c; A->val[base + q] = buf[q].v; }
+        if (src) for (int q = 0; q < l; ++q) src[base + q] = buf[q].k;
       }
       free(buf);
     }
@@ -373,6 +399,8 @@ static int upload_operator(pa_operator_t* o, double t_build0) {
   return 0;
 }
 
+static int g_keep_value_order = 1;   /* 0 while preAlps_OperatorBuild builds from a file: that value order is not the caller's */
+
 int preAlps_OperatorBuildFromCSR(int N, const int* rowPtr, const int* colInd, const double* val,
                                  int nparts, const int* part, int scale) {
   if (!g_plan_only) PA_REQUIRE_GPU();
@@ -386,7 +414,7 @@ int preAlps_OperatorBuildFromCSR(int N, const int* rowPtr, const int* colInd, co
     return PA_FAIL("Each process needs at least one block (nparts = %d < %d = processes)", nparts, size);
   double* d = NULL; int* iperm = NULL; int* recv_by_proc = NULL;
   if (order_and_scale(N, rowPtr, colInd, val, nparts, part, scale, in, &d, &iperm)) return 1;
-  if (build_panel(o, rowPtr, colInd, val, 1, d, iperm, (long long)rowPtr[N], &recv_by_proc)) { free(d); free(iperm); return 1; }
+  if (build_panel(o, rowPtr, colInd, val, 1, g_keep_value_order, d, iperm, (long long)rowPtr[N], &recv_by_proc)) { free(d); free(iperm); return 1; }
   free(d);
   TRACE_DECL;
   int m = in->m, lo = in->row_off, hi = in->row_off + m;
@@ -425,6 +453,12 @@ int preAlps_OperatorBuildFromCSR(int N, const int* rowPtr, const int* colInd, co
   finish_peers(o, recv_by_proc, send_idx, asked_cnt);
   free(recv_by_proc); free(asked_cnt);
   TRACE("peer lists");
+  if (g_keep_value_order) {
+    o->src_rowptr = (int*)malloc(((size_t)N + 1) * sizeof(int));
+    if (!o->src_rowptr) return PA_FAIL("out of host memory");
+    memcpy(o->src_rowptr, rowPtr, ((size_t)N + 1) * sizeof(int));
+    o->from_csr = 1; o->scaled = scale != 0;
+  }
   return upload_operator(o, t_build0);
 }
 
@@ -792,7 +826,7 @@ static int build_distributed(const char* file, int rank, int size) {
     }
     free(bl); free(bc); free(bv);
     TRACE("rank 0: panels sent");
-    prc = build_panel(o, rp, ci, v, 1, d, iperm, hdr[3], &recv_by_proc);
+    prc = build_panel(o, rp, ci, v, 1, 0, d, iperm, hdr[3], &recv_by_proc);
     free(rp); free(ci); free(v);
   } else {
     int p0 = (int)((long long)rank * nparts / size), p1 = (int)((long long)(rank + 1) * nparts / size);
@@ -809,7 +843,7 @@ static int build_distributed(const char* file, int rank, int size) {
     if (pa_mpi_recv(lrp, ((size_t)mg + 1) * sizeof(int), 0, 41) || (size_t)lrp[mg] != nz) return PA_FAIL("receiving the panel failed");
     if (pa_mpi_recv(lci, nz * sizeof(int), 0, 42) || pa_mpi_recv(lv, nz * sizeof(double), 0, 43)) return 1;
     TRACE("panel received");
-    int rc = build_panel(o, lrp, lci, lv, 0, d, iperm, hdr[3], &recv_by_proc);
+    int rc = build_panel(o, lrp, lci, lv, 0, 0, d, iperm, hdr[3], &recv_by_proc);
     free(lrp); free(lci); free(lv);
     prc = rc;
   }
@@ -869,7 +903,9 @@ int preAlps_OperatorBuild(const char* matrixFilename, MPI_Comm comm) {
   int nparts = env_int("PREALPS_NPARTS", pa_world_size());
   int* part = NULL;
   if (choose_partition(N, rp, ci, nparts, &part)) { free(rp); free(ci); free(v); return 1; }
+  g_keep_value_order = 0;
   rc = preAlps_OperatorBuildFromCSR(N, rp, ci, v, nparts, part, 1);
+  g_keep_value_order = 1;
   free(part); free(rp); free(ci); free(v);
   return rc;
 }
@@ -1009,6 +1045,104 @@ int preAlps_hip_prepare_operator(int enlFac) {
   return 0;
 }
 
+/* ------------------------------------------------------ new values in place ---- */
+int pa_operator_values_epoch(void) { return g_op.values_epoch; }
+/* the last update: host seconds of scaling vector + panel, host seconds of the copy of the panel values to the
+ * device, device seconds of k_plan_set_values between two events; the seconds the last value map took (cut, upload) */
+static double g_update_host_s, g_update_copy_s, g_update_kernel_s, g_update_map_s;
+
+/* The value map of the current plan on the device, cut once per plan (spmm_plan.h). */
+static int ensure_value_map(pa_operator_t* o) {
+  if (o->d_vmap) return 0;
+  pa_spmm_plan_in_t pin = plan_input(o, o->plan_ts);
+  pa_spmm_value_map_t vm;
+  if (pa_spmm_plan_value_map(&pin, &vm)) return PA_FAIL("out of host memory for the value map of the SpMM plan");
+  ++o->vmap_builds;
+  int rc = 0;
+  if (vm.nslices != o->plan.nslices || vm.nblk != o->plan.nblk || vm.staged != o->plan.staged || vm.runs != o->plan.runs ||
+      vm.runs_cols != o->plan.runs_cols || vm.n != o->plan_val_n)
+    rc = PA_FAIL("the value map does not fit the SpMM plan on the device (slices %d / %d, blocks %d / %d, values %zu / %zu)",
+                 vm.nslices, o->plan.nslices, vm.nblk, o->plan.nblk, vm.n, o->plan_val_n);
+  if (!rc) {
+    unsigned* dm = (unsigned*)pa_rt_malloc((vm.n ? vm.n : 1) * sizeof(unsigned));
+    if (!dm || pa_rt_h2d(dm, vm.map, vm.n * sizeof(unsigned))) {
+      pa_rt_free(dm);
+      rc = PA_FAIL("uploading the value map failed: %s", pa_rt_error());
+    } else o->d_vmap = dm;
+  }
+  free(vm.map);
+  return rc;
+}
+
+/* The operator that a fresh preAlps_OperatorBuildFromCSR with these values (same pattern, partition and scale) would
+ * give, bit for bit, without the build: the host panel is rewritten through o->src, the plan on the device through
+ * its value map (k_plan_set_values); every address stays.  Every refusal and every allocation comes before the first
+ * write. */
+int preAlps_OperatorUpdateValues(const double* val) {
+  pa_operator_t* o = &g_op;
+  pa_operator_info_t* in = &o->info;
+  if (!in->built) return PA_FAIL("operator not built");
+  if (!o->from_csr)
+    return PA_FAIL("the operator was built from a file by preAlps_OperatorBuild: the order of its values is not the caller's");
+  if (!val) return PA_FAIL(" wrong test 'val != NULL'");
+  double t0 = pa_wtime();
+  g_update_copy_s = g_update_kernel_s = 0.0;
+  const int N = in->N, m = in->m;
+  const int* rp = o->src_rowptr;
+  double* d = NULL;
+  if (o->scaled) {   /* the scaling vector of order_and_scale, from the new values */
+    d = (double*)malloc((size_t)N * sizeof(double));
+    if (!d) return PA_FAIL("out of host memory");
+    int zero_row = 0;
+#pragma omp parallel for num_threads(pa_host_threads()) schedule(static) reduction(|| : zero_row)
+    for (int i = 0; i < N; ++i) {
+      double mx = 0.0;
+      for (int k = rp[i]; k < rp[i + 1]; ++k) { double a = fabs(val[k]); if (a > mx) mx = a; }
+      if (mx == 0.0) zero_row = 1;
+      d[i] = mx > 0.0 ? sqrt(1.0 / mx) : 0.0;
+    }
+    if (zero_row) { free(d); return PA_FAIL("Impossible to scale the matrix, rcmin=0"); }
+  }
+  const int on_device = !g_plan_only && o->plan_ts != 0;
+  double* d_pv = NULL;
+  if (on_device) {
+    double tm = pa_wtime();
+    const int cut = !o->d_vmap;
+    if (ensure_value_map(o)) { free(d); return 1; }
+    if (cut) g_update_map_s = pa_wtime() - tm;
+    t0 += pa_wtime() - tm;
+    d_pv = (double*)pa_rt_malloc((size_t)(o->lnnz ? o->lnnz : 1) * sizeof(double));
+    if (!d_pv) { free(d); return PA_FAIL("no device memory for the new panel values: %s", pa_rt_error()); }
+  }
+  /* the panel, as build_panel forms it: d[old row] * v * d[old column], in that order */
+  const CPLM_Mat_CSR_t* A = &in->A;
+#pragma omp parallel for num_threads(pa_host_threads()) schedule(static)
+  for (int i = 0; i < m; ++i) {
+    const int old = in->perm[in->row_off + i];
+    for (int e = A->rowPtr[i]; e < A->rowPtr[i + 1]; ++e) {
+      const double v = val[o->src[e]];
+      A->val[e] = d ? d[old] * v * d[in->perm[A->colInd[e]]] : v;
+    }
+  }
+  free(d);
+  ++o->values_epoch;
+  g_update_host_s = pa_wtime() - t0;
+  if (!on_device) return 0;
+  /* behind the products already queued on the library stream; the copy returns when it has read A->val */
+  t0 = pa_wtime();
+  int rc = pa_rt_h2d(d_pv, A->val, (size_t)o->lnnz * sizeof(double));
+  g_update_copy_s = pa_wtime() - t0;
+  void* e0 = pa_rt_event_create();
+  void* e1 = pa_rt_event_create();
+  rc = rc || !e0 || !e1 || pa_rt_event_record(e0) ||
+       pa_k_plan_set_values(o->d_vmap, d_pv, (double*)o->plan.val, o->plan_val_n) || pa_rt_event_record(e1) || pa_rt_sync();
+  if (!rc) g_update_kernel_s = pa_rt_event_elapsed_s(e0, e1);
+  pa_rt_event_destroy(e0); pa_rt_event_destroy(e1);
+  pa_rt_free(d_pv);             /* (the launch has finished) */
+  if (rc) return PA_FAIL("writing the new values into the SpMM plan failed: %s", pa_rt_error());
+  return 0;
+}
+
 /* Run-to-run spread study: move the matrix values (which & 1) and / or the slot array
  * (which & 2) of the run plan to freshly allocated device memory; the old arrays stay allocated, so the
  * new ones land on other physical pages. */
@@ -1123,6 +1257,14 @@ int preAlps_hip_get_stat(const char* key, double* value) {
   else if (!strcmp(key, "spmm_runs")) *value = o->plan.runs;
   else if (!strcmp(key, "spmm_stage_rows")) *value = o->plan.stage_cap;
   else if (!strcmp(key, "spmm_interior_blocks")) *value = o->plan.n_interior;
+  else if (!strcmp(key, "op_values_epoch")) *value = o->values_epoch;
+  else if (!strcmp(key, "op_value_map_builds")) *value = o->vmap_builds;
+  else if (!strcmp(key, "op_value_map_bytes")) *value = o->d_vmap ? (double)o->plan_val_n * sizeof(unsigned) : 0.0;
+  else if (!strcmp(key, "bj_values_epoch")) *value = pa_bj_values_epoch();
+  else if (!strcmp(key, "op_update_host_s")) *value = g_update_host_s;
+  else if (!strcmp(key, "op_update_copy_s")) *value = g_update_copy_s;
+  else if (!strcmp(key, "op_update_kernel_s")) *value = g_update_kernel_s;
+  else if (!strcmp(key, "op_update_map_s")) *value = g_update_map_s;
   else if (!strcmp(key, "setup_build_s")) *value = g_setup_build_s;
   else if (!strcmp(key, "setup_plan_s")) *value = g_setup_plan_s;
   else if (!strcmp(key, "setup_bj_factor_s")) *value = pa_bj_setup_seconds(0);

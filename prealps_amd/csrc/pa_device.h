@@ -126,6 +126,10 @@ void pa_k_bj_gram_arm(const double* in, const double* out, const double* prev, d
 void pa_k_bj_gram_disarm(const double* owner);
 long long pa_k_bj_gram_applies(void);        /* block solves that left the Gram block behind so far */
 int pa_k_bj_gram_take(const double* in, const double* out);
+/* New values for the plan's value array (spmm_values.hip): val[s] = map[s] ? pv[map[s] - 1] : 0.0 for s < n, the
+ * slots the upload copied (n even; entries past n are not touched).  map: spmm_plan.h, pa_spmm_plan_value_map;
+ * pv: the panel's values in panel order.  All three on the device. */
+int pa_k_plan_set_values(const unsigned* map, const double* pv, double* val, size_t n);
 /* sendbuf[i*ts + c] = X[idx[i]*ts + c] */
 int pa_k_pack_rows(int n, int ts, const int* idx, const double* X, double* sendbuf);
 

@@ -80,6 +80,9 @@ int pa_operator_gram_blocks(int ts);
  * pk_slot[pk_off[r] .. pk_off[r + 1]) of sendbuf, ts doubles each); the next preAlps_BlockOperator(X, .) skips its pack */
 int pa_operator_pack_hint(int ts, const double* X, const int** pk_off, const int** pk_slot, double** sendbuf);
 
+int pa_operator_values_epoch(void);   /* 0 after a build, + 1 per preAlps_OperatorUpdateValues */
+int pa_bj_values_epoch(void);         /* that count at the last preAlps_BlockJacobiCreate */
+
 int pa_panel_stride(int enlFac);
 static inline int pa_desc_stride(const CPLM_Mat_Dense_t* A) { return A->info.lda; }
 void pa_set_desc(CPLM_Mat_Dense_t* A, int M, int N, int m, int n, int ts);

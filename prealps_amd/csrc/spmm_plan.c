@@ -7,6 +7,7 @@
  *   staged  every X row a block touches is copied to LDS first; 16-bit LDS slots instead of columns;
  *   runs    the staged plan with one slot per run of up to three consecutive columns.
  * Host arithmetic only (spmm_plan.h); operator.c reads the switches and uploads the result.
+ * pa_spmm_plan_value_map: which panel entry every stored value is, for an update of the values in place.
  */
 #include <string.h>
 
@@ -438,4 +439,28 @@ int pa_spmm_plan_build(const pa_spmm_plan_in_t* in, pa_spmm_host_plan_t* pl) {
     }
   }
   return attempt(in, pl, FORM_WINDOW);
+}
+
+/* ---------------------------------------------------------- the value map ---- */
+int pa_spmm_plan_value_map(const pa_spmm_plan_in_t* in, pa_spmm_value_map_t* vm) {
+  memset(vm, 0, sizeof(*vm));
+  const size_t nnz = (size_t)in->rowPtr[in->m];
+  double* code = (double*)pa_big_alloc((nnz ? nnz : 1) * sizeof(double));
+  if (!code) return -1;
+  for (size_t k = 0; k < nnz; ++k) code[k] = (double)(k + 1);
+  pa_spmm_plan_in_t coded = *in;
+  coded.val = code;
+  pa_spmm_host_plan_t pl;
+  int rc = pa_spmm_plan_build(&coded, &pl);
+  free(code);
+  if (rc) return -1;
+  const size_t n = pl.a[PA_PL_VAL].n;
+  const double* v = ARR(&pl, PA_PL_VAL, double);
+  uint32_t* map = (uint32_t*)pa_big_alloc((n ? n : 1) * sizeof(uint32_t));
+  if (!map) { pa_spmm_plan_free(&pl); return -1; }
+  for (size_t s = 0; s < n; ++s) map[s] = (uint32_t)v[s];
+  vm->map = map; vm->n = n;
+  vm->nslices = pl.nslices; vm->nblk = pl.nblk; vm->staged = pl.staged; vm->runs = pl.runs; vm->runs_cols = pl.runs_cols;
+  pa_spmm_plan_free(&pl);
+  return 0;
 }

@@ -7,6 +7,7 @@
 #define PA_SPMM_PLAN_H
 
 #include <stddef.h>
+#include <stdint.h>
 #include <stdlib.h>
 #include <sys/mman.h>
 
@@ -64,5 +65,19 @@ typedef struct {
 int pa_spmm_plan_build(const pa_spmm_plan_in_t* in, pa_spmm_host_plan_t* pl);
 /* Release a plan in any state (also half built); leaves it empty. */
 void pa_spmm_plan_free(pa_spmm_host_plan_t* pl);
+
+/* Where the values of a plan come from.  No decision of a builder reads a value, so the `val` array of the
+ * plan for `in` is a fixed gather of the panel's values: val[s] = map[s] ? in->val[map[s] - 1] : 0.0 for the
+ * n slots the upload copies (0: padding).  The map is read off a second pa_spmm_plan_build with the same
+ * input and the values k + 1 (exact in a double for every int32 count) in place of in->val, which is not
+ * read: the builders stay as they are and the map cannot drift from them.  The scalars are those of that
+ * second plan, for the caller to hold against the plan it has. */
+typedef struct {
+  uint32_t* map;   /* n entries; release with free() */
+  size_t n;        /* = a[PA_PL_VAL].n of the plan */
+  int nslices, nblk, staged, runs, runs_cols;
+} pa_spmm_value_map_t;
+/* Returns 0, or -1 when out of memory (vm->map is then NULL). */
+int pa_spmm_plan_value_map(const pa_spmm_plan_in_t* in, pa_spmm_value_map_t* vm);
 
 #endif

@@ -1,0 +1,40 @@
+// spmm_values.hip -- new values for the SpMM plan that is on the device (preAlps_OperatorUpdateValues): the plan's
+// value array is a fixed gather of the panel's values (spmm_plan.h: pa_spmm_plan_value_map), so an update of the
+// matrix with the same pattern rewrites that one array in place and leaves slices, slots and blocks alone.
+#include "kernels_common.h"
+
+namespace {
+
+// val[s] = map[s] ? pv[map[s] - 1] : 0.0 for the n stored slots (n even: every slot array of the three plans is a
+// multiple of 64 long).  A streaming kernel: a lane takes two neighbouring slots -- one 8-byte load of the map, one
+// 16-byte store -- and the grid strides over the pairs; val is written once and read by the next product at the
+// earliest, hence the nontemporal hint.  The reads of pv follow the plan's slice order: entry-major inside a slice,
+// so neighbouring lanes read neighbouring rows of the panel (a row apart in pv) and a slice's part of pv is read
+// whole within a few steps, out of L2.
+typedef unsigned u2v __attribute__((ext_vector_type(2)));
+typedef double d2v __attribute__((ext_vector_type(2)));
+
+__global__ __launch_bounds__(WG) void k_plan_set_values(const u2v* __restrict__ map, const double* __restrict__ pv,
+                                                       double* __restrict__ val, size_t npairs) {
+  const size_t stride = (size_t)gridDim.x * WG;
+  for (size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < npairs; i += stride) {
+    const u2v e = __builtin_nontemporal_load(map + i);
+    d2v v;
+    v.x = e.x ? pv[e.x - 1u] : 0.0;
+    v.y = e.y ? pv[e.y - 1u] : 0.0;
+    __builtin_nontemporal_store(v, reinterpret_cast<d2v*>(val) + i);
+  }
+}
+
+}  // namespace
+
+extern "C" int pa_k_plan_set_values(const unsigned* map, const double* pv, double* val, size_t n) {
+  if (n == 0) return 0;
+  if (n & 1) { snprintf(g_kerr, sizeof(g_kerr), "k_plan_set_values: odd slot count %zu", n); return 1; }
+  const size_t npairs = n / 2;
+  const int cus = pa_rt_num_cus() > 0 ? pa_rt_num_cus() : 256;
+  size_t blocks = (npairs + WG - 1) / WG;
+  if (blocks > (size_t)8 * cus) blocks = (size_t)8 * cus;      // eight workgroups per CU, the rest by the stride
+  PA_LAUNCH(k_plan_set_values, dim3((unsigned)blocks), dim3(WG), 0, cur_stream(), (const u2v*)map, pv, val, npairs);
+  return kfail("k_plan_set_values");
+}

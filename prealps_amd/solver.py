@@ -186,15 +186,21 @@ class EcgProblem:
     the library, as in the reference) and solves on them."""
 
     def __init__(self, rowptr, colind, val, nparts, part=None, scale=True, device=None,
-                 distributed=False, use_torch_stream=False, partitioner=False, shard=None):
+                 distributed=False, use_torch_stream=False, partitioner=False, shard=None, plan_only=False):
         """part: explicit partition vector; None = contiguous row blocks, or -- with
         partitioner=True -- the library's k-way graph partitioner (what preAlps_OperatorBuild
         uses where the reference calls METIS).  shard = (r, G): rehearse rank r of a G-process run in
-        this one process (preAlps_hip_loopback)."""
+        this one process (preAlps_hip_loopback).  plan_only=True: the host side alone, without a GPU
+        (preAlps_hip_plan_only, until close()): the panel, the halo plan and update_values work, products and
+        solves are refused."""
         self.L = L = _l.load()
         import os
         dev = int(os.environ.get("LOCAL_RANK", "0")) if device is None else device
-        check(L.preAlps_hip_init(dev), "preAlps_hip_init")
+        self._plan_only = bool(plan_only)
+        if self._plan_only:
+            L.preAlps_hip_plan_only(1)
+        else:
+            check(L.preAlps_hip_init(dev), "preAlps_hip_init")
         self.hooks, self.comm_kind = None, "none"
         if distributed:
             import torch
@@ -211,12 +217,15 @@ class EcgProblem:
         colind = np.ascontiguousarray(colind, dtype=np.int32)
         val = np.ascontiguousarray(val, dtype=np.float64)
         self.N = len(rowptr) - 1
+        self._nnz_global = int(rowptr[-1])
         p = None if part is None else np.ascontiguousarray(part, dtype=np.int32)
         if p is None and partitioner:
             p = partition_kway(rowptr, colind, nparts)
-        check(L.preAlps_OperatorBuildFromCSR(self.N, _pi(rowptr), _pi(colind), _pd(val), int(nparts),
-                                             None if p is None else _pi(p), 1 if scale else 0),
-              "preAlps_OperatorBuildFromCSR")
+        rc = L.preAlps_OperatorBuildFromCSR(self.N, _pi(rowptr), _pi(colind), _pd(val), int(nparts),
+                                            None if p is None else _pi(p), 1 if scale else 0)
+        if rc != 0 and self._plan_only:
+            L.preAlps_hip_plan_only(0)
+        check(rc, "preAlps_OperatorBuildFromCSR")
         self._after_build()
 
     @classmethod
@@ -259,6 +268,7 @@ class EcgProblem:
         self.nparts = L.preAlps_hip_nparts()
         self.row_off = 0
         self.has_precond = False
+        self._precond_args = (None, None)
 
     def part_vector(self):
         """part[i] of every original row i, recovered from the permutation and rowPos."""
@@ -294,6 +304,33 @@ class EcgProblem:
             if bbits:
                 self.L.preAlps_hip_set_band_precision(0)
         self.has_precond = True
+        self._precond_args = (nd_precision, band_precision)
+
+    def update_values(self, val, precond="keep"):
+        """preAlps_OperatorUpdateValues: new values for the same pattern, partition and scaling flag, in the order of
+        the val this problem was built from (the whole matrix); the operator becomes the one a fresh problem built from
+        them would hold, bit for bit, without the set-up.  self.A and local_csr() show the new panel.
+        precond="keep": the block-Jacobi factor of the old values stays, a lagged preconditioner for the new matrix
+        (stat("bj_values_epoch") < stat("op_values_epoch") tells); "rebuild": it is freed and created again from the
+        new panel with the precision arguments of the last create_block_jacobi."""
+        if precond not in ("keep", "rebuild"):
+            raise ValueError("precond must be 'keep' or 'rebuild', not %r" % (precond,))
+        if val is None:
+            ptr = None
+        else:
+            val = np.ascontiguousarray(val, dtype=np.float64)
+            if val.ndim != 1:
+                raise ValueError("val must be one-dimensional, not of shape %r" % (val.shape,))
+            nnz = getattr(self, "_nnz_global", None)      # (from_mtx: the library refuses, with its own message)
+            if nnz is not None and val.shape[0] != nnz:
+                raise ValueError("val has %d entries, the matrix this problem was built from has %d"
+                                 % (val.shape[0], nnz))
+            ptr = _pd(val)
+        check(self.L.preAlps_OperatorUpdateValues(ptr), "preAlps_OperatorUpdateValues")
+        if precond == "rebuild" and self.has_precond:
+            self.L.preAlps_BlockJacobiFree()
+            self.has_precond = False
+            self.create_block_jacobi(*self._precond_args)
 
     def reference_rhs(self):
         rhs = np.zeros(self.m)
@@ -477,3 +514,6 @@ class EcgProblem:
         self.L.preAlps_BlockJacobiFree()
         self.L.preAlps_OperatorFree()
         self.has_precond = False
+        if getattr(self, "_plan_only", False):
+            self.L.preAlps_hip_plan_only(0)
+            self._plan_only = False
