@@ -97,8 +97,9 @@ int preAlps_OperatorBuildFromCSR(int N, const int* rowPtr, const int* colInd,
  * an iteration would go on with panels of the old matrix.
  *   The preconditioner is not touched: the block-Jacobi factor of the old values stays in place -- it is still
  * symmetric positive definite, a lagged preconditioner for the new matrix -- and preAlps_BlockJacobiFree +
- * preAlps_BlockJacobiCreate on the updated A give the fresh one.  "op_values_epoch" (0 after a build, + 1 per
- * successful update) against "bj_values_epoch" (that count at the last preAlps_BlockJacobiCreate) tells a lagged
+ * preAlps_BlockJacobiCreate on the updated A give the fresh one, preAlps_BlockJacobiUpdateValues (below) the same
+ * factor in place.  "op_values_epoch" (0 after a build, + 1 per
+ * successful update) against "bj_values_epoch" (that count at the last create or refactorisation) tells a lagged
  * factor; "op_value_map_builds" and "op_value_map_bytes" count the maps cut for this operator and the device bytes
  * of the current one; "op_update_host_s" / "op_update_copy_s" / "op_update_kernel_s" are the last update's host
  * seconds (scaling vector and panel), the host seconds of the copy of the panel values to the device and the device
@@ -107,6 +108,44 @@ int preAlps_OperatorBuildFromCSR(int N, const int* rowPtr, const int* colInd,
  * preAlps_OperatorBuild read from a file (the order of its values is not the caller's); val == NULL; the zero row
  * above; no memory for the scaling vector, the map or the device copy of the panel values. */
 int preAlps_OperatorUpdateValues(const double* val);
+/* The block-Jacobi preconditioner follows an update of the values: a numeric refactorisation in place.  No argument:
+ * the values are the library's own host panel, as preAlps_OperatorGetA shows it after preAlps_OperatorUpdateValues.
+ *   Band blocks (every block without the sparse factor): the result is the preconditioner that
+ * preAlps_BlockJacobiFree + preAlps_BlockJacobiCreate on the current panel would give, bit for bit -- the plain
+ * records of both sweeps, 1 / L(j,j), the one-copy records (fp64 or fp32, in the storage of the create that is being
+ * refreshed) and the paired records -- without what depends on the pattern alone: the adjacency graphs, the orders,
+ * the bandwidths, the dispatch classes, the record offsets, the index arrays, the class lists, the host assembly of
+ * the bands and their upload.  The decisions of the create are kept with the preconditioner; no switch of the
+ * environment is read again.  The panel values go up in one copy, the bands are assembled on the device through
+ * the band map (below), and the band Cholesky and the layout kernels of the create run on the create's lists.
+ *   Addresses stay: no device array of the band factor is freed or allocated again ("bj_records_address",
+ * "bj_g4_address" of preAlps_hip_get_stat show two of them), so a HIP graph that captured an apply stays valid.
+ * The assembled bands and the copy of the panel values are temporary device memory inside the call, as in the create.
+ *   The band map: one entry of 8 bytes for every panel entry inside a band block's diagonal block, on or below the
+ * diagonal in factor order -- 4 bytes for its index in the panel's val, 4 for its place inside its block's band --
+ * and a list of chunks (block, first entry).  It is cut at the first update after a create, so a caller who never
+ * updates pays nothing, and stays on the device until the preconditioner is freed.
+ *   Blocks with the sparse (nested-dissection) factor are NOT refreshed in place: the library does not keep their
+ * symbolic structure, so they are created again from the new panel with the arguments and the storage of the create,
+ * and THEIR device arrays move ("bj_update_nd_rebuilt" = the number of blocks refreshed this way).  Band blocks of
+ * the same preconditioner still take the path above.
+ *   Stats: "bj_values_epoch" becomes "op_values_epoch"; "bj_updates" counts the successful updates since the create;
+ * "bj_band_map_builds", "bj_band_map_entries", "bj_band_map_bytes"; "bj_update_map_s" / "bj_update_copy_s" are the
+ * host seconds of the last map cut (with its upload) and of the last copy of the panel values, "bj_update_kernel_s"
+ * the device seconds between two events around assembly, factorisation and second layouts, "bj_update_total_s" the
+ * host wall seconds of the whole call.
+ *   Ordering: the work is queued on the library stream behind earlier applies, and the entry returns when the new
+ * factor is in place.  No communication: any world size.  Call it between solves.
+ *   Refused, the factor left exactly as it was (the message names this entry point; every refusal and every allocation
+ * of the band path comes before the first write into the factor): no preconditioner created; no operator built, or
+ * one freed or built again since the create; a create whose A was not the operator's own panel; a preconditioner
+ * created with PREALPS_BJ_FACTOR=host, whose records come from the host Cholesky (free and create instead); a band of
+ * 2^32 entries or more; no memory for the map, the values or the bands.
+ *   New values that are not SPD: the kernels have overwritten the records by the time a pivot fails, so the old
+ * factor cannot be kept.  The entry reports "diagonal block is not SPD (global row r)" as the create does and frees
+ * the preconditioner, as a failed create does (so does any device error after the first write, and a failure of the
+ * sparse blocks' create); a later preAlps_BlockJacobiCreate works. */
+int preAlps_BlockJacobiUpdateValues(void);
 /* k-way partition of the adjacency graph of a square matrix with a structurally symmetric
  * pattern (0-based CSR, diagonal stored) into nparts compact, balanced parts:
  * part[i] in [0, nparts) for every row i.  This is what the library calls in place of the

@@ -25,6 +25,7 @@
 #include <string.h>
 
 #include "pa_host.h"
+#include "bj_band_map.h"
 
 typedef struct {
   int created;
@@ -43,6 +44,23 @@ typedef struct {
   const int* class_list_c[16];
   pa_bj_plan_t plan;
   double factor_bytes; int max_bw; int nd_blocks;
+  /* What preAlps_BlockJacobiUpdateValues needs of the create, so that it reads no switch again and repeats no
+   * decision: the host copies of the per-block arrays and of the factor order, the switches as the create read
+   * them, and what tells that operator and panel are still the create's. */
+  int* h_row0; int* h_nrows; int* h_bw; int* h_grow0; int* h_map_f; char* h_is_nd;
+  int row_off, wide_from, dev_factor, dev_wmax, nd_bits;
+  int class_pairs[16];           /* 1: the class has paired records in Lf2 / Lb2 */
+  size_t tot;                    /* doubles of the plain records, per sweep */
+  const int* A_rowptr;           /* rowPtr of the create's A */
+  int op_build;                  /* pa_operator_build_count() at the create */
+  /* the band map on the device (bj_band_map.h) and the launch lists of the two factorisation kernels, cut at the
+   * first update and kept until the preconditioner is freed */
+  unsigned* d_bm_src; unsigned* d_bm_dst; int* d_bm_chunk_blk; unsigned* d_bm_chunk_first;
+  size_t bm_n, bm_nchunks, bm_bytes, btot;
+  long long* d_boff; int* d_slist; int* d_blist; int* d_fail;
+  int ns, nbig, wsmall, wbig;
+  int bm_builds, updates, nd_rebuilt;
+  double upd_map_s, upd_copy_s, upd_kernel_s, upd_total_s;
 } pa_bj_t;
 
 /* block that holds local (factor-order) position `pos` */
@@ -100,6 +118,9 @@ void preAlps_BlockJacobiFree(void) {
   pa_rt_free(s->d_Lf); pa_rt_free(s->d_Lb); pa_rt_free(s->d_invd_f); pa_rt_free(s->d_invd_b);
   pa_rt_free(s->d_Lf2); pa_rt_free(s->d_Lb2); pa_rt_free(s->d_off2); pa_rt_free(s->d_Lg4);
   for (int c = 0; c < 16; ++c) pa_rt_free(s->class_list[c]);
+  free(s->h_row0); free(s->h_nrows); free(s->h_bw); free(s->h_grow0); free(s->h_map_f); free(s->h_is_nd);
+  pa_rt_free(s->d_bm_src); pa_rt_free(s->d_bm_dst); pa_rt_free(s->d_bm_chunk_blk); pa_rt_free(s->d_bm_chunk_first);
+  pa_rt_free(s->d_boff); pa_rt_free(s->d_slist); pa_rt_free(s->d_blist); pa_rt_free(s->d_fail);
   pa_nd_free();
   memset(s, 0, sizeof(*s));
 }
@@ -685,6 +706,26 @@ static int bj_nd_handoff(const bj_build_t* B) {
 /* tot2 elements of 8 or 4 bytes (off2 counts elements: every offset a multiple of 8 of them, so a block
  * starts 32-byte aligned in fp32 too), and 8 KiB of zeroed slack: a request of the apply reads whole KiB
  * from a chunk's start, up to 1 KiB beyond the end of the last block's last chunk. */
+/* The launches that fill the second layouts from the plain records (the create, and the refactorisation in place). */
+static int bj_launch_g4(const pa_bj_t* s) {
+  for (int c = 0; c < s->nclass; ++c)
+    if (s->class_g4[c] &&
+        (s->g4_bits == 32
+           ? pa_k_bj_g4_setup_f32(s->class_list[c], s->class_count[c], s->d_nrows, s->d_bw, s->d_off, s->d_off2, s->d_Lf, (float*)s->d_Lg4)
+           : pa_k_bj_g4_setup(s->class_list[c], s->class_count[c], s->d_nrows, s->d_bw, s->d_off, s->d_off2, s->d_Lf, (double*)s->d_Lg4)))
+      return 1;
+  return 0;
+}
+
+static int bj_launch_pairs(const pa_bj_t* s, const int* cls_pairs) {
+  for (int c = 0; c < s->nclass; ++c)
+    if (cls_pairs[c])
+      if (pa_k_bj_pairs(s->class_list[c], s->class_count[c], s->d_nrows, s->d_bw, s->d_off, s->d_off2, s->d_Lf, s->d_Lf2) ||
+          pa_k_bj_pairs(s->class_list[c], s->class_count[c], s->d_nrows, s->d_bw, s->d_off, s->d_off2, s->d_Lb, s->d_Lb2))
+        return 1;
+  return 0;
+}
+
 static int bj_make_g4(pa_bj_t* s, int band_bits, long long tot2) {
   const size_t esz = band_bits == 32 ? sizeof(float) : sizeof(double);
   const size_t g4_alloc = (size_t)tot2 * esz + 8192;
@@ -692,12 +733,7 @@ static int bj_make_g4(pa_bj_t* s, int band_bits, long long tot2) {
   s->d_Lg4 = pa_rt_malloc(g4_alloc);
   if (!s->d_Lg4 || pa_rt_memset(s->d_Lg4, 0, g4_alloc))
     return BJ_FAIL("allocating the one-copy sweep records failed: %s", pa_rt_error());
-  for (int c = 0; c < s->nclass; ++c)
-    if (s->class_g4[c] &&
-        (band_bits == 32
-           ? pa_k_bj_g4_setup_f32(s->class_list[c], s->class_count[c], s->d_nrows, s->d_bw, s->d_off, s->d_off2, s->d_Lf, (float*)s->d_Lg4)
-           : pa_k_bj_g4_setup(s->class_list[c], s->class_count[c], s->d_nrows, s->d_bw, s->d_off, s->d_off2, s->d_Lf, (double*)s->d_Lg4)))
-      return BJ_FAIL("k_bj_g4_setup failed");
+  if (bj_launch_g4(s)) return BJ_FAIL("k_bj_g4_setup failed");
   s->g4_bytes = (double)esz * (double)tot2;
   return 0;
 }
@@ -708,11 +744,7 @@ static int bj_make_pairs(pa_bj_t* s, const int* cls_pairs, long long tot2) {
   if (!s->d_Lf2 || !s->d_Lb2 ||
       pa_rt_memset(s->d_Lf2 + tot2, 0, 512 * sizeof(double)) || pa_rt_memset(s->d_Lb2 + tot2, 0, 512 * sizeof(double)))
     return BJ_FAIL("allocating the paired sweep records failed: %s", pa_rt_error());
-  for (int c = 0; c < s->nclass; ++c)
-    if (cls_pairs[c])
-      if (pa_k_bj_pairs(s->class_list[c], s->class_count[c], s->d_nrows, s->d_bw, s->d_off, s->d_off2, s->d_Lf, s->d_Lf2) ||
-          pa_k_bj_pairs(s->class_list[c], s->class_count[c], s->d_nrows, s->d_bw, s->d_off, s->d_off2, s->d_Lb, s->d_Lb2))
-        return BJ_FAIL("k_bj_pairs failed");
+  if (bj_launch_pairs(s, cls_pairs)) return BJ_FAIL("k_bj_pairs failed");
   s->pairs_bytes = 2.0 * 8.0 * (double)tot2;
   return 0;
 }
@@ -736,6 +768,7 @@ static int bj_second_layouts(pa_bj_t* s, const bj_build_t* B) {
                       s->class_bmax[c] <= pa_bj_g4_max_rows();
     cls_pairs[c] = want_pairs && !s->class_g4[c] && (s->class_R[c] == 2 || s->class_R[c] == 3);
     any_g4 |= s->class_g4[c]; any_pairs |= cls_pairs[c];
+    s->class_pairs[c] = cls_pairs[c];
   }
   long long* off2 = (long long*)calloc((size_t)np + 1, sizeof(long long));
   long long tot2 = 0;
@@ -767,6 +800,29 @@ static void bj_fill_plan(pa_bj_t* s) {
   pl->nclass = s->nclass; pl->class_R = s->class_R; pl->class_count = s->class_count;
   pl->class_wmax = s->class_wmax;
   pl->class_list = s->class_list_c;
+}
+
+/* ---- stage 10: what a later preAlps_BlockJacobiUpdateValues needs (host memory only) ---- */
+static void* bj_dup(const void* p, size_t bytes) {
+  void* c = malloc(bytes ? bytes : 1);
+  if (c) memcpy(c, p, bytes);
+  return c;
+}
+
+static int bj_keep_decisions(pa_bj_t* s, const bj_build_t* B) {
+  const size_t np = (size_t)B->np;
+  s->h_row0 = (int*)bj_dup(B->row0, np * sizeof(int));
+  s->h_nrows = (int*)bj_dup(B->nrows, np * sizeof(int));
+  s->h_bw = (int*)bj_dup(B->bw, np * sizeof(int));
+  s->h_is_nd = (char*)bj_dup(B->is_nd, np);
+  s->h_map_f = (int*)bj_dup(B->map_f, (size_t)B->m * sizeof(int));
+  s->h_grow0 = (int*)bj_dup(B->rowPos + B->op->part0, np * sizeof(int));
+  if (!s->h_row0 || !s->h_nrows || !s->h_bw || !s->h_is_nd || !s->h_map_f || !s->h_grow0)
+    return BJ_FAIL("out of host memory for the block arrays");
+  s->row_off = B->row_off; s->wide_from = B->wide_from; s->dev_factor = B->dev_factor; s->dev_wmax = B->dev_wmax;
+  s->nd_bits = B->nd_bits; s->tot = B->tot;
+  s->A_rowptr = B->A->rowPtr; s->op_build = pa_operator_build_count();
+  return 0;
 }
 
 int preAlps_BlockJacobiCreate(CPLM_Mat_CSR_t* A, int* rowPos, int sizeRowPos, int* colPos,
@@ -805,6 +861,7 @@ int preAlps_BlockJacobiCreate(CPLM_Mat_CSR_t* A, int* rowPos, int sizeRowPos, in
   if (!rc && B.ndev > 0) rc = bj_factor_device(s, &B);
   if (!rc && B.nnd > 0) rc = bj_nd_handoff(&B);
   if (!rc) rc = bj_second_layouts(s, &B);
+  if (!rc) rc = bj_keep_decisions(s, &B);
   const size_t tot = B.tot;
   const int nnd = B.nnd;
   bj_build_release(&B);
@@ -815,6 +872,179 @@ int preAlps_BlockJacobiCreate(CPLM_Mat_CSR_t* A, int* rowPos, int sizeRowPos, in
   s->created = 1;
   g_bj_values_epoch = pa_operator_values_epoch();
   g_bj_setup_s[1] = pa_wtime() - t_setup0;
+  return 0;
+}
+
+/* ---- numeric refactorisation in place (preAlps_BlockJacobiUpdateValues) ---------- */
+#define BJU_FAIL(...) pa_fail_at("preAlps_BlockJacobiUpdateValues", __VA_ARGS__)
+
+/* The band map of the current preconditioner on the device, with the offsets of the bands and the launch lists of
+ * pa_k_bj_factor / pa_k_bj_factor_big as bj_factor_device forms them: cut once per create. */
+static int bj_ensure_band_map(pa_bj_t* s, const pa_operator_info_t* op) {
+  if (s->d_bm_src) return 0;
+  const int np = s->np;
+  const double t0 = pa_wtime();
+  pa_bj_band_map_in_t in = {.np = np, .rowPtr = op->A.rowPtr, .colInd = op->A.colInd, .row0 = s->h_row0, .nrows = s->h_nrows,
+                            .grow0 = s->h_grow0, .bw = s->h_bw, .order = s->h_map_f, .is_nd = s->h_is_nd,
+                            .wmax = s->dev_wmax, .chunk = 1024};
+  pa_bj_band_map_t bm;
+  const int brc = pa_bj_band_map_build(&in, &bm);
+  if (brc == -2)
+    return BJU_FAIL("the band of block %d (%d rows, bandwidth %d) has 2^32 entries or more: free and create instead",
+                    bm.bad_block, s->h_nrows[bm.bad_block], s->h_bw[bm.bad_block]);
+  if (brc == -3) return BJU_FAIL("block %d of the panel no longer has the pattern the preconditioner was created from", bm.bad_block);
+  if (brc) return BJU_FAIL("out of host memory for the band map");
+  ++s->bm_builds;
+  int* slist = (int*)malloc((np ? np : 1) * sizeof(int));
+  int* blist = (int*)malloc((np ? np : 1) * sizeof(int));
+  int rc = 0;
+  if (!slist || !blist) rc = BJU_FAIL("out of host memory for the band map");
+  s->ns = s->nbig = s->wsmall = s->wbig = 0;
+  for (int q = 0; q < np && !rc; ++q) {
+    if (s->h_is_nd[q]) continue;
+    if (s->h_bw[q] <= s->dev_wmax) { slist[s->ns++] = q; if (s->h_bw[q] > s->wsmall) s->wsmall = s->h_bw[q]; }
+    else { blist[s->nbig++] = q; if (s->h_bw[q] > s->wbig) s->wbig = s->h_bw[q]; }
+  }
+  if (!rc) {
+    s->d_bm_src = (unsigned*)pa_rt_malloc((bm.n ? bm.n : 1) * sizeof(unsigned));
+    s->d_bm_dst = (unsigned*)pa_rt_malloc((bm.n ? bm.n : 1) * sizeof(unsigned));
+    s->d_bm_chunk_blk = (int*)pa_rt_malloc((bm.nchunks ? bm.nchunks : 1) * sizeof(int));
+    s->d_bm_chunk_first = (unsigned*)pa_rt_malloc((bm.nchunks + 1) * sizeof(unsigned));
+    s->d_boff = (long long*)pa_rt_malloc(((size_t)np + 1) * sizeof(long long));
+    s->d_slist = (int*)pa_rt_malloc((s->ns ? s->ns : 1) * sizeof(int));
+    s->d_blist = (int*)pa_rt_malloc((s->nbig ? s->nbig : 1) * sizeof(int));
+    s->d_fail = (int*)pa_rt_malloc(sizeof(int));
+    if (!s->d_bm_src || !s->d_bm_dst || !s->d_bm_chunk_blk || !s->d_bm_chunk_first || !s->d_boff || !s->d_slist ||
+        !s->d_blist || !s->d_fail ||
+        pa_rt_h2d(s->d_bm_src, bm.src, bm.n * sizeof(unsigned)) || pa_rt_h2d(s->d_bm_dst, bm.dst, bm.n * sizeof(unsigned)) ||
+        pa_rt_h2d(s->d_bm_chunk_blk, bm.chunk_blk, bm.nchunks * sizeof(int)) ||
+        pa_rt_h2d(s->d_bm_chunk_first, bm.chunk_first, (bm.nchunks + 1) * sizeof(unsigned)) ||
+        pa_rt_h2d(s->d_boff, bm.boff, ((size_t)np + 1) * sizeof(long long)) ||
+        pa_rt_h2d(s->d_slist, slist, (size_t)s->ns * sizeof(int)) || pa_rt_h2d(s->d_blist, blist, (size_t)s->nbig * sizeof(int))) {
+      rc = BJU_FAIL("uploading the band map (%zu entries) failed: %s", bm.n, pa_rt_error());
+      pa_rt_free(s->d_bm_src); pa_rt_free(s->d_bm_dst); pa_rt_free(s->d_bm_chunk_blk); pa_rt_free(s->d_bm_chunk_first);
+      pa_rt_free(s->d_boff); pa_rt_free(s->d_slist); pa_rt_free(s->d_blist); pa_rt_free(s->d_fail);
+      s->d_bm_src = s->d_bm_dst = s->d_bm_chunk_first = NULL; s->d_bm_chunk_blk = s->d_slist = s->d_blist = s->d_fail = NULL;
+      s->d_boff = NULL;
+    }
+  }
+  if (!rc) {
+    s->bm_n = bm.n; s->bm_nchunks = bm.nchunks; s->bm_bytes = pa_bj_band_map_bytes(&bm); s->btot = (size_t)bm.boff[np];
+    s->upd_map_s = pa_wtime() - t0;
+  }
+  free(slist); free(blist);
+  pa_bj_band_map_free(&bm);
+  return rc;
+}
+
+/* The band blocks: panel values up in one copy, bands assembled on the device through the map, then the
+ * factorisation and layout launches of the create on the create's lists, offsets and records.  Every kernel
+ * writes, for the same (rows, bandwidth, wide), the positions it wrote at the create -- k_bj_factor and
+ * k_bj_layout_big the in-band entries of the plain records, k_bj_g4_setup and k_bj_pairs every element of a
+ * block's second record -- so the zero background of the create survives and nothing is cleared.
+ * *spd_fail: 1 + local position of a non-positive pivot.  Returns non-zero with the error reported;
+ * *wrote tells whether the factor may have been written to by then. */
+static int bj_refactor_bands(pa_bj_t* s, const pa_operator_info_t* op, int* wrote, int* spd_fail) {
+  const size_t lnnz = (size_t)op->A.rowPtr[s->m];
+  double* d_pv = (double*)pa_rt_malloc((lnnz ? lnnz : 1) * sizeof(double));
+  double* d_band = (double*)pa_rt_malloc((s->btot ? s->btot : 1) * sizeof(double));
+  void* e0 = pa_rt_event_create();
+  void* e1 = pa_rt_event_create();
+  int rc = 0, fail = 0;
+  if (!d_pv || !d_band || !e0 || !e1)
+    rc = BJU_FAIL("no device memory for the panel values (%zu) and the bands (%zu entries): %s", lnnz, s->btot, pa_rt_error());
+  if (!rc) {
+    /* behind the applies already queued on the library stream; the copy returns when it has read A->val */
+    const double t0 = pa_wtime();
+    if (pa_rt_h2d(d_pv, op->A.val, lnnz * sizeof(double))) rc = BJU_FAIL("uploading the panel values failed: %s", pa_rt_error());
+    s->upd_copy_s = pa_wtime() - t0;
+  }
+  if (!rc) {
+    *wrote = 1;
+    if (pa_rt_event_record(e0) || pa_rt_memset(d_band, 0, s->btot * sizeof(double)) || pa_rt_memset(s->d_fail, 0, sizeof(int)) ||
+        pa_k_bj_band_assemble(s->d_bm_src, s->d_bm_dst, s->d_bm_chunk_blk, s->d_bm_chunk_first, s->bm_nchunks, s->d_boff,
+                              d_pv, d_band) ||
+        pa_k_bj_factor(s->d_slist, s->ns, s->wsmall, s->d_row0, s->d_nrows, s->d_bw, s->d_off, s->d_boff, d_band, s->d_Lf,
+                       s->d_Lb, s->d_invd_f, s->d_invd_b, s->d_fail) ||
+        pa_k_bj_factor_big(s->d_blist, s->nbig, s->wbig, s->wide_from, s->d_row0, s->d_nrows, s->d_bw, s->d_off, s->d_boff,
+                           d_band, s->d_Lf, s->d_Lb, s->d_invd_f, s->d_invd_b, s->d_fail) ||
+        pa_rt_d2h(&fail, s->d_fail, sizeof(int)))
+      rc = BJU_FAIL("factorising the diagonal blocks on the device failed: %s", pa_rt_error());
+    *spd_fail = fail;
+  }
+  if (!rc && fail == 0) {     /* the second layouts, from the new plain records */
+    if (s->d_Lg4 && bj_launch_g4(s)) rc = BJU_FAIL("k_bj_g4_setup failed");
+    if (!rc && s->d_Lf2 && bj_launch_pairs(s, s->class_pairs)) rc = BJU_FAIL("k_bj_pairs failed");
+    if (!rc && (pa_rt_event_record(e1) || pa_rt_sync())) rc = BJU_FAIL("%s", pa_rt_error());
+    if (!rc) s->upd_kernel_s = pa_rt_event_elapsed_s(e0, e1);
+  }
+  pa_rt_event_destroy(e0); pa_rt_event_destroy(e1);
+  pa_rt_free(d_pv); pa_rt_free(d_band);
+  return rc;
+}
+
+int preAlps_BlockJacobiUpdateValues(void) {
+  pa_bj_t* s = &g_bj;
+  const double t_all = pa_wtime();
+  if (!s->created) return BJU_FAIL("preconditioner not created");
+  const pa_operator_info_t* op = pa_operator_info();
+  if (!op) return BJU_FAIL("operator not built: it was freed since preAlps_BlockJacobiCreate (free and create instead)");
+  if (pa_operator_build_count() != s->op_build)
+    return BJU_FAIL("the operator was built again since preAlps_BlockJacobiCreate: free and create instead");
+  if (s->A_rowptr != op->A.rowPtr)
+    return BJU_FAIL("the preconditioner was not created from the operator's own panel (preAlps_OperatorGetA): free and create instead");
+  if (!s->dev_factor)
+    return BJU_FAIL("the preconditioner was created with PREALPS_BJ_FACTOR=host, its records come from the host "
+                    "Cholesky: free and create instead");
+  int rc = 0, wrote = 0, spd_fail = 0;
+  s->upd_copy_s = s->upd_kernel_s = 0.0;
+  if (s->np - s->nd_blocks > 0) {
+    rc = bj_ensure_band_map(s, op);
+    if (rc) return rc;                      /* (nothing of the factor has been touched) */
+    rc = bj_refactor_bands(s, op, &wrote, &spd_fail);
+    if (!rc && spd_fail > 0)
+      rc = BJU_FAIL("diagonal block is not SPD (global row %d)", s->row_off + s->h_map_f[spd_fail - 1] +
+                    s->h_row0[part_of_local_row(s->h_row0, s->h_nrows, s->np, spd_fail - 1)]);
+    if (rc && !wrote) return rc;
+  }
+  /* the blocks with the sparse factor: created again from the new panel, with the arguments of the create */
+  if (!rc && s->nd_blocks > 0) {
+    int* ndl = (int*)malloc((size_t)s->nd_blocks * sizeof(int));
+    int x = 0, nd_fail = -1;
+    if (!ndl) rc = BJU_FAIL("out of host memory");
+    else {
+      for (int q = 0; q < s->np; ++q) if (s->h_is_nd[q]) ndl[x++] = q;
+      const int r2 = pa_nd_create(&op->A, s->nd_blocks, ndl, s->h_row0, s->h_nrows, s->h_grow0, s->m, s->nd_bits, &nd_fail);
+      if (r2 == 2) rc = BJU_FAIL("diagonal block is not SPD (global row %d)", s->row_off + nd_fail);
+      else if (r2) rc = 1;
+      else { s->nd_rebuilt = s->nd_blocks; s->factor_bytes = 2.0 * 8.0 * (double)s->tot + pa_nd_factor_bytes(); }
+      free(ndl);
+    }
+  }
+  /* the records hold the new values in part, or not even a factor: there is no old preconditioner to go back to */
+  if (rc) { preAlps_BlockJacobiFree(); return rc; }
+  ++s->updates;
+  g_bj_values_epoch = pa_operator_values_epoch();
+  s->upd_total_s = pa_wtime() - t_all;
+  return 0;
+}
+
+/* "bj_updates", "bj_band_map_*", "bj_update_*", the two addresses: preAlps_hip_get_stat; 0 = key known */
+int pa_bj_update_stat(const char* key, double* value) {
+  const pa_bj_t* s = &g_bj;
+  const int on = s->created;
+  if (!strcmp(key, "bj_updates")) *value = on ? s->updates : 0;
+  else if (!strcmp(key, "bj_update_nd_rebuilt")) *value = on ? s->nd_rebuilt : 0;
+  else if (!strcmp(key, "bj_band_map_builds")) *value = on ? s->bm_builds : 0;
+  else if (!strcmp(key, "bj_band_map_entries")) *value = on && s->d_bm_src ? (double)s->bm_n : 0.0;
+  else if (!strcmp(key, "bj_band_map_bytes")) *value = on && s->d_bm_src ? (double)s->bm_bytes : 0.0;
+  else if (!strcmp(key, "bj_update_map_s")) *value = on ? s->upd_map_s : 0.0;
+  else if (!strcmp(key, "bj_update_copy_s")) *value = on ? s->upd_copy_s : 0.0;
+  else if (!strcmp(key, "bj_update_kernel_s")) *value = on ? s->upd_kernel_s : 0.0;
+  else if (!strcmp(key, "bj_update_total_s")) *value = on ? s->upd_total_s : 0.0;
+  else if (!strcmp(key, "bj_records_address")) *value = on ? (double)(size_t)s->d_Lf : 0.0;
+  else if (!strcmp(key, "bj_g4_address")) *value = on ? (double)(size_t)s->d_Lg4 : 0.0;
+  else return 1;
   return 0;
 }
 

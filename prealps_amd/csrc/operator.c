@@ -72,6 +72,7 @@ typedef struct {
 } pa_operator_t;
 
 static pa_operator_t g_op;
+static int g_op_builds;   /* operators built so far (pa_operator_build_count) */
 static double g_setup_build_s, g_setup_plan_s;   /* host seconds: scale/permute/halo lists, SpMM plan */
 
 const pa_operator_info_t* pa_operator_info(void) { return g_op.info.built ? &g_op.info : NULL; }
@@ -387,6 +388,7 @@ static int finish_peers(pa_operator_t* o, const int* recv_by_proc, int* asked_lo
 
 static int upload_operator(pa_operator_t* o, double t_build0) {
   pa_operator_info_t* in = &o->info;
+  ++g_op_builds;
   if (g_plan_only) { in->built = 1; return 0; }
   int rc = 0;
   if (o->nsend > 0) {
@@ -1047,6 +1049,7 @@ int preAlps_hip_prepare_operator(int enlFac) {
 
 /* ------------------------------------------------------ new values in place ---- */
 int pa_operator_values_epoch(void) { return g_op.values_epoch; }
+int pa_operator_build_count(void) { return g_op_builds; }
 /* the last update: host seconds of scaling vector + panel, host seconds of the copy of the panel values to the
  * device, device seconds of k_plan_set_values between two events; the seconds the last value map took (cut, upload) */
 static double g_update_host_s, g_update_copy_s, g_update_kernel_s, g_update_map_s;
@@ -1281,7 +1284,7 @@ int preAlps_hip_get_stat(const char* key, double* value) {
   else if (!strcmp(key, "bj_g4_last_ring")) *value = pa_bj_g4_last(0);
   else if (!strcmp(key, "bj_g4_last_bits")) *value = pa_bj_g4_last(1);
   else if (!strcmp(key, "bj_g4_last_pipelined")) *value = pa_bj_g4_last(2);
-  else return 1;
+  else return pa_bj_update_stat(key, value);
   return 0;
 }
 

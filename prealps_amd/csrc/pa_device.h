@@ -333,6 +333,10 @@ int pa_k_bj_factor(const int* list, int count, int wmax, const int* row0, const 
                    const long long* off, const long long* boff, const double* band, double* Lf, double* Lb,
                    double* invd_f, double* invd_b, int* fail);
 int pa_k_bj_apply(const pa_bj_plan_t* pl, int ts, const double* in, double* out);
+/* bj_refactor.hip: band[boff[chunk_blk[c]] + dst[e]] = pv[src[e]] for the entries e of every chunk c of the band
+ * map (bj_band_map.h); band zeroed beforehand, everything on the device. */
+int pa_k_bj_band_assemble(const unsigned* src, const unsigned* dst, const int* chunk_blk, const unsigned* chunk_first,
+                          size_t nchunks, const long long* boff, const double* pv, double* band);
 
 /* ---- sparse block solve for large diagonal blocks (nd.c) --------------------------------- */
 /* Supernodes of a nested-dissection Cholesky factor, all blocks of the process in one numbering.

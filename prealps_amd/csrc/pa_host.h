@@ -81,7 +81,9 @@ int pa_operator_gram_blocks(int ts);
 int pa_operator_pack_hint(int ts, const double* X, const int** pk_off, const int** pk_slot, double** sendbuf);
 
 int pa_operator_values_epoch(void);   /* 0 after a build, + 1 per preAlps_OperatorUpdateValues */
-int pa_bj_values_epoch(void);         /* that count at the last preAlps_BlockJacobiCreate */
+int pa_bj_values_epoch(void);         /* that count at the last preAlps_BlockJacobiCreate / preAlps_BlockJacobiUpdateValues */
+int pa_operator_build_count(void);    /* + 1 per operator built in this process: tells a rebuilt operator from the one a preconditioner was created on */
+int pa_bj_update_stat(const char* key, double* value);   /* the stats of preAlps_BlockJacobiUpdateValues by name; 1: unknown key */
 
 int pa_panel_stride(int enlFac);
 static inline int pa_desc_stride(const CPLM_Mat_Dense_t* A) { return A->info.lda; }

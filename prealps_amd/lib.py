@@ -82,7 +82,7 @@ EXPORTS = [
     "preAlps_hip_set_nd_precision", "preAlps_hip_set_band_precision",
     "preAlps_ECGInitializeMulti", "preAlps_ECGSystemResiduals", "preAlps_ECGFinalizeMulti", "preAlps_ECGSolveMulti",
     "preAlps_ECGInitializeGuess", "preAlps_ECGSolveGuess",
-    "preAlps_OperatorUpdateValues",
+    "preAlps_OperatorUpdateValues", "preAlps_BlockJacobiUpdateValues",
 ]
 
 _lib = None
@@ -133,6 +133,7 @@ def load():
     L.preAlps_OperatorBuild.argtypes = [C.c_char_p, C.c_int]
     L.preAlps_OperatorBuildFromCSR.argtypes = [C.c_int, pi, pi, pd, C.c_int, pi, C.c_int]
     L.preAlps_OperatorUpdateValues.argtypes = [pd]
+    L.preAlps_BlockJacobiUpdateValues.argtypes = []
     L.preAlps_OperatorGetA.argtypes = [C.POINTER(CPLM_Mat_CSR_t)]
     L.preAlps_OperatorGetSizes.argtypes = [pi, pi]
     L.preAlps_OperatorGetRowPosPtr.argtypes = [C.POINTER(pi), pi]

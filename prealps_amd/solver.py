@@ -306,15 +306,26 @@ class EcgProblem:
         self.has_precond = True
         self._precond_args = (nd_precision, band_precision)
 
+    def refactor_block_jacobi(self):
+        """preAlps_BlockJacobiUpdateValues: the factor of the current panel in place -- for band blocks the bits of
+        a fresh create_block_jacobi with the precision of the last one, at the same device addresses, without the
+        orders, the host assembly and the band upload; blocks with the sparse factor are created again.  A panel
+        that is no longer SPD raises and leaves no preconditioner (has_precond becomes False)."""
+        rc = self.L.preAlps_BlockJacobiUpdateValues()
+        if rc != 0:
+            self.has_precond = self.stat("bj_parts_local") > 0     # (freed by the library when the values are not SPD)
+        check(rc, "preAlps_BlockJacobiUpdateValues")
+
     def update_values(self, val, precond="keep"):
         """preAlps_OperatorUpdateValues: new values for the same pattern, partition and scaling flag, in the order of
         the val this problem was built from (the whole matrix); the operator becomes the one a fresh problem built from
         them would hold, bit for bit, without the set-up.  self.A and local_csr() show the new panel.
         precond="keep": the block-Jacobi factor of the old values stays, a lagged preconditioner for the new matrix
         (stat("bj_values_epoch") < stat("op_values_epoch") tells); "rebuild": it is freed and created again from the
-        new panel with the precision arguments of the last create_block_jacobi."""
-        if precond not in ("keep", "rebuild"):
-            raise ValueError("precond must be 'keep' or 'rebuild', not %r" % (precond,))
+        new panel with the precision arguments of the last create_block_jacobi; "refactor": refactor_block_jacobi(),
+        the same factor in place.  Without a preconditioner "rebuild" and "refactor" do what "keep" does."""
+        if precond not in ("keep", "rebuild", "refactor"):
+            raise ValueError("precond must be 'keep', 'rebuild' or 'refactor', not %r" % (precond,))
         if val is None:
             ptr = None
         else:
@@ -331,6 +342,8 @@ class EcgProblem:
             self.L.preAlps_BlockJacobiFree()
             self.has_precond = False
             self.create_block_jacobi(*self._precond_args)
+        elif precond == "refactor" and self.has_precond:
+            self.refactor_block_jacobi()
 
     def reference_rhs(self):
         rhs = np.zeros(self.m)
