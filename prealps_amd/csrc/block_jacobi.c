@@ -429,12 +429,14 @@ static int bj_record_offsets(pa_bj_t* s, bj_build_t* B) {
     if (B->wide_from > 64 * maxR - 64) B->wide_from = 64 * maxR - 64;
   }
   int maxw = 0, maxw_all = 0;
+  long long maxrec = 0;
   B->off[0] = 0;
   for (int q = 0; q < np; ++q) {
     const int w = B->bw[q];
     const long long reclen = w > B->wide_from ? pa_bj_wide_window(w) : ((w + 2) & ~1);
     if (w > maxw_all) maxw_all = w;
     if (B->is_nd[q]) { B->off[q + 1] = B->off[q]; ++B->nnd; continue; }     /* no band records: sparse factor */
+    if (w <= B->wide_from && reclen > maxrec) maxrec = reclen;
     if (B->dev_factor) ++B->ndev;
     B->off[q + 1] = B->off[q] + (long long)B->nrows[q] * reclen;
     if (w > maxw) maxw = w;
@@ -444,7 +446,9 @@ static int bj_record_offsets(pa_bj_t* s, bj_build_t* B) {
     return BJ_FAIL("block-Jacobi: a diagonal block has bandwidth %d after reordering; the workgroup-resident "
                    "solve supports up to 4032 -- use more (smaller) subdomains", maxw);
   const size_t tot = B->tot = (size_t)B->off[np];
-  const size_t pad = 256; /* the last LDS-DMA piece of a chunk may read up to 1 KiB past it */
+  /* A narrow block is streamed in chunks of 8 steps, whole KiB each: the last chunk of a block whose rows are no
+   * multiple of 8 reads up to 7 records and 1 KiB beyond the block -- behind the last block, into this slack. */
+  const size_t pad = 256 + 8 * (size_t)maxrec;
   s->d_invd_f = (double*)pa_rt_malloc((size_t)(m ? m : 1) * sizeof(double));
   s->d_invd_b = (double*)pa_rt_malloc((size_t)(m ? m : 1) * sizeof(double));
   s->d_Lf = (double*)pa_rt_malloc((tot + pad) * sizeof(double));

@@ -178,3 +178,71 @@ def box_partition_nodes(nn, box, dofs=3):
     ni, nj, nk = -(-nx // bi), -(-ny // bj), -(-nz // bk)
     part = ((k // bk) * nj + (j // bj)) * ni + (i // bi)
     return np.repeat(part, dofs).astype(np.int32), ni * nj * nk
+
+
+def band_blocks_csr(blocks, seed, grading=0.0, shuffle=False, coupling=None):
+    """Block-diagonal SPD matrix whose diagonal blocks have prescribed rows and bandwidth: `blocks` is a list of
+    (rows b, bandwidth w), a w above b - 1 is clipped to b - 1.  Block q is L0 L0^T, symmetrised exactly (the upper
+    triangle is the mirror of the lower one, bit for bit), L0 lower banded with every in-band entry nonzero:
+    sub-diagonal magnitudes uniform in [0.25, 1] / sqrt(w + 1) with random sign, diagonal uniform in [1, 2] for
+    grading = 0 and 10 ** U(-grading / 4, grading / 4) otherwise.  The band of the block is full and exactly w, so
+    no ordering of it is narrower than the natural one.
+    shuffle: a random symmetric permutation inside every block (the rows stay, the band does not).
+    coupling = (per_row, mag): per_row random entries c, |c| uniform in [mag / 2, mag] with random sign, from every
+    row to rows of other blocks, mirrored, with |c| added to both diagonal entries concerned: every such 2 x 2
+    contribution is positive semidefinite and no entry inside a block other than its diagonal changes.
+    Returns int32 rowptr, int32 colind, float64 val (sorted columns), the int32 part vector (rows of block q are
+    contiguous and in part q) and the number of parts."""
+    rng = np.random.default_rng(seed)
+    blocks = [(int(b), min(int(w), int(b) - 1)) for b, w in blocks]
+    if not blocks or any(b < 1 or w < 0 for b, w in blocks):
+        raise ValueError("blocks must be a non-empty list of (rows >= 1, bandwidth >= 0)")
+    P = len(blocks)
+    N = sum(b for b, _ in blocks)
+    rows, cols, vals = [], [], []
+    r0 = 0
+    for b, w in blocks:
+        i, j = np.indices((b, b))
+        inband = (i - j <= w) & (i > j)
+        L0 = np.zeros((b, b))
+        n = int(inband.sum())
+        L0[inband] = rng.uniform(0.25, 1.0, n) / np.sqrt(w + 1.0) * rng.choice([-1.0, 1.0], n)
+        if grading:
+            L0[np.arange(b), np.arange(b)] = 10.0 ** rng.uniform(-grading / 4.0, grading / 4.0, b)
+        else:
+            L0[np.arange(b), np.arange(b)] = rng.uniform(1.0, 2.0, b)
+        G = L0 @ L0.T
+        A = np.tril(G) + np.tril(G, -1).T
+        keep = np.abs(i - j) <= w
+        if shuffle:
+            p = rng.permutation(b)
+            A, keep = A[np.ix_(p, p)], keep[np.ix_(p, p)]
+        rows.append(r0 + i[keep])
+        cols.append(r0 + j[keep])
+        vals.append(A[keep])
+        r0 += b
+    rows, cols, vals = np.concatenate(rows), np.concatenate(cols), np.concatenate(vals)
+    part = np.repeat(np.arange(P, dtype=np.int32), [b for b, _ in blocks])
+    if coupling is not None:
+        per_row, mag = int(coupling[0]), float(coupling[1])
+        if P < 2:
+            raise ValueError("coupling needs at least two blocks")
+        ci = np.repeat(np.arange(N, dtype=np.int64), per_row)
+        cj = rng.integers(0, N, ci.size)
+        c = rng.uniform(0.5 * mag, mag, ci.size) * rng.choice([-1.0, 1.0], ci.size)
+        other = part[ci] != part[cj]
+        lo, hi, c = np.minimum(ci, cj)[other], np.maximum(ci, cj)[other], c[other]
+        key, first = np.unique(lo * N + hi, return_index=True)          # one entry per pair of rows
+        lo, hi, c = lo[first], hi[first], c[first]
+        diag = np.zeros(N)
+        np.add.at(diag, lo, np.abs(c))
+        np.add.at(diag, hi, np.abs(c))
+        vals[rows == cols] += diag[rows[rows == cols]]
+        rows = np.concatenate([rows, lo, hi])
+        cols = np.concatenate([cols, hi, lo])
+        vals = np.concatenate([vals, c, c])
+    order = np.lexsort((cols, rows))
+    rows, cols, vals = rows[order], cols[order], vals[order]
+    rowptr = np.zeros(N + 1, dtype=np.int64)
+    rowptr[1:] = np.cumsum(np.bincount(rows, minlength=N))
+    return rowptr.astype(np.int32), cols.astype(np.int32), np.ascontiguousarray(vals, dtype=np.float64), part, P

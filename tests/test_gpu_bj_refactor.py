@@ -32,6 +32,15 @@ def _two_cubes(n):
     return sp.csr_matrix(sp.kron(sp.kron(T2, I), I) + sp.kron(sp.kron(I2, T), I) + sp.kron(sp.kron(I2, I), T))
 
 
+# (rows, band) per block: 1 .. 192 rows at bands 0 .. 64 in one launch; 256 rows, the last index of the packed row map,
+# at bands 40 and 112 beside small blocks; band 129 (default dispatch: one workgroup per block, k_bj_factor_big)
+BAND_BLOCKS = {
+    "band-mixed": [(b, w) for w in (64, 0, 33, 5, 32) for b in (1, 192, 2, 129, 3, 128, 4, 127, 5, 65, 15, 64, 16, 63, 17, 191)],
+    "band-256": 2 * [(256, 40), (1, 0), (130, 112), (256, 112), (16, 40), (130, 40), (2, 1)],
+    "band-129": [(192, 129), (130, 129), (300, 129), (500, 129)],
+}
+
+
 @functools.lru_cache(maxsize=None)
 def _matrix(kind):
     """rowptr, colind, val, val2, number of parts, partition vector."""
@@ -56,6 +65,8 @@ def _matrix(kind):
     elif kind == "poisson12-mixed":                   # one part of 864 rows, six of 144
         rp, ci, v = O.as_csr(O.poisson3d(12))
         P, part = 7, np.concatenate([np.zeros(864, dtype=np.int32), np.repeat(np.arange(1, 7, dtype=np.int32), 144)])
+    elif kind in BAND_BLOCKS:                         # synthetic blocks with prescribed rows and a full band
+        rp, ci, v, part, P = gen.band_blocks_csr(BAND_BLOCKS[kind], seed=len(kind), grading=2.0)
     else:
         raise KeyError(kind)
     return rp, ci, v, _new_values(rp, ci, v), P, part
@@ -175,6 +186,34 @@ def test_a_shard_with_halo_columns():
     finally:                                              # one process, no hooks, for the tests that follow
         L.preAlps_hip_set_world(0, 1)
         L.preAlps_hip_set_comm(prealps_amd.lib.ALLREDUCE_FN(), prealps_amd.lib.EXCHANGE_FN(), None)
+
+
+# ---- synthetic band blocks: unequal rows in one class, 256 rows, just outside the one-copy records ------------------
+@pytest.mark.parametrize("t", [4, 8, 16])
+@pytest.mark.parametrize("kind", ["band-mixed", "band-256"])
+def test_unequal_band_blocks_have_the_bits_of_a_fresh_create(kind, t, monkeypatch):
+    """k_bj_band_assemble and k_bj_factor writing into old records of blocks of 1 .. 192 (256) rows side by side."""
+    monkeypatch.setenv("PREALPS_BJ_ND", "0")
+    monkeypatch.setenv("PREALPS_BJ_WIDE_FROM", "448")
+    stats = _refactor_case(kind, t)
+    assert stats["bj_max_bandwidth"] == max(min(w, b - 1) for b, w in BAND_BLOCKS[kind])
+    assert stats["bj_g4_bytes"] > 0 and stats["bj_pairs_bytes"] == 0 and stats["bj_band_precision"] == 64
+
+
+@pytest.mark.parametrize("kind", ["band-mixed", "band-256"])
+def test_unequal_band_blocks_with_single_precision_records(kind, monkeypatch):
+    monkeypatch.setenv("PREALPS_BJ_ND", "0")
+    monkeypatch.setenv("PREALPS_BJ_WIDE_FROM", "448")
+    stats = _refactor_case(kind, 4, create_kw={"band_precision": "single"})
+    assert stats["bj_band_precision"] == 32
+
+
+@pytest.mark.parametrize("t", [4, 8])
+def test_band_129_just_outside_the_one_copy_records(t, monkeypatch):
+    """Default dispatch, few blocks: band 129 has window-slot records, k_bj_factor_big and k_bj_layout_big refresh them."""
+    monkeypatch.setenv("PREALPS_BJ_ND", "0")
+    stats = _refactor_case("band-129", t)
+    assert stats["bj_max_bandwidth"] == 129 and stats["bj_g4_bytes"] == 0 and stats["bj_pairs_bytes"] == 0
 
 
 # ---- the map is cut once ----------------------------------------------------------------------------------------
