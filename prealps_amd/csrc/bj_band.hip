@@ -2,7 +2,7 @@
 // (gfx950): the set-up kernels (band Cholesky of the diagonal blocks, record layout, COO scatter,
 // paired records), the apply kernels (k_bj_apply, k_bj_apply_pairs, k_bj_mfma, k_bj_wide), their
 // launchers and the dispatch by bandwidth class, pa_k_bj_apply.  The one-copy records of panels of up
-// to 4 columns are bj_g4.hip; the dense panel kernels of the ECG iteration are kernels.hip.
+// to 4 columns are bj_g4.hip; the dense panel kernels of the ECG iteration are dense_*.hip.
 #include "kernels_common.h"
 
 namespace {
@@ -961,7 +961,7 @@ static int bj_launch_ch(const pa_bj_plan_t* pl, int R, int wmax, const int* list
   int per_wave = nbuf * cbuf;
   int waves = (160 * 1024) / (per_wave * 8);
   if (waves > 4) waves = 4;
-  if (waves < 1) { snprintf(g_kerr, sizeof(g_kerr), "block-Jacobi band too wide for LDS (R=%d)", R); return 1; }
+  if (waves < 1) { pa_rt_set_error("block-Jacobi band too wide for LDS (R=%d)", R); return 1; }
   const size_t lds = (size_t)waves * per_wave * 8;
   const int units = count * (XS / TS);   // one wavefront per (subdomain, column group)
   const int blocks = (units + waves - 1) / waves;
@@ -1013,7 +1013,7 @@ static int bj_launch_ch(const pa_bj_plan_t* pl, int R, int wmax, const int* list
   switch (R) {
     BJ_CASE(1) BJ_CASE(2) BJ_CASE(3) BJ_CASE(4) BJ_CASE(5) BJ_CASE(6) BJ_CASE(7) BJ_CASE(8)
     default:
-      snprintf(g_kerr, sizeof(g_kerr), "block-Jacobi bandwidth class R=%d unsupported", R);
+      pa_rt_set_error("block-Jacobi bandwidth class R=%d unsupported", R);
       return 1;
   }
 #undef BJ_CASE
@@ -1066,10 +1066,9 @@ static int bj_launch_wide(const pa_bj_plan_t* pl, int wmax, const int* list, int
   const int W = pa_bj_wide_window(wmax);
   const int nw = (W + 64 * R - 1) / (64 * R);
   if (nw > 16 || TS * R > 16) {
-    snprintf(g_kerr, sizeof(g_kerr),
-             "block-Jacobi: bandwidth %d is too wide for panel stride %d (window %d rows); use more subdomains",
-             wmax, TS, W);
-    fprintf(stderr, "[prealps_hip] %s\n", g_kerr);
+    pa_rt_set_error("block-Jacobi: bandwidth %d is too wide for panel stride %d (window %d rows); use more subdomains",
+                    wmax, TS, W);
+    fprintf(stderr, "[prealps_hip] %s\n", pa_rt_error());
     return 1;
   }
   if constexpr (TS * R <= 16) {

@@ -44,7 +44,7 @@ extern "C" int pa_k_bj_band_assemble(const unsigned* src, const unsigned* dst, c
                                      const unsigned* chunk_first, size_t nchunks, const long long* boff,
                                      const double* pv, double* band) {
   if (nchunks == 0) return 0;
-  if (nchunks > 0x7fffffffu) { snprintf(g_kerr, sizeof(g_kerr), "k_bj_band_assemble: %zu chunks", nchunks); return 1; }
+  if (nchunks > 0x7fffffffu) { pa_rt_set_error("k_bj_band_assemble: %zu chunks", nchunks); return 1; }
   const int cus = pa_rt_num_cus() > 0 ? pa_rt_num_cus() : 256;
   size_t blocks = nchunks;
   if (blocks > (size_t)8 * cus) blocks = (size_t)8 * cus;      // eight workgroups per CU, the rest by the stride

@@ -1064,7 +1064,7 @@ int preAlps_BlockJacobiApply(CPLM_Mat_Dense_t* A_in, CPLM_Mat_Dense_t* B_out) {
   B_out->info.n = A_in->info.n; B_out->info.N = A_in->info.N;
   B_out->info.nval = B_out->info.m * B_out->info.n;
   pa_time_begin(PA_T_PRECOND);
-  if (pa_k_bj_apply(&s->plan, ts, A_in->val, B_out->val)) return PA_FAIL("block-Jacobi kernel launch failed");
+  if (pa_k_bj_apply(&s->plan, ts, A_in->val, B_out->val)) return PA_FAIL("block-Jacobi kernel launch failed: %s", pa_rt_error());
   if (s->nd_blocks > 0 && pa_nd_apply(ts, A_in->val, B_out->val)) return 1;
   pa_time_end(PA_T_PRECOND);
   return 0;

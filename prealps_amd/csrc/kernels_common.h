@@ -1,6 +1,7 @@
 // kernels_common.h -- what the kernel translation units share: launch macro, the library stream,
 // launch-error report, panel row loads / stores and lane moves.  (Included inside each unit: every
-// unit has its own copy of the anonymous-namespace helpers.)
+// unit has its own copy of the anonymous-namespace helpers; none of them holds state -- a refusal or a
+// failed launch is reported through pa_rt_set_error, the one error text of the library's device side.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -19,12 +20,12 @@ constexpr int GRAM_WIDE_BLOCKS = 1024;    // Gram kernels of 8 / 16-column panel
 
 inline hipStream_t cur_stream() { return (hipStream_t)pa_rt_stream(); }
 
-char g_kerr[256];
-int kfail(const char* what) {
+// a failed launch, reported where the host code looks: pa_rt_error() (runtime.hip)
+inline int kfail(const char* what) {
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) return 0;
-  snprintf(g_kerr, sizeof(g_kerr), "%s: %s", what, hipGetErrorString(e));
-  fprintf(stderr, "[prealps_hip] kernel launch failed: %s\n", g_kerr);
+  pa_rt_set_error("%s: %s", what, hipGetErrorString(e));
+  fprintf(stderr, "[prealps_hip] kernel launch failed: %s\n", pa_rt_error());
   return 1;
 }
 
@@ -130,5 +131,5 @@ __device__ __forceinline__ void quad_transpose4(double (&a)[4], int c) {
     case 4: { constexpr int TS_ = 4; CALL; } break;   \
     case 8: { constexpr int TS_ = 8; CALL; } break;   \
     case 16: { constexpr int TS_ = 16; CALL; } break; \
-    default: snprintf(g_kerr, sizeof(g_kerr), "unsupported panel stride %d", ts); return 1; \
+    default: pa_rt_set_error("unsupported panel stride %d", ts); return 1; \
   }

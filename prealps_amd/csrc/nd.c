@@ -654,16 +654,16 @@ static int nd_numeric_device(pa_nd_t* S, const nd_block_t* B, int nblk, const in
         nd_tiles_build(&ll, ids, cnt, h_n, h_m, 1) || nd_tiles_build(&rc_t, ids, cnt, h_n, h_m, 0))
       rc = PA_FAIL("block factorisation: work lists of level %d: %s", h, pa_rt_error());
     const int* cf = S->f_front[h]; const int* cr = S->f_row0[h]; const int nch = S->f_count[h];
-    if (!rc && pa_k_ndf_assemble(&a, ll.f, ll.ti, ll.tj, ll.n, d_ids, cnt)) rc = PA_FAIL("block factorisation: kernel launch failed");
+    if (!rc && pa_k_ndf_assemble(&a, ll.f, ll.ti, ll.tj, ll.n, d_ids, cnt)) rc = PA_FAIL("block factorisation: kernel launch failed: %s", pa_rt_error());
     for (int jb = 0; jb < nmax && !rc; jb += 64)
       if (pa_k_ndf_potrf(&a, d_ids, cnt, jb) || pa_k_ndf_trsm(&a, cf, cr, nch, jb, 0) || pa_k_ndf_update(&a, ll.f, ll.ti, ll.tj, ll.n, jb, 0))
-        rc = PA_FAIL("block factorisation: kernel launch failed");
-    if (!rc && pa_k_ndf_pinit(&a, cf, cr, nch)) rc = PA_FAIL("block factorisation: kernel launch failed");
+        rc = PA_FAIL("block factorisation: kernel launch failed: %s", pa_rt_error());
+    if (!rc && pa_k_ndf_pinit(&a, cf, cr, nch)) rc = PA_FAIL("block factorisation: kernel launch failed: %s", pa_rt_error());
     for (int jb = ((nmax - 1) / 64) * 64; jb >= 0 && !rc; jb -= 64)
       if (pa_k_ndf_trsm(&a, cf, cr, nch, jb, 1) || pa_k_ndf_update(&a, rc_t.f, rc_t.ti, rc_t.tj, rc_t.n, jb, 1))
-        rc = PA_FAIL("block factorisation: kernel launch failed");
+        rc = PA_FAIL("block factorisation: kernel launch failed: %s", pa_rt_error());
     if (!rc && (pa_k_ndf_finalize(&a, rc_t.f, rc_t.ti, rc_t.tj, rc_t.n) || pa_k_ndf_check(&a, d_ids, cnt, nmax)))
-      rc = PA_FAIL("block factorisation: kernel launch failed");
+      rc = PA_FAIL("block factorisation: kernel launch failed: %s", pa_rt_error());
     tm0 = pa_wtime();
     if (!rc && pa_rt_sync()) rc = PA_FAIL("block factorisation of level %d failed: %s", h, pa_rt_error());
     t_sync += pa_wtime() - tm0;
@@ -968,7 +968,7 @@ int pa_nd_apply(int ts, const double* in, double* out) {
   }
   S->plan.contrib = S->d_contrib;
   S->plan.Y = S->d_Y;
-  if (pa_k_nd_apply(&S->plan, ts, in, out)) return PA_FAIL("block-solve kernel launch failed");
+  if (pa_k_nd_apply(&S->plan, ts, in, out)) return PA_FAIL("block-solve kernel launch failed: %s", pa_rt_error());
   return 0;
 }
 

@@ -32,7 +32,8 @@ inline hipStream_t cur_stream() { return (hipStream_t)pa_rt_stream(); }
 int kfail(const char* what) {
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) return 0;
-  fprintf(stderr, "[prealps_hip] kernel launch failed: %s: %s\n", what, hipGetErrorString(e));
+  pa_rt_set_error("%s: %s", what, hipGetErrorString(e));
+  fprintf(stderr, "[prealps_hip] kernel launch failed: %s\n", pa_rt_error());
   return 1;
 }
 

@@ -1,6 +1,6 @@
 /*
  * pa_device.h -- the thin C-ABI shim between the C host code (ecg.c,
- * operator.c, block_jacobi.c) and the HIP side (runtime.hip, kernels.hip,
+ * operator.c, block_jacobi.c) and the HIP side (runtime.hip, dense_*.hip,
  * bj_band.hip, ...).
  * Host code never includes a HIP header; device code never sees a preAlps
  * struct.  Panels are row-interleaved: element (i, j) at p[i * ts + j].
@@ -20,6 +20,9 @@ void pa_rt_set_stream(void* s);
 void* pa_rt_stream(void);
 int pa_rt_sync(void);
 const char* pa_rt_error(void);
+/* The one error text of the device side: the runtime calls and every kernel unit (a launcher that refuses its
+ * arguments, a failed launch) leave their reason here, where PA_CHECK and the host's pa_rt_error() calls read it. */
+void pa_rt_set_error(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 void* pa_rt_malloc(size_t bytes);
 void pa_rt_free(void* d);
 void* pa_rt_host_alloc(size_t bytes);
@@ -215,6 +218,9 @@ int pa_k_update_z_pack(int ts, const int* pk_off, const int* pk_slot, double* se
  * `host`, pa_k_update_z with note_host) also writes host[2] = seq behind them (seq != 0; one-shot), for
  * a host that polls that word instead of waiting for an event. */
 void pa_k_note_seq(double seq);
+/* Takes that number for a launch that writes to `host` (0 when host is NULL or none was set): the one copy of the
+ * state, for the launchers of every kernel unit. */
+double pa_k_take_note_seq(const double* host);
 /* dst(:, :nc) = src(:, :nc) (mkl_domatcopy, ecg.c:358,521-523). */
 int pa_k_copy_cols(int m, int ts, int nc, const double* src, double* dst);
 /* A(:, :t) <- A(:, :t) Q, Q is t x t column-major (the effect of LAPACKE_dormqr

@@ -2,6 +2,7 @@
 // gfx950 only; no fallback: every failure is reported to the C host code,
 // which aborts like the reference's CPLM_Abort.
 #include <hip/hip_runtime.h>
+#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include "pa_device.h"
@@ -31,6 +32,12 @@ int fail(hipError_t e, const char* what) {
 extern "C" {
 
 const char* pa_rt_error(void) { return g_err; }
+void pa_rt_set_error(const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  va_end(ap);
+}
 int pa_rt_ready(void) { return g_ready ? 1 : 0; }
 int pa_rt_num_cus(void) { return g_cus; }
 /* devices visible to this process (does not select one) */

@@ -30,7 +30,7 @@ __global__ __launch_bounds__(WG) void k_plan_set_values(const u2v* __restrict__ 
 
 extern "C" int pa_k_plan_set_values(const unsigned* map, const double* pv, double* val, size_t n) {
   if (n == 0) return 0;
-  if (n & 1) { snprintf(g_kerr, sizeof(g_kerr), "k_plan_set_values: odd slot count %zu", n); return 1; }
+  if (n & 1) { pa_rt_set_error("k_plan_set_values: odd slot count %zu", n); return 1; }
   const size_t npairs = n / 2;
   const int cus = pa_rt_num_cus() > 0 ? pa_rt_num_cus() : 256;
   size_t blocks = (npairs + WG - 1) / WG;

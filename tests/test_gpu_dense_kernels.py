@@ -127,3 +127,63 @@ def test_permute_solve(panels, m, n, t):
         ref[:, :t] = ref[:, :t] @ np.linalg.inv(U)
     np.testing.assert_allclose(outs[0], ref, rtol=1e-11, atol=1e-11 * np.abs(ref).max())
     np.testing.assert_array_equal(outs[0], outs[1])
+
+
+def test_gram_finish_refusal_is_reported_and_harmless(panels):
+    """pa_k_gram_finish refuses a [W ; G^T] request whose leading dimension is not t + T on the host, before the
+    finishing launch: return code 1, the reason in pa_rt_error(), and the same buffers serve a valid call after it."""
+    L = panels.L
+    m, t = 64, 4
+    L.pa_rt_error.restype = C.c_char_p
+    L.pa_rt_malloc.restype = C.c_void_p
+    L.pa_rt_malloc.argtypes = [C.c_size_t]
+    L.pa_rt_free.argtypes = [C.c_void_p]
+    L.pa_rt_free.restype = None
+    L.pa_rt_memset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+    L.pa_rt_h2d.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.pa_rt_d2h.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    vp, ci = C.c_void_p, C.c_int
+    L.pa_k_gram.argtypes = [ci, ci, vp, vp, vp, vp, C.POINTER(ci)]
+    L.pa_k_gram_finish.argtypes = [ci, ci, vp, vp, vp, vp, ci, ci, ci, vp, ci, ci, ci, vp, vp, vp]
+    rng = np.random.default_rng(64 + t)
+    A0, A1 = rng.standard_normal((m, t)), rng.standard_normal((m, t))      # (row-interleaved panels of stride t)
+    bufs = []
+
+    def dev(nbytes, src=None):
+        d = L.pa_rt_malloc(nbytes)
+        assert d
+        bufs.append(d)
+        panels.check(L.pa_rt_memset(d, 0, nbytes), "memset")
+        if src is not None:
+            panels.check(L.pa_rt_h2d(d, src.ctypes.data, src.nbytes), "h2d")
+        return d
+
+    def host(d, shape):
+        h = np.zeros(shape, order="F")
+        panels.check(L.pa_rt_d2h(h.ctypes.data, d, h.nbytes), "d2h")
+        return h
+
+    try:
+        d0, d1 = dev(A0.nbytes, A0), dev(A1.nbytes, A1)
+        part = dev(L.pa_gram_max_blocks() * 2 * t * t * 8)
+        out, mu, alpha, info = dev(2 * t * t * 8), dev(t * t * 8), dev(t * t * 8), dev(8)
+        nblk = ci(0)
+        panels.check(L.pa_k_gram(m, t, d0, d1, d0, part, C.byref(nblk)), "gram")
+        assert nblk.value >= 1
+        rc = L.pa_k_gram_finish(m, t, d0, d1, d0, part, t, t, t, out, 2 * t + 1, t, t, mu, alpha, info)
+        assert rc == 1
+        assert "layout expected" in L.pa_rt_error().decode()
+        assert L.pa_k_gram_finish(m, t, d0, d1, d0, part, t, t, t, out, 2 * t, t, t, mu, alpha, info) == 0
+        panels.check(L.preAlps_hip_sync(), "sync")
+        ref = np.hstack([A0, A1]).T @ A0                      # [W ; G^T], W = A0^T A0
+        np.testing.assert_allclose(host(out, (2 * t, t)), ref, rtol=1e-12, atol=1e-12 * np.abs(ref).max())
+        U = np.linalg.cholesky(ref[:t]).T
+        ref_alpha = np.linalg.solve(U.T, ref[t:].T)
+        status = np.zeros(2, dtype=np.int32)
+        panels.check(L.pa_rt_d2h(status.ctypes.data, info, 8), "d2h")
+        assert status[0] == 0
+        np.testing.assert_allclose(np.triu(host(mu, (t, t))), U, rtol=1e-11, atol=1e-11 * np.abs(U).max())
+        np.testing.assert_allclose(host(alpha, (t, t)), ref_alpha, rtol=1e-11, atol=1e-11 * np.abs(ref_alpha).max())
+    finally:
+        for d in bufs:
+            L.pa_rt_free(d)

@@ -1,0 +1,41 @@
+"""The kernel units report through the runtime's error channel: a pa_k_* launcher that refuses its arguments
+returns 1 and leaves its reason where pa_rt_error() finds it -- and so every PA_CHECK and PA_FAIL of the host
+code, whose text preAlps_hip_last_error() hands on.  The three launchers here refuse before any HIP call (no
+stream is looked up, nothing is launched), so the checks need no GPU."""
+import ctypes as C
+
+import pytest
+
+import prealps_amd
+
+
+@pytest.fixture(scope="module")
+def L():
+    lib = prealps_amd.load()
+    lib.pa_rt_error.restype = C.c_char_p
+    return lib
+
+
+def _refused(L, rc, reason):
+    assert rc == 1
+    assert reason in L.pa_rt_error().decode()
+
+
+def test_multi_start_reports_systems_that_do_not_fit(L):
+    nblk = C.c_int(-1)
+    rc = L.pa_k_multi_start(64, 4, 3, 2, None, 64, None, None, None, C.byref(nblk))
+    _refused(L, rc, "pa_k_multi_start: 3 systems of 2 columns do not fit a panel of stride 4")
+    assert nblk.value == -1
+
+
+def test_update_xrz_reports_the_panel_width(L):
+    nblk = C.c_int(-1)
+    rc = L.pa_k_update_xrz(64, 8, 4, None, None, None, None, None, None, None, None, None, C.byref(nblk),
+                           None, None, 8, None)
+    _refused(L, rc, "pa_k_update_xrz: 4-column panels with lazy normalisation only")
+    assert nblk.value == -1
+
+
+def test_rowsum_reports_an_unsupported_stride(L):
+    rc = L.pa_k_rowsum(64, 3, 3, None, None)
+    _refused(L, rc, "unsupported panel stride 3")
