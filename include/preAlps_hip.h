@@ -263,6 +263,66 @@ int preAlps_ECGSolveGuess(preAlps_ECG_t* ecg, int nrhs, const double* rhs, int l
                           const double* x0, int ldx0, double* sol, int ldsol,
                           double* res_hist, int* bs_hist, double* sys_hist, double* sys_normb,
                           double* sys_res0, int max_hist, int* n_hist);
+/* ---- the caller's own system: original order, scale and residual norm -------------------------------------------
+ * Every entry above works in the operator's internal space: it takes the right-hand side and returns the solution of
+ * A' = P D A D P^T, where P groups the rows part by part (preAlps_OperatorGetPermPtr: perm[new] = old) and D = diag(d),
+ * d_i = sqrt(1 / max_j |a_ij|), is the scaling of preAlps_OperatorBuild and of preAlps_OperatorBuildFromCSR with
+ * scale != 0.  The entries below solve A x = b as the caller stated it.  They are for one process, where N = m.
+ *   preAlps_OperatorGetScalingPtr: the vector d, N doubles, entry i for row i of the matrix the operator was built
+ * from (the caller's order).  The array is library-owned; preAlps_OperatorUpdateValues writes the new vector into the
+ * same allocation (after its last refusal: a refused update leaves the old one), preAlps_OperatorFree releases it.
+ * *d = NULL with *n = N: the operator is unscaled.  Works in plan-only mode and for any number of processes (every
+ * process holds the whole vector).
+ *   preAlps_ECGSolveSystem is preAlps_ECGSolveGuess around a gather and a scatter.  b, x0 (may be NULL: no guess) and
+ * x hold N rows in the order and units of that matrix -- the CSR arrays of preAlps_OperatorBuildFromCSR, the rows of
+ * the file -- column major, nrhs columns, ldb, ldx0, ldx >= N.  One launch forms b' = (D b)[perm] and x0' =
+ * (D^-1 x0)[perm] (a true division) in the staging arrays of the start and leaves ||b_j||^2 in the caller's units; one
+ * launch at the end writes x[perm[i]] = d[perm[i]] * (the solution of the scaled system); b and x0 are only read.
+ * The row map on the device (12 bytes per row: perm and d[perm]) is cut at the first call and again after
+ * preAlps_OperatorUpdateValues (stats "op_system_map_builds", "op_system_map_bytes").
+ *   flags: PREALPS_SYS_DEVICE: b, x0 and x are device pointers.  They are read and written on the library stream and
+ * the entry returns after that stream has drained, as the solve loops do; the caller orders their own stream before
+ * the call.  Without it they are host arrays.
+ *   PREALPS_SYS_STOP_ORIGINAL: the iteration goes on while ||b_j - A x_j|| > tol * ||b_j|| for some j, both norms in
+ * the caller's units (and iter < maxIter, bs > 0; a NaN stops it), for one system as for several.  The left side is
+ * the recurrence residual: the sum of system j's columns of R is that system's whole residual in the scaled space
+ * (every update keeps sum_c R(:, c) = b'_j - A' sum_c X(:, c)), and divided row by row by d[perm] it is b_j - A x_j.
+ * Its norm is the norm itself, not the sqrt(s) bound of the split.  It costs one more pass over the R panel and one
+ * small launch per iteration.  Without the flag the test is the library's: ||D (b_j - A x_j)|| split over its columns
+ * against ||D b_j||, the test of preAlps_ECGSolveGuess; with a graded coefficient the two differ by orders of
+ * magnitude.  ecg->res and ecg->normb stay the scaled Frobenius norms under both, and so does res_hist.
+ *   sys_hist (may be NULL; entry i of system j at sys_hist[i + j * max_hist]) and sys_normb (may be NULL) are in the
+ * metric of the stopping test.  sys_res (may be NULL) always receives the nrhs recurrence residual norms in the
+ * caller's units at the end, from one more launch after the loop; with PREALPS_SYS_STOP_ORIGINAL that is the last row
+ * of sys_hist bit for bit.
+ *   Without PREALPS_SYS_STOP_ORIGINAL the iterate, the histories and the iteration count are those of
+ * preAlps_ECGSolveGuess (x0 == NULL: preAlps_ECGSolveMulti) on (D b)[perm] and (D^-1 x0)[perm], bit for bit, and
+ * x[perm[i]] is d[perm[i]] times its solution.  The start always goes through the device kernels of several systems
+ * (pa_k_multi_start, or the three of a guess), also for one system without a guess; for that case the scaled
+ * right-hand side comes back to the host once (m doubles) so that ecg->normb is summed as _preAlps_ECGReset sums it.
+ *   A guess under which every system already meets its threshold, in whichever metric is selected, comes back as x,
+ * bit for bit, after no iteration (*n_hist = 0).
+ *   Refused (the message names the entry point): everything preAlps_ECGInitializeGuess refuses -- nrhs < 1 or
+ * enlFac % nrhs != 0, s against the number of parts, ORTHODIR_FUSED, more than one process or a preAlps_hip_loopback
+ * shard, a right-hand side of norm zero, a start residual that is not finite, a system that starts at exactly zero
+ * beside ones that do not -- and ldb, ldx0 or ldx < N, b or x == NULL, a right-hand side that is not finite, unknown
+ * flags.  After a refusal the operator and the preconditioner are usable as before.  HIP graphs and PREALPS_ECG_POLL
+ * are off for such a solver, as for several systems.  The solver object is released before the entry returns.
+ *   preAlps_OperatorSystemResiduals: res[j] = ||b_j - A x_j|| and normb[j] = ||b_j|| (either may be NULL) in the
+ * caller's units, fresh -- formed from b and x, not from a recurrence: one start from the guess x at s = 1 on a
+ * temporary solver of width nrhs (the gather, the library's own product, R0), the norm kernel on R0, and a free.
+ * nrhs <= 16 (what the per-system arrays of a solver hold); flags: PREALPS_SYS_DEVICE or 0.  No preconditioner is
+ * needed.  It refuses what the start refuses (a zero or non-finite right-hand side, a non-finite x, more than one
+ * process); a residual of exactly zero is an answer here, not a refusal. */
+#define PREALPS_SYS_DEVICE        1   /* b, x0, x are device pointers */
+#define PREALPS_SYS_STOP_ORIGINAL 2   /* stop on ||b_j - A x_j|| <= tol ||b_j|| in the caller's units */
+int preAlps_OperatorGetScalingPtr(double** d, int* n);
+int preAlps_ECGSolveSystem(preAlps_ECG_t* ecg, int nrhs, const double* b, int ldb,
+                           const double* x0, int ldx0, double* x, int ldx, int flags,
+                           double* res_hist, int* bs_hist, double* sys_hist, double* sys_normb,
+                           double* sys_res, int max_hist, int* n_hist);
+int preAlps_OperatorSystemResiduals(int nrhs, const double* b, int ldb, const double* x, int ldx,
+                                    int flags, double* res, double* normb);
 /* 1 / 0: the two driver loops above and below replay each half of an iteration from a HIP graph
  * captured on its first passes (default: off, or PREALPS_ECG_GRAPH; plain launches measured faster). */
 void preAlps_hip_graphs(int on);

@@ -69,6 +69,11 @@ typedef struct {
   unsigned* d_vmap;    /* device: stored value -> panel entry + 1, 0 = padding (plan_val_n entries; NULL: not cut yet) */
   int values_epoch;    /* 0 after a build, + 1 per update */
   int vmap_builds;     /* value maps cut for this operator */
+  /* the row map of preAlps_ECGSolveSystem on the device, cut at the first system solve: for local row i the caller's
+   * row src[i] = perm[row_off + i] and its scaling factor dl[i] = d[src[i]] (1.0 when unscaled), 12 bytes per row */
+  int* d_sys_src; double* d_sys_dl;
+  int sys_map_epoch;   /* values_epoch when it was cut: an update of the values moves d */
+  int sys_map_builds;
 } pa_operator_t;
 
 static pa_operator_t g_op;
@@ -121,7 +126,8 @@ void preAlps_OperatorFree(void) {
   pa_operator_t* o = &g_op;
   free_plan(o);
   free(o->lcol); free(o->src); free(o->src_rowptr);
-  free(o->info.rowPos); free(o->info.perm);
+  free(o->info.rowPos); free(o->info.perm); free(o->info.scaling);
+  pa_rt_free(o->d_sys_src); pa_rt_free(o->d_sys_dl);
   free(o->info.A.rowPtr); free(o->info.A.colInd); free(o->info.A.val);
   free(o->peers); free(o->send_rows); free(o->recv_rows); free(o->send_cnt); free(o->recv_cnt);
   free(o->send_idx); free(o->halo_cols);
@@ -417,7 +423,7 @@ int preAlps_OperatorBuildFromCSR(int N, const int* rowPtr, const int* colInd, co
   double* d = NULL; int* iperm = NULL; int* recv_by_proc = NULL;
   if (order_and_scale(N, rowPtr, colInd, val, nparts, part, scale, in, &d, &iperm)) return 1;
   if (build_panel(o, rowPtr, colInd, val, 1, g_keep_value_order, d, iperm, (long long)rowPtr[N], &recv_by_proc)) { free(d); free(iperm); return 1; }
-  free(d);
+  in->scaling = d;     /* (kept: preAlps_OperatorGetScalingPtr, the row map of preAlps_ECGSolveSystem) */
   TRACE_DECL;
   int m = in->m, lo = in->row_off, hi = in->row_off + m;
   /* Send lists, exactly: process g receives from us the rows of ours that occur as columns in
@@ -851,7 +857,7 @@ static int build_distributed(const char* file, int rank, int size) {
   }
   free(nzs);
   if (pa_mpi_agree(prc)) return prc ? 1 : PA_FAIL("another rank could not build its row panel");
-  free(d);
+  in->scaling = d;     /* (every rank holds the whole vector) */
   /* send lists: every rank asks the owners for the rows behind its halo slots (halo_cols is
    * ascending, hence grouped by owner); what a rank is asked for, in that order, is what it packs */
   int* asked = NULL;
@@ -955,6 +961,40 @@ int preAlps_OperatorGetHaloPlan(int* npeers, int** peers, int** send_rows, int**
 int preAlps_OperatorGetPermPtr(int** perm, int* n) {
   if (!g_op.info.built) return PA_FAIL("operator not built");
   *perm = g_op.info.perm; *n = g_op.info.N;
+  return 0;
+}
+int preAlps_OperatorGetScalingPtr(double** d, int* n) {
+  if (!g_op.info.built) return PA_FAIL("operator not built");
+  if (!d || !n) return PA_FAIL(" wrong test 'd != NULL && n != NULL'");
+  *d = g_op.info.scaling; *n = g_op.info.N;
+  return 0;
+}
+/* The device copy of the row map, cut at the first system solve and again when the values (and so d) have moved. */
+int pa_operator_system_map(const int** src, const double** dl) {
+  pa_operator_t* o = &g_op;
+  const pa_operator_info_t* in = &o->info;
+  if (!in->built) return PA_FAIL("operator not built");
+  if (g_plan_only) return PA_FAIL("the operator was built in plan-only mode (no GPU)");
+  if (o->d_sys_src && o->sys_map_epoch == o->values_epoch) { *src = o->d_sys_src; *dl = o->d_sys_dl; return 0; }
+  const size_t mm = (size_t)(in->m > 0 ? in->m : 1);
+  double* hdl = (double*)malloc(mm * sizeof(double));
+  if (!hdl) return PA_FAIL("out of host memory for the row map");
+  const int* hsrc = in->perm + in->row_off;
+  for (int i = 0; i < in->m; ++i) hdl[i] = in->scaling ? in->scaling[hsrc[i]] : 1.0;
+  if (!o->d_sys_src) {
+    o->d_sys_src = (int*)pa_rt_malloc(mm * sizeof(int));
+    o->d_sys_dl = (double*)pa_rt_malloc(mm * sizeof(double));
+  }
+  int rc = !o->d_sys_src || !o->d_sys_dl || pa_rt_h2d(o->d_sys_src, hsrc, (size_t)in->m * sizeof(int)) ||
+           pa_rt_h2d(o->d_sys_dl, hdl, (size_t)in->m * sizeof(double));
+  free(hdl);
+  if (rc) {
+    pa_rt_free(o->d_sys_src); pa_rt_free(o->d_sys_dl); o->d_sys_src = NULL; o->d_sys_dl = NULL;
+    return PA_FAIL("the row map of the system solve: %s", pa_rt_error());
+  }
+  o->sys_map_epoch = o->values_epoch;
+  ++o->sys_map_builds;
+  *src = o->d_sys_src; *dl = o->d_sys_dl;
   return 0;
 }
 int preAlps_hip_nparts(void) { return g_op.info.built ? g_op.info.nparts : 0; }
@@ -1093,6 +1133,7 @@ int preAlps_OperatorUpdateValues(const double* val) {
   const int N = in->N, m = in->m;
   const int* rp = o->src_rowptr;
   double* d = NULL;
+  if (o->scaled && !in->scaling) return PA_FAIL("the operator is scaled but holds no scaling vector");
   if (o->scaled) {   /* the scaling vector of order_and_scale, from the new values */
     d = (double*)malloc((size_t)N * sizeof(double));
     if (!d) return PA_FAIL("out of host memory");
@@ -1127,6 +1168,8 @@ int preAlps_OperatorUpdateValues(const double* val) {
       A->val[e] = d ? d[old] * v * d[in->perm[A->colInd[e]]] : v;
     }
   }
+  /* the last refusal is behind us: the new vector into the allocation the getter handed out */
+  if (d) memcpy(in->scaling, d, (size_t)N * sizeof(double));
   free(d);
   ++o->values_epoch;
   g_update_host_s = pa_wtime() - t0;
@@ -1263,6 +1306,8 @@ int preAlps_hip_get_stat(const char* key, double* value) {
   else if (!strcmp(key, "op_values_epoch")) *value = o->values_epoch;
   else if (!strcmp(key, "op_value_map_builds")) *value = o->vmap_builds;
   else if (!strcmp(key, "op_value_map_bytes")) *value = o->d_vmap ? (double)o->plan_val_n * sizeof(unsigned) : 0.0;
+  else if (!strcmp(key, "op_system_map_builds")) *value = o->sys_map_builds;
+  else if (!strcmp(key, "op_system_map_bytes")) *value = o->d_sys_src ? 12.0 * (double)o->info.m : 0.0;
   else if (!strcmp(key, "bj_values_epoch")) *value = pa_bj_values_epoch();
   else if (!strcmp(key, "op_update_host_s")) *value = g_update_host_s;
   else if (!strcmp(key, "op_update_copy_s")) *value = g_update_copy_s;

@@ -249,6 +249,20 @@ int pa_k_guess_start(int m, int ts, int k, int s, const double* B, int ldb, cons
 int pa_k_group_norms(const double* rtr_partials, int nblk, int ts, int k, int s, double* out, double* host);
 /* sol[i + j*ld] = sum of X[i][c] over the columns of system j, ascending c (pa_k_rowsum per system). */
 int pa_k_rowsum_groups(int m, int ts, int k, int s, const double* X, double* sol, int ld);
+/* ---- the caller's own system (dense_system.hip; preAlps_ECGSolveSystem) ----
+ * Local row i is the caller's row src[i] with scaling factor dl[i] (1.0 when the operator is unscaled); src, dl: m
+ * entries on the device.  B, X0, Xout: device, column major, k columns, rows in the caller's order, ld >= m.
+ * Bp(i, j) = dl[i] * B(src[i], j) and, when X0 is given, X0p(i, j) = X0(src[i], j) / dl[i], both with leading dimension
+ * m; sums[blk*ts + j] = the block's share of sum_i B(src[i], j)^2 (*nblk blocks, the layout of pa_k_colnorm2, for
+ * pa_k_group_norms with s = 1).  B and X0 are only read. */
+int pa_k_sys_gather(int m, int ts, int k, const int* src, const double* dl, const double* B, int ldb, const double* X0,
+                    int ldx0, double* Bp, double* X0p, double* sums, int* nblk);
+/* Xout(src[i], j) = dl[i] * (the sum of X[i][c] over the columns of system j, ascending c as pa_k_rowsum_groups). */
+int pa_k_sys_scatter(int m, int ts, int k, int s, const double* X, const int* src, const double* dl, double* Xout,
+                     int ldx);
+/* part[blk*ts + j] = the block's share of sum_i ((sum of R[i][c] over the columns of system j, ascending) / dl[i])^2
+ * (*nblk blocks): ||b_j - A x_j||^2 in the caller's units once pa_k_group_norms with s = 1 has folded them. */
+int pa_k_sys_norms(int m, int ts, int k, int s, const double* R, const double* dl, double* part, int* nblk);
 
 /* ---- block-Jacobi apply (block_jacobi.c:93-109, K8) --------------------- */
 typedef struct {

@@ -71,6 +71,7 @@ typedef struct {
   int* perm;        /* N: perm[new] = old */
   CPLM_Mat_CSR_t A; /* local row panel, global column ids (host) */
   int halo;         /* halo rows */
+  double* scaling;  /* N: d[i] of row i in the caller's (original) order, order_and_scale's d; NULL: built with scale = 0 */
 } pa_operator_info_t;
 const pa_operator_info_t* pa_operator_info(void);
 /* Workgroups of the SpMM at panel stride ts when it can leave the ECG Gram block behind
@@ -80,6 +81,9 @@ int pa_operator_gram_blocks(int ts);
  * pk_slot[pk_off[r] .. pk_off[r + 1]) of sendbuf, ts doubles each); the next preAlps_BlockOperator(X, .) skips its pack */
 int pa_operator_pack_hint(int ts, const double* X, const int** pk_off, const int** pk_slot, double** sendbuf);
 
+/* The row map of the system solve on the device (one process: N = m rows): src[i] = perm[row_off + i], dl[i] =
+ * scaling[src[i]] (1.0 when unscaled); cut lazily, again after preAlps_OperatorUpdateValues; library-owned. */
+int pa_operator_system_map(const int** src, const double** dl);
 int pa_operator_values_epoch(void);   /* 0 after a build, + 1 per preAlps_OperatorUpdateValues */
 int pa_bj_values_epoch(void);         /* that count at the last preAlps_BlockJacobiCreate / preAlps_BlockJacobiUpdateValues */
 int pa_operator_build_count(void);    /* + 1 per operator built in this process: tells a rebuilt operator from the one a preconditioner was created on */

@@ -23,6 +23,16 @@ def poisson3d_csr(n):
     return rowptr.astype(np.int32), C[M].astype(np.int32), np.ascontiguousarray(V[M], dtype=np.float64)
 
 
+def graded_values(rowptr, colind, val, lo, hi):
+    """The values of S A S, S = diag(10^g), g = linspace(lo, hi, N): the same pattern, still SPD (a congruence), with
+    a coefficient graded over hi - lo decades.  The row scaling of the solver equilibrates it, so a residual norm
+    in the scaled space and one in the caller's units weigh the rows differently by up to 10^(hi - lo)."""
+    N = len(rowptr) - 1
+    sc = 10.0 ** np.linspace(lo, hi, N)
+    rows = np.repeat(np.arange(N), np.diff(rowptr))
+    return sc[rows] * np.asarray(val, dtype=np.float64) * sc[colind]
+
+
 def box_partition(n, box):
     """Part id of every node of an n^3 grid cut into boxes of `box` = (bi, bj, bk)
     nodes (the last box of a direction may be smaller).  Parts are numbered

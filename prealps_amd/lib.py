@@ -9,6 +9,7 @@ LIB_PATH = os.path.join(_HERE, "libprealps_hip.so")
 ORTHOMIN, ORTHODIR, ORTHODIR_FUSED = 0, 1, 2
 ADAPT_BS, NO_BS_RED = 0, 1
 ROW_MAJOR, COL_MAJOR = 0, 1
+SYS_DEVICE, SYS_STOP_ORIGINAL = 1, 2      # flags of preAlps_ECGSolveSystem
 
 
 class PreAlpsError(RuntimeError):
@@ -83,6 +84,7 @@ EXPORTS = [
     "preAlps_ECGInitializeMulti", "preAlps_ECGSystemResiduals", "preAlps_ECGFinalizeMulti", "preAlps_ECGSolveMulti",
     "preAlps_ECGInitializeGuess", "preAlps_ECGSolveGuess",
     "preAlps_OperatorUpdateValues", "preAlps_BlockJacobiUpdateValues",
+    "preAlps_OperatorGetScalingPtr", "preAlps_ECGSolveSystem", "preAlps_OperatorSystemResiduals",
 ]
 
 _lib = None
@@ -123,6 +125,11 @@ def load():
     L.preAlps_ECGInitializeGuess.argtypes = [pe, C.c_int, pd, C.c_int, pd, C.c_int, pi]
     L.preAlps_ECGSolveGuess.argtypes = [pe, C.c_int, pd, C.c_int, pd, C.c_int, pd, C.c_int, pd, pi, pd, pd, pd,
                                         C.c_int, pi]
+    # b, x0, x: host or device addresses (PREALPS_SYS_DEVICE), so plain pointers
+    L.preAlps_ECGSolveSystem.argtypes = [pe, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                         C.c_int, pd, pi, pd, pd, pd, C.c_int, pi]
+    L.preAlps_OperatorSystemResiduals.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, pd, pd]
+    L.preAlps_OperatorGetScalingPtr.argtypes = [C.POINTER(pd), pi]
     L._preAlps_ECGReset.argtypes = [pe, pd, pi]
     L.preAlps_BlockOperator.argtypes = [_PD, _PD]
     L.preAlps_BlockJacobiApply.argtypes = [_PD, _PD]

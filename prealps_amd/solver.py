@@ -38,6 +38,10 @@ class EcgResult:
     sys_hist: np.ndarray = None
     # a solve from an initial guess (x0= / X0=): the residual norm every system starts from
     sys_res0: np.ndarray = None
+    # solve_system only: the metric of the stopping test, of sys_res, sys_normb and sys_hist ("original" / "scaled"),
+    # and the recurrence residual norms ||b_j - A x_j|| in the caller's units at the end, whichever metric stopped it
+    metric: str = None
+    sys_res_original: np.ndarray = None
 
 
 class DistributedHooks:
@@ -344,6 +348,151 @@ class EcgProblem:
             self.create_block_jacobi(*self._precond_args)
         elif precond == "refactor" and self.has_precond:
             self.refactor_block_jacobi()
+
+    @property
+    def scaling(self):
+        """preAlps_OperatorGetScalingPtr: a NumPy copy of d (N values, entry i for row i of the matrix this problem
+        was built from; d_i = sqrt(1 / max_j |a_ij|)), None when the problem is unscaled.  The operator the solver
+        iterates on is P D A D P^T with perm[new] = old."""
+        d, n = C.POINTER(C.c_double)(), C.c_int()
+        check(self.L.preAlps_OperatorGetScalingPtr(C.byref(d), C.byref(n)), "preAlps_OperatorGetScalingPtr")
+        if not d:
+            return None
+        return np.ctypeslib.as_array(d, shape=(n.value,)).copy()
+
+    def _system_args(self, what, b, x0, x0_name):
+        """The checks solve_system and system_residuals share, before any library call: ("host" | "device", k, one
+        column given as a vector).  Raises ValueError."""
+        def is_tensor(a):
+            return type(a).__module__.split(".")[0] == "torch" and hasattr(a, "data_ptr")
+        arrays = [("b" if what == "solve_system" else "B", b)] + ([] if x0 is None else [(x0_name, x0)])
+        kinds = {"device" if (is_tensor(a) and a.is_cuda) else "host" for _, a in arrays}
+        if len(kinds) > 1:
+            raise ValueError("%s: host and device arguments are mixed (%s): pass NumPy arrays or float64 CUDA tensors, "
+                             "not both" % (what, ", ".join("%s on the %s" % (n, "device" if is_tensor(a) and a.is_cuda
+                                                                             else "host") for n, a in arrays)))
+        kind = kinds.pop()
+        shapes = []
+        for name, a in arrays:
+            if is_tensor(a):
+                import torch
+                if a.dtype != torch.float64:
+                    raise ValueError("%s: %s has dtype %s, float64 is needed" % (what, name, a.dtype))
+                if not a.is_cuda:
+                    raise ValueError("%s: %s is a CPU tensor: pass a NumPy array or a CUDA tensor" % (what, name))
+            shp = tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
+            if len(shp) not in (1, 2) or shp[0] != self.N or (len(shp) == 2 and shp[1] < 1):
+                raise ValueError("%s: %s must be of shape (%d,) or (%d, k), not %r" % (what, name, self.N, self.N, shp))
+            shapes.append(shp)
+        if len(shapes) == 2 and shapes[0] != shapes[1]:
+            raise ValueError("%s: %s has shape %r, %s has %r" % (what, arrays[1][0], shapes[1], arrays[0][0], shapes[0]))
+        return kind, (1 if len(shapes[0]) == 1 else int(shapes[0][1])), len(shapes[0]) == 1
+
+    def _device_columns(self, a):
+        """(tensor to keep alive, address, leading dimension) of an (N, k) float64 CUDA tensor: passed as it lies when
+        its strides are (1, ld) with ld >= N, otherwise copied once on the device into that layout."""
+        import torch
+        if a.dim() == 1:
+            a = a.unsqueeze(1)
+        k = a.shape[1]
+        ok = a.stride(0) == 1 and (k == 1 or a.stride(1) >= self.N)
+        if not ok:
+            a = torch.empty((k, self.N), dtype=torch.float64, device=a.device).copy_(a.t()).t()
+        return a, a.data_ptr(), (int(a.stride(1)) if k > 1 else max(self.N, 1))
+
+    def _order_torch_stream(self):
+        """The library reads and writes device arguments on its own stream: unless that is torch's current stream
+        (use_torch_stream), what torch has queued must be done first."""
+        import torch
+        cur = torch.cuda.current_stream().cuda_stream
+        if int(self.L.preAlps_hip_get_stream() or 0) != int(cur):
+            torch.cuda.current_stream().synchronize()
+
+    def solve_system(self, b, t, x0=None, stop="original", ortho_alg=ORTHODIR, bs_red=NO_BS_RED, tol=1e-5,
+                     max_iter=1000):
+        """preAlps_ECGSolveSystem: A x = b as the caller stated it -- the rows in the order of the matrix this problem
+        was built from, the values in its units -- for one system (b of shape (N,)) or k systems (b of shape (N, k), t a
+        multiple of k), with or without a starting value x0 of the same shape.  One process.
+        stop="original" (the default: this method exists so that tol means the caller's): iterate until
+        ||b_j - A x_j|| <= tol * ||b_j|| for every j, both norms in the caller's units; "scaled": the library's own test
+        on the scaled system, as solve / solve_multi apply it -- then the iterate is theirs bit for bit.
+        NumPy arrays go the host way.  float64 torch CUDA tensors go the device way: they are passed by address (copied
+        once on the device if their strides are not (1, ld >= N)), never written, and the result's x is a CUDA tensor;
+        unless the problem runs on torch's stream, torch's current stream is synchronised before the call.
+        Returns an EcgResult: x in the caller's order and units, metric = stop, sys_res / sys_normb / sys_hist in that
+        metric, sys_res_original = the recurrence residual norms in the caller's units at the end; res / bs / normb /
+        final_res stay the scaled Frobenius norms.  Mixed host and device arguments, a tensor that is not float64, wrong
+        shapes and a bad stop raise ValueError before any library call."""
+        if stop not in ("original", "scaled"):
+            raise ValueError("stop must be 'original' or 'scaled', not %r" % (stop,))
+        kind, k, vector = self._system_args("solve_system", b, x0, "x0")
+        if int(t) < 1 or int(t) % k != 0:
+            raise ValueError("the enlarging factor t = %d is not a multiple of the %d right-hand sides" % (t, k))
+        if not self.has_precond:
+            self.create_block_jacobi()
+        import time
+        L = self.L
+        check(L.preAlps_hip_prepare_operator(int(t)), "preAlps_hip_prepare_operator")
+        e = self.new_ecg(t, ortho_alg, bs_red, tol, max_iter)
+        flags = _l.SYS_STOP_ORIGINAL if stop == "original" else 0
+        N = self.N
+        if kind == "device":
+            import torch
+            flags |= _l.SYS_DEVICE
+            bk, pb, ldb = self._device_columns(b)
+            xk, px0, ldx0 = (None, None, 0) if x0 is None else self._device_columns(x0)
+            x = torch.empty((k, N), dtype=torch.float64, device=bk.device).t()     # strides (1, N)
+            px, ldx = x.data_ptr(), max(N, 1)
+            self._order_torch_stream()
+        else:
+            bk = np.asfortranarray(np.asarray(b, dtype=np.float64).reshape(N, k))
+            pb, ldb = bk.ctypes.data, max(N, 1)
+            xk = None if x0 is None else np.asfortranarray(np.asarray(x0, dtype=np.float64).reshape(N, k))
+            px0, ldx0 = (None, 0) if xk is None else (xk.ctypes.data, max(N, 1))
+            x = np.zeros((N, k), order="F")
+            px, ldx = x.ctypes.data, max(N, 1)
+        cap = max_iter + 2
+        res = np.zeros(cap)
+        bs = np.zeros(cap, dtype=np.int32)
+        sys_hist = np.zeros((cap, k), order="F")
+        sys_normb, sys_end = np.zeros(k), np.zeros(k)
+        nh = C.c_int()
+        t0 = time.perf_counter()
+        check(L.preAlps_ECGSolveSystem(C.byref(e), k, pb, ldb, px0, ldx0, px, ldx, flags, _pd(res), _pi(bs),
+                                       _pd(sys_hist), _pd(sys_normb), _pd(sys_end), cap, C.byref(nh)),
+              "preAlps_ECGSolveSystem")
+        dt = time.perf_counter() - t0
+        n = nh.value
+        if vector:
+            x = x[:, 0].contiguous() if kind == "device" else np.ascontiguousarray(x[:, 0])
+        timers = {k_: getattr(e, k_) for k_ in ("tot_t", "comm_t", "trsm_t", "gemm_t", "potrf_t", "copy_t")}
+        return EcgResult(x=x, iters=e.iter, res=res[:n].copy(), bs=bs[:n].copy(), final_res=e.res, final_bs=e.bs,
+                         normb=e.normb, seconds=dt, timers=timers,
+                         sys_res=sys_hist[n - 1].copy() if n else (sys_end.copy() if stop == "original" else None),
+                         sys_normb=sys_normb, sys_hist=np.ascontiguousarray(sys_hist[:n]), metric=stop,
+                         sys_res_original=sys_end)
+
+    def system_residuals(self, B, X):
+        """preAlps_OperatorSystemResiduals: (res, normb) with res[j] = ||b_j - A x_j|| and normb[j] = ||b_j|| in the
+        caller's order and units, formed afresh from B and X (shape (N,) or (N, k), k <= 16; NumPy arrays or float64 CUDA
+        tensors, as solve_system takes them).  Needs no preconditioner."""
+        kind, k, _ = self._system_args("system_residuals", B, X, "X")
+        L = self.L
+        N = self.N
+        flags = 0
+        if kind == "device":
+            flags = _l.SYS_DEVICE
+            bk, pb, ldb = self._device_columns(B)
+            xk, px, ldx = self._device_columns(X)
+            self._order_torch_stream()
+        else:
+            bk = np.asfortranarray(np.asarray(B, dtype=np.float64).reshape(N, k))
+            xk = np.asfortranarray(np.asarray(X, dtype=np.float64).reshape(N, k))
+            pb, ldb, px, ldx = bk.ctypes.data, max(N, 1), xk.ctypes.data, max(N, 1)
+        res, normb = np.zeros(max(k, 1)), np.zeros(max(k, 1))
+        check(L.preAlps_OperatorSystemResiduals(k, pb, ldb, px, ldx, flags, _pd(res), _pd(normb)),
+              "preAlps_OperatorSystemResiduals")
+        return res[:k], normb[:k]
 
     def reference_rhs(self):
         rhs = np.zeros(self.m)
