@@ -146,6 +146,49 @@ int preAlps_OperatorUpdateValues(const double* val);
  * the preconditioner, as a failed create does (so does any device error after the first write, and a failure of the
  * sparse blocks' create); a later preAlps_BlockJacobiCreate works. */
 int preAlps_BlockJacobiUpdateValues(void);
+/* ---- two-level block Jacobi: an additive coarse correction from given vectors -----------------------------------
+ * Block Jacobi has no coarse space, so its iteration count grows with the number of blocks.  With k vectors V near the
+ * kernel of A (the translations or the rigid-body modes of an elasticity problem, the constant of a diffusion problem)
+ * the preconditioner becomes M^-1 = B^-1 + Z E^-1 Z^T: B^-1 is the block-Jacobi apply as it is, band and sparse
+ * factors alike; Z holds the vectors cut aggregate by aggregate -- an aggregate is a set of parts, row i of a part in
+ * aggregate g has its k values in the columns g*k .. g*k + k - 1 -- and E = Z^T A' Z with A' = P D A D P^T the
+ * operator's own matrix, nc = naggr * k unknowns.  M^-1 is symmetric positive definite whenever E is; the ECG
+ * iteration needs nothing else.  Opt-in: without this call nothing changes, bit for bit.
+ *   V: N x k column major, ldv >= N, 1 <= k <= 8, in the order and units of the matrix the operator was built from,
+ * as b of preAlps_ECGSolveSystem; internally Vp = (D^-1 V)[perm] (a vector near the kernel of A is near the kernel
+ * of D A D after division by d).  part_aggregate: nparts ints in [0, naggr), every aggregate non-empty; NULL selects
+ * one aggregate per part when nparts * k fits the cap, otherwise floor(cap / k) aggregates from
+ * preAlps_hip_partition_kway on the quotient graph of the parts (an edge where some a_ij joins two parts).
+ *   Set-up (host, fp64, the same bits for any number of threads): E is assembled by aggregates in row order, factored
+ * by Cholesky, and Einv = L^-T L^-1 is formed explicitly and made symmetric in bits; a pivot <= nc * eps * max diag E
+ * refuses the vectors and names the aggregate and the vector.  The cap on nc is "bj_coarse_max_dofs" (1536: 18.9 MB
+ * of Einv on the device, about nc^3 host flops).
+ *   Apply: preAlps_BlockJacobiApply adds Z Einv Z^T in to out after the block solve, over the live columns, with three
+ * stages of coarse.hip: a pass over `in` that leaves one k x columns block per chunk of at most 1024 rows, the sum of
+ * each aggregate's blocks in list order and one streaming pass over Einv, and a read-modify-write pass over `out`.
+ * No atomics: two applies of one input agree in bits.  While a coarse space is attached the block solve does not
+ * leave the Gram block of the iteration behind ("bj_gram_applies" stays), and the solver takes the path of
+ * PREALPS_BJ_GRAM=0, also a solver initialised before the call.
+ *   Values: preAlps_BlockJacobiUpdateValues forms zv, E and Einv again from the kept V (8 k N bytes on the host) and
+ * aggregates and the new values and scaling vector, into the same device arrays ("bj_coarse_einv_address" stays); a
+ * singular E there drops the coarse space and reports, the refreshed block factor stays.  After
+ * preAlps_OperatorUpdateValues alone the coarse space is lagged with the factor, still SPD.
+ * preAlps_BlockJacobiFree releases it; setting one again replaces it.
+ *   Solvers: set, replace or clear between solves.  Both entries drain the library stream first.  A solver that replays
+ * HIP graphs (preAlps_hip_graphs) notices the change at its next iteration and captures its segments anew, as it does
+ * after preAlps_BlockJacobiFree + Create; a solver in the middle of an iteration goes on with the new apply.
+ *   Stats: "bj_coarse_dofs", "bj_coarse_vectors", "bj_coarse_aggregates", "bj_coarse_chunks", "bj_coarse_bytes"
+ * (device), "bj_coarse_setup_s" (host seconds of the last build with its upload), "bj_coarse_builds" (the set and
+ * every refresh since), "bj_coarse_applies", "bj_coarse_einv_address": 0 without a coarse space; and
+ * "bj_coarse_max_dofs".
+ *   Refused, the preconditioner left as it was (a coarse space set earlier included): no operator or no
+ * preconditioner; more than one process or a preAlps_hip_loopback shard; plan-only mode; k out of range; ldv < N; a
+ * non-finite entry of V; naggr * k above the cap; an empty aggregate or one out of range; a singular E. */
+int preAlps_BlockJacobiSetCoarseSpace(int k, const double* V, int ldv, const int* part_aggregate, int naggr);
+int preAlps_BlockJacobiClearCoarseSpace(void);
+/* The aggregates of the attached coarse space: part_aggregate[p] for every part (nparts ints, the caller's array) --
+ * what the caller gave, or the default the library chose -- and *naggr (may be NULL).  Refused without a coarse space. */
+int preAlps_BlockJacobiGetCoarseAggregates(int* part_aggregate, int* naggr);
 /* k-way partition of the adjacency graph of a square matrix with a structurally symmetric
  * pattern (0-based CSR, diagonal stored) into nparts compact, balanced parts:
  * part[i] in [0, nparts) for every row i.  This is what the library calls in place of the
@@ -385,7 +428,8 @@ int preAlps_hip_panel_permute_solve(const CPLM_Mat_Dense_t* Z, CPLM_Mat_Dense_t*
  * 0: no class has them, e.g. PREALPS_BJ_G4=0), "bj_g4_bytes" (bytes of those records as stored: half in single
  * precision; "bj_factor_bytes" does not count them), "bj_g4_last_ring" / "bj_g4_last_bits" /
  * "bj_g4_last_pipelined" (the last launch that read them: LDS ring depth, storage bits of the records, 1 = the
- * pipelined few-blocks chain), ...  Returns non-zero for unknown keys. */
+ * pipelined few-blocks chain), "ecg_graph_captures" / "ecg_graph_replays" (iteration segments captured and graphs
+ * launched by the driver loops so far, preAlps_hip_graphs), ...  Returns non-zero for unknown keys. */
 int preAlps_hip_get_stat(const char* key, double* value);
 /* A stopwatch made of two hipEvents on the library stream: start records the
  * first, stop records the second, waits for it and returns the device time

@@ -105,6 +105,7 @@ typedef struct {
   int phase;          /* iterations since the last reset, mod 6 */
   void* graph[2][6];
   unsigned char seen[2][6];
+  int bj_epoch;       /* pa_bj_apply_epoch() the graphs were captured under */
   /* Several right-hand sides (preAlps_ECGInitializeMulti): nrhs systems of sgrp = enlFac / nrhs columns each, system
    * j in the columns j*sgrp .. j*sgrp + sgrp - 1.  nrhs <= 1: one system, nothing below is used.  Every launch that
    * leaves the column sums of R^2 in d_rtr_part is followed by pa_k_group_norms (queue_group_norms), which leaves
@@ -733,8 +734,16 @@ static int wait_for_note(ecg_priv_t* pv) {
  * graph is instantiated and launched.  From then on the host code still runs -- it rotates
  * pointers and counts -- with every launch suppressed (pa_rt_skip), and the graph is launched in
  * its place: one launch instead of three to six per segment. */
+static long long g_graph_captures, g_graph_replays;     /* segments captured / graphs launched so far, all solvers */
+long long pa_ecg_graph_count(int which) { return which ? g_graph_replays : g_graph_captures; }
 static int seg_begin(ecg_priv_t* pv, int seg) {
   if (!pv->use_graphs || pa_timing_enabled()) return 0;    /* (phase timers put events between the launches) */
+  if (pv->bj_epoch != pa_bj_apply_epoch()) {
+    /* the preconditioner was created again, or its coarse space set or cleared, since the capture: the graphs hold
+     * the old launches and pointers (the entry that changed them has drained the stream), so capture anew */
+    for (int a = 0; a < 2; ++a) for (int b = 0; b < 6; ++b) { pa_rt_graph_free(pv->graph[a][b]); pv->graph[a][b] = NULL; pv->seen[a][b] = 0; }
+    pv->bj_epoch = pa_bj_apply_epoch();
+  }
   if (pv->graph[seg][pv->phase]) { pa_rt_skip(1); return 2; }
   if (pv->seen[seg][pv->phase]++ == 0) return 0;
   if (pa_rt_capture_begin()) { pv->use_graphs = 0; return 0; }   /* (nothing queued yet: go on without graphs) */
@@ -747,9 +756,11 @@ static int seg_end(ecg_priv_t* pv, int seg, int mode, int body_rc) {
     int rc = pa_rt_capture_end(&exec);
     if (rc || body_rc) { pa_rt_graph_free(exec); return PA_FAIL("capturing an iteration segment failed: %s", pa_rt_error()); }
     pv->graph[seg][pv->phase] = exec;
+    ++g_graph_captures;
   }
   if (body_rc) return 1;
   if (mode && pa_rt_graph_launch(pv->graph[seg][pv->phase])) return PA_FAIL("%s", pa_rt_error());
+  if (mode) ++g_graph_replays;
   return 0;
 }
 /* One full iteration from the state "AP = A P is there" (rci 0) to the same state: the order of

@@ -202,6 +202,7 @@ static int g_plan_only = 0;
 /* Host-side planning without touching the GPU (sharding, halo lists): what the
  * multi-process CPU tests exercise.  BlockOperator is unavailable in this mode. */
 void preAlps_hip_plan_only(int on) { g_plan_only = on ? 1 : 0; }
+int pa_operator_plan_only(void) { return g_plan_only; }
 
 /* ---- the build, in three steps ------------------------------------------------------------
  * (1) order_and_scale: what needs the whole matrix -- the diagonal check, the scaling vector of
@@ -1293,6 +1294,8 @@ int preAlps_hip_get_stat(const char* key, double* value) {
   else if (!strcmp(key, "spmm_blocks")) *value = o->plan.nblk;
   else if (!strcmp(key, "spmm_gram_launches")) *value = (double)pa_k_spmm_gram_launches();
   else if (!strcmp(key, "bj_gram_applies")) *value = (double)pa_k_bj_gram_applies();
+  else if (!strcmp(key, "ecg_graph_captures")) *value = (double)pa_ecg_graph_count(0);
+  else if (!strcmp(key, "ecg_graph_replays")) *value = (double)pa_ecg_graph_count(1);
   else if (!strcmp(key, "packs_fused")) *value = (double)g_packs_fused;
   else if (!strcmp(key, "spmm_slices")) *value = o->plan.nslices;
   else if (!strcmp(key, "spmm_stored_entries")) *value = o->sell_entries;

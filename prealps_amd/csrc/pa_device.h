@@ -358,6 +358,24 @@ int pa_k_bj_apply(const pa_bj_plan_t* pl, int ts, const double* in, double* out)
 int pa_k_bj_band_assemble(const unsigned* src, const unsigned* dst, const int* chunk_blk, const unsigned* chunk_first,
                           size_t nchunks, const long long* boff, const double* pv, double* band);
 
+/* ---- coarse correction of the two-level block-Jacobi preconditioner (coarse.hip) -------------------------
+ * out(:, :ncols) += Z Einv Z^T in(:, :ncols), every array on the device, fp64.  Z as zv (m x k row major: row i of
+ * a chunk of aggregate g has its k values in the columns g*k .. g*k + k - 1 of Z), the chunk lists and Einv
+ * (nc x nc, nc = naggr * k) as coarse_space.h lays them out.  Three stages on the library stream, no atomics (an
+ * apply is reproducible in bits): k_coarse_restrict, one workgroup per chunk, partial[chunk][a][c] = sum_i zv[i][a]
+ * in[i][c]; k_coarse_gather + k_coarse_einv, c[g*k + a][:] = the sum of aggregate g's chunk partials in list
+ * order and y = Einv c in one pass over Einv; k_coarse_prolong_add, out[i][c] += sum_a zv[i][a] y[g(i)*k + a][c].
+ * partial: nchunks * k * 16 doubles, c and y: nc * 16 doubles (scratch the plan owns). */
+typedef struct {
+  int m, k, naggr, nc, nchunks;
+  const double* zv;
+  const int* ch_row0; const int* ch_nrows; const int* ch_aggr;
+  const int* agg_ptr; const int* agg_chunk;
+  const double* Einv;
+  double* partial; double* c; double* y;
+} pa_coarse_plan_t;
+int pa_k_coarse_apply(const pa_coarse_plan_t* pl, int ts, int ncols, const double* in, double* out);
+
 /* ---- sparse block solve for large diagonal blocks (nd.c) --------------------------------- */
 /* Supernodes of a nested-dissection Cholesky factor, all blocks of the process in one numbering.
  * Supernode s: n[s] pivot columns, m[s] rows below, panel P = [T ; -G] (see nd_apply.hip) twice:

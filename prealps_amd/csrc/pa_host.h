@@ -86,6 +86,7 @@ int pa_operator_pack_hint(int ts, const double* X, const int** pk_off, const int
 int pa_operator_system_map(const int** src, const double** dl);
 int pa_operator_values_epoch(void);   /* 0 after a build, + 1 per preAlps_OperatorUpdateValues */
 int pa_bj_values_epoch(void);         /* that count at the last preAlps_BlockJacobiCreate / preAlps_BlockJacobiUpdateValues */
+int pa_operator_plan_only(void);     /* 1: preAlps_hip_plan_only is on (host side only, no GPU) */
 int pa_operator_build_count(void);    /* + 1 per operator built in this process: tells a rebuilt operator from the one a preconditioner was created on */
 int pa_bj_update_stat(const char* key, double* value);   /* the stats of preAlps_BlockJacobiUpdateValues by name; 1: unknown key */
 
@@ -120,6 +121,8 @@ double pa_bj_setup_seconds(int which);   /* 0: ordering + band Cholesky, 1: swee
 int pa_bj_nparts(void);
 int pa_bj_nd_blocks(void);
 int pa_bj_nd_precision(void);       /* storage of the sparse factors (64 / 32), 0 if no block has one */
+long long pa_ecg_graph_count(int which);   /* 0: iteration segments captured so far, 1: graphs launched (ecg.c) */
+int pa_bj_apply_epoch(void);       /* + 1 per change of what preAlps_BlockJacobiApply launches or reads (create, free, coarse space) */
 int pa_bj_gram_blocks(void);       /* blocks of an apply that can leave [in | prev]^T out behind (0: cannot) */
 double pa_bj_g4_bytes(void);        /* bytes of the one-copy records of bj_g4.hip as stored (fp64 / fp32), 0 if absent */
 int pa_bj_band_precision(void);     /* storage of those records (64 / 32), 0 if absent */

@@ -85,6 +85,8 @@ EXPORTS = [
     "preAlps_ECGInitializeGuess", "preAlps_ECGSolveGuess",
     "preAlps_OperatorUpdateValues", "preAlps_BlockJacobiUpdateValues",
     "preAlps_OperatorGetScalingPtr", "preAlps_ECGSolveSystem", "preAlps_OperatorSystemResiduals",
+    "preAlps_BlockJacobiSetCoarseSpace", "preAlps_BlockJacobiClearCoarseSpace",
+    "preAlps_BlockJacobiGetCoarseAggregates",
 ]
 
 _lib = None
@@ -141,6 +143,9 @@ def load():
     L.preAlps_OperatorBuildFromCSR.argtypes = [C.c_int, pi, pi, pd, C.c_int, pi, C.c_int]
     L.preAlps_OperatorUpdateValues.argtypes = [pd]
     L.preAlps_BlockJacobiUpdateValues.argtypes = []
+    L.preAlps_BlockJacobiSetCoarseSpace.argtypes = [C.c_int, pd, C.c_int, pi, C.c_int]
+    L.preAlps_BlockJacobiClearCoarseSpace.argtypes = []
+    L.preAlps_BlockJacobiGetCoarseAggregates.argtypes = [pi, pi]
     L.preAlps_OperatorGetA.argtypes = [C.POINTER(CPLM_Mat_CSR_t)]
     L.preAlps_OperatorGetSizes.argtypes = [pi, pi]
     L.preAlps_OperatorGetRowPosPtr.argtypes = [C.POINTER(pi), pi]

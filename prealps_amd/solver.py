@@ -240,6 +240,7 @@ class EcgProblem:
         self = cls.__new__(cls)
         self.L = L = _l.load()
         self.hooks, self.comm_kind = None, "none"
+        self._plan_only = False
         check(L.preAlps_hip_init(device), "preAlps_hip_init")
         if nparts is not None:
             os.environ["PREALPS_NPARTS"] = str(nparts)
@@ -273,6 +274,7 @@ class EcgProblem:
         self.row_off = 0
         self.has_precond = False
         self._precond_args = (None, None)
+        self._coarse = None
 
     def part_vector(self):
         """part[i] of every original row i, recovered from the permutation and rowPos."""
@@ -281,8 +283,51 @@ class EcgProblem:
         return part
 
     # -- pieces of the driver --------------------------------------------------
-    def create_block_jacobi(self, nd_precision=None, band_precision=None):
-        """nd_precision: storage of the sparse factors of large blocks -- None follows
+    def set_coarse_space(self, V, aggregates=None):
+        """preAlps_BlockJacobiSetCoarseSpace: M^-1 = B^-1 + Z E^-1 Z^T from the k columns of V (N x k, or N values
+        for one vector; 1 <= k <= 8), given in the order and units of the matrix this problem was built from
+        (nearkernel.translations, nearkernel.rigid_body_modes).  aggregates: one aggregate id per part (numbered
+        0 .. naggr - 1, none empty); None = one aggregate per part when that fits stat("bj_coarse_max_dofs"),
+        otherwise the library's partition of the parts' quotient graph.  Creates the block-Jacobi factor first if
+        there is none.  A refusal raises and leaves the preconditioner (and an earlier coarse space) as it was."""
+        V = np.asarray(V, dtype=np.float64)
+        if V.ndim == 1:
+            V = V[:, None]
+        if V.ndim != 2:
+            raise ValueError("V must be two-dimensional (N x k), not of shape %r" % (V.shape,))
+        if V.shape[0] != self.N:
+            raise ValueError("V has %d rows, the matrix has %d" % (V.shape[0], self.N))
+        V = np.asfortranarray(V)
+        agg, naggr = None, 0
+        if aggregates is not None:
+            agg = np.ascontiguousarray(aggregates, dtype=np.int32)
+            if agg.shape != (self.nparts,):
+                raise ValueError("aggregates must hold one id per part (%d), not be of shape %r" % (self.nparts, agg.shape))
+            naggr = int(agg.max()) + 1 if agg.size else 0
+        if not self.has_precond and not self._plan_only:
+            self.create_block_jacobi()
+        check(self.L.preAlps_BlockJacobiSetCoarseSpace(int(V.shape[1]), _pd(V), max(self.N, 1),
+                                                       None if agg is None else _pi(agg), naggr),
+              "preAlps_BlockJacobiSetCoarseSpace")
+        # remembered for update_values(..., precond="rebuild"); V is not copied a second time (the library keeps its
+        # own copy): an N x k float64 array in column-major order is held as it is, so leave it unchanged meanwhile
+        self._coarse = (V, None if agg is None else agg.copy())
+
+    def coarse_aggregates(self):
+        """preAlps_BlockJacobiGetCoarseAggregates: the aggregate of every part of the attached coarse space (the
+        ones given, or the default the library chose) as an int32 array of nparts values."""
+        agg, n = np.zeros(self.nparts, dtype=np.int32), C.c_int()
+        check(self.L.preAlps_BlockJacobiGetCoarseAggregates(_pi(agg), C.byref(n)), "preAlps_BlockJacobiGetCoarseAggregates")
+        return agg
+
+    def clear_coarse_space(self):
+        """preAlps_BlockJacobiClearCoarseSpace: plain block Jacobi again, with the bits it had before."""
+        check(self.L.preAlps_BlockJacobiClearCoarseSpace(), "preAlps_BlockJacobiClearCoarseSpace")
+        self._coarse = None
+
+    def create_block_jacobi(self, nd_precision=None, band_precision=None, coarse=None):
+        """coarse: vectors for set_coarse_space(coarse) right after the create (default aggregates).
+        nd_precision: storage of the sparse factors of large blocks -- None follows
         PREALPS_BJ_ND_PRECISION, "double" / "single" select it for this create (band blocks stay fp64).
         With a value, the library's setting (preAlps_hip_set_nd_precision) is 0 again afterwards: a value
         set earlier through the C entry is not restored.
@@ -309,6 +354,9 @@ class EcgProblem:
                 self.L.preAlps_hip_set_band_precision(0)
         self.has_precond = True
         self._precond_args = (nd_precision, band_precision)
+        self._coarse = None                      # (a create frees the old preconditioner with its coarse space)
+        if coarse is not None:
+            self.set_coarse_space(coarse)
 
     def refactor_block_jacobi(self):
         """preAlps_BlockJacobiUpdateValues: the factor of the current panel in place -- for band blocks the bits of
@@ -318,6 +366,8 @@ class EcgProblem:
         rc = self.L.preAlps_BlockJacobiUpdateValues()
         if rc != 0:
             self.has_precond = self.stat("bj_parts_local") > 0     # (freed by the library when the values are not SPD)
+            if self.stat("bj_coarse_dofs") == 0:                    # (or only the coarse space dropped: singular E)
+                self._coarse = None
         check(rc, "preAlps_BlockJacobiUpdateValues")
 
     def update_values(self, val, precond="keep"):
@@ -327,7 +377,9 @@ class EcgProblem:
         precond="keep": the block-Jacobi factor of the old values stays, a lagged preconditioner for the new matrix
         (stat("bj_values_epoch") < stat("op_values_epoch") tells); "rebuild": it is freed and created again from the
         new panel with the precision arguments of the last create_block_jacobi; "refactor": refactor_block_jacobi(),
-        the same factor in place.  Without a preconditioner "rebuild" and "refactor" do what "keep" does."""
+        the same factor in place.  Without a preconditioner "rebuild" and "refactor" do what "keep" does.
+        A coarse space (set_coarse_space) goes along: lagged with the factor under "keep", formed again in place at
+        the same device addresses under "refactor", attached again to the new factor under "rebuild"."""
         if precond not in ("keep", "rebuild", "refactor"):
             raise ValueError("precond must be 'keep', 'rebuild' or 'refactor', not %r" % (precond,))
         if val is None:
@@ -343,9 +395,12 @@ class EcgProblem:
             ptr = _pd(val)
         check(self.L.preAlps_OperatorUpdateValues(ptr), "preAlps_OperatorUpdateValues")
         if precond == "rebuild" and self.has_precond:
+            coarse = self._coarse
             self.L.preAlps_BlockJacobiFree()
             self.has_precond = False
             self.create_block_jacobi(*self._precond_args)
+            if coarse is not None:                   # the remembered coarse space, attached again to the new factor
+                self.set_coarse_space(coarse[0], coarse[1])
         elif precond == "refactor" and self.has_precond:
             self.refactor_block_jacobi()
 
