@@ -433,12 +433,14 @@ static int launch_spmm(const pa_spmm_plan_t* pl, const int* order, int nlist, co
     if (g_sg.armed && (pl->runs || pl->staged) && lds <= 64 * 1024 && X == g_sg.X && Y == g_sg.Y && g_sg.count >= 0 &&
         g_sg.count + nlist <= g_sg.cap) {
       const int cpx = (nlist + 7) / 8;
+      // (spmm_gram_tail passes the wavefronts' shares through the first 1024 bytes, whatever a tiny plan stages)
+      const size_t lds_gram = lds > 1024 ? lds : 1024;
       if (pl->runs)
-        PA_LAUNCH(k_spmm_runs_gram<3>, dim3(cpx * 8), dim3(WG), lds, cur_stream(), pl->m, pl->sl_off,
+        PA_LAUNCH(k_spmm_runs_gram<3>, dim3(cpx * 8), dim3(WG), lds_gram, cur_stream(), pl->m, pl->sl_off,
                   pl->sl_len, pl->sl_row0, pl->sl_nrows, pl->col16, pl->val, pl->blk_slice, pl->blk_ext_off,
                   pl->blk_nlow, pl->ext_rows, order, nlist, X, Xh, Y, g_sg.R, g_sg.partials, g_sg.count);
       else         // one staged row per slot (matrices without runs of three): no low / high split, no zero rows
-        PA_LAUNCH(k_spmm_runs_gram<1>, dim3(cpx * 8), dim3(WG), lds, cur_stream(), pl->m, pl->sl_off,
+        PA_LAUNCH(k_spmm_runs_gram<1>, dim3(cpx * 8), dim3(WG), lds_gram, cur_stream(), pl->m, pl->sl_off,
                   pl->sl_len, pl->sl_row0, pl->sl_nrows, pl->col16, pl->val, pl->blk_slice, pl->blk_ext_off,
                   (const int*)nullptr, pl->ext_rows, order, nlist, X, Xh, Y, g_sg.R, g_sg.partials, g_sg.count);
       g_sg.count += nlist;

@@ -190,6 +190,42 @@ def box_partition_nodes(nn, box, dofs=3):
     return np.repeat(part, dofs).astype(np.int32), ni * nj * nk
 
 
+def node_graph_csr(nn, stride, seed, far_every=7, nfar=2, excess=1.0):
+    """SPD matrix of a graph of nn nodes with three dofs per node (dof = 3*node + c): every row has its nonzeros in
+    runs of three consecutive columns and only a few of them, so a host product of 3 nn rows takes a fraction of a
+    second.  Links: i -- i+1 and i -- i+stride; every far_every-th node (0, far_every, ...) also gets nfar links to
+    nodes drawn with rng.integers(0, nn) (nfar draws of one node per such node, in that order; a self link is
+    dropped).  The graph is symmetrised and gets the identity; every link becomes a dense 3 x 3 block of values
+    -rng.random() (drawn in CSR order of the 3 nn x 3 nn pattern), the matrix is symmetrised by (A + A^T) / 2 and the
+    diagonal is set to (1 + excess) * sum |off-diagonal| of its row: strictly diagonally dominant, the smaller excess
+    the worse conditioned.  Returns int32 rowptr, int32 colind, float64 val with sorted columns."""
+    import scipy.sparse as sp
+    nn, stride = int(nn), int(stride)
+    if nn < 2 or not 0 < stride < nn or far_every < 1 or nfar < 0 or excess <= 0.0:
+        raise ValueError("node_graph_csr needs nn >= 2, 0 < stride < nn, far_every >= 1, nfar >= 0 and excess > 0")
+    rng = np.random.default_rng(seed)
+    i = np.arange(nn)
+    src, dst = [i[:-1], i[:-stride]], [i[1:], i[stride:]]
+    far = i[::far_every]
+    for _ in range(nfar):
+        src.append(far)
+        dst.append(rng.integers(0, nn, len(far)))
+    s, d = np.concatenate(src), np.concatenate(dst)
+    keep = s != d
+    G = sp.coo_matrix((np.ones(int(keep.sum())), (s[keep], d[keep])), shape=(nn, nn)).tocsr()
+    G = ((G + G.T) > 0).astype(np.float64) + sp.identity(nn, format="csr")
+    A = sp.kron(G, np.ones((3, 3)), format="csr")
+    A.sort_indices()
+    A.data = -rng.random(A.nnz)
+    A = sp.csr_matrix((A + A.T) * 0.5)
+    A.sort_indices()
+    rows = np.repeat(np.arange(3 * nn), np.diff(A.indptr))
+    on_diag = A.indices == rows
+    off = np.bincount(rows[~on_diag], weights=np.abs(A.data[~on_diag]), minlength=3 * nn)
+    A.data[on_diag] = (1.0 + excess) * off
+    return A.indptr.astype(np.int32), A.indices.astype(np.int32), np.ascontiguousarray(A.data, dtype=np.float64)
+
+
 def band_blocks_csr(blocks, seed, grading=0.0, shuffle=False, coupling=None):
     """Block-diagonal SPD matrix whose diagonal blocks have prescribed rows and bandwidth: `blocks` is a list of
     (rows b, bandwidth w), a w above b - 1 is clipped to b - 1.  Block q is L0 L0^T, symmetrised exactly (the upper
