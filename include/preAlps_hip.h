@@ -38,7 +38,8 @@ int preAlps_hip_panel_stride(int enlFac);
  * operator; the library itself never opens a socket: sums and halo rows go
  * through the two hooks, which the host binds to RCCL (torch.distributed
  * backend "nccl", MPI, ...).  Buffers handed to the hooks are device memory
- * and all work queued on preAlps_hip_get_stream() must be ordered before the
+ * (in plan-only mode, where there is no device, the one word on which the ranks
+ * agree about a refused start is host memory) and all work queued on preAlps_hip_get_stream() must be ordered before the
  * hook's own communication (the hook is responsible for that ordering). */
 typedef int (*preAlps_allreduce_fn)(void* ctx, double* dev_buf, int count);
 /* peers[i] sends recv_counts[i] doubles to us and gets send_counts[i] doubles
@@ -219,6 +220,10 @@ int preAlps_OperatorGetHaloPlan(int* npeers, int** peers, int** send_rows, int**
  * DESIGN section 5): local row r goes into the send-buffer slots slot_out[off_out[r] .. off_out[r + 1]).
  * off_out: m + 1 ints, slot_out: nsend ints (caller's arrays).  Works in plan-only mode. */
 int preAlps_hip_pack_map(int* off_out, int* slot_out);
+/* Where preAlps_ECGInitializeMulti / Guess put a local row at s columns per system: pcol[i] = p % s for a row of part
+ * p, p the global index of the part, so the shards of several processes hold slices of the one-process array.
+ * pcol: m ints (caller's array).  Works in plan-only mode. */
+int preAlps_hip_system_columns(int s, int* pcol);
 /* perm[new] = old, of the whole problem (library-owned, N ints). */
 int preAlps_OperatorGetPermPtr(int** perm, int* n);
 int preAlps_hip_nparts(void);
@@ -249,9 +254,21 @@ int preAlps_ECGSolve(preAlps_ECG_t* ecg, double* rhs, double* sol,
  * ||b_j - A x_j|| <= sqrt(s) * g_j (Cauchy-Schwarz); s = 1: they are equal.
  *   Refused (non-zero / abort, the message names the entry point): nrhs < 1 or enlFac % nrhs != 0; s larger than
  * the number of parts; ldrhs or ldsol < m; a right-hand side of norm zero (its columns of R0 would be empty);
- * ORTHODIR_FUSED (it decides inside preAlps_ECGIterate on one sum); more than one process and
- * preAlps_hip_loopback shards; preAlps_ECGFinalize and preAlps_ECGAdvance on a solver that holds more than one
- * system.  HIP graphs (preAlps_hip_graphs, PREALPS_ECG_GRAPH) and PREALPS_ECG_POLL are off for such a solver.
+ * ORTHODIR_FUSED (it decides inside preAlps_ECGIterate on one sum); preAlps_ECGFinalize and preAlps_ECGAdvance on a
+ * solver that holds more than one system.  HIP graphs (preAlps_hip_graphs, PREALPS_ECG_GRAPH) and PREALPS_ECG_POLL
+ * are off for such a solver.
+ *   Several processes (and a preAlps_hip_loopback shard, which rehearses one of them with empty collectives): as for
+ * preAlps_ECGSolve every rank passes its own m rows; rhs, x0 and sol are local.  sys_normb, the per-system histories,
+ * preAlps_ECGSystemResiduals, ecg->res and ecg->normb hold global values, equal on all ranks: the start sums b_j^2
+ * (and, with a guess, the columns of R0) over the ranks in one all-reduce, and in the iteration the k local sums ride
+ * behind the residual norm in the collective that carries it anyway (2 + k words where one system reduces its norm,
+ * the block beta and 2 + k words with the lazy stopping test), so an iteration gains no collective.  ORTHODIR and
+ * ORTHOMIN with NO_BS_RED.  Refused there as well: bs_red = ADAPT_BS with more than one system or a guess; an
+ * operator that was built before preAlps_hip_set_world / preAlps_hip_loopback changed the process group (the message
+ * is the one that asked for a single process).  A refusal that depends on one rank's arguments or resources (ldrhs,
+ * ldx0, locPbSize, an allocation) is agreed on by all ranks before any of them returns -- the rank at fault reports its
+ * reason, the others "another process of the group refused" -- and a norm that is zero or not finite is judged on
+ * the global sum: no rank is left waiting in a collective.
  *   Linearly dependent right-hand sides (a repeated load case, say) make P^T A P singular: keeping them apart is the
  * caller's business; bs_red = ADAPT_BS drops the directions that have become dependent. */
 int preAlps_ECGInitializeMulti(preAlps_ECG_t* ecg, int nrhs, const double* rhs, int ldrhs, int* rci_request);
@@ -284,8 +301,8 @@ int preAlps_ECGSolveMulti(preAlps_ECG_t* ecg, int nrhs, const double* rhs, int l
  * ecg->iter = 0, sol receives x0 bit for bit, and nothing of the iteration is queued, neither the block solve nor
  * the product.
  *   Refused (the message names the entry point): everything preAlps_ECGInitializeMulti refuses (nrhs, divisibility,
- * s against the number of parts, ldrhs, a right-hand side of norm zero, ORTHODIR_FUSED, more than one process, a
- * preAlps_hip_loopback shard); ldx0 < m; a start residual that is not finite (NaN or Inf in x0), which reports the
+ * s against the number of parts, ldrhs, a right-hand side of norm zero, ORTHODIR_FUSED; on several processes
+ * ADAPT_BS and a process group changed since the build); ldx0 < m; a start residual that is not finite (NaN or Inf in x0), which reports the
  * system; and a system whose r0_j is exactly zero beside one whose is not ("system %d starts with a zero residual
  * ..."): its columns of the block would be empty and P^T A P singular, as with a zero right-hand side.  A small but
  * nonzero start residual is no error: a system that starts at 1e-8 ||b_j|| iterates beside systems that start at

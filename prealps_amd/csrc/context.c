@@ -245,9 +245,14 @@ int preAlps_hip_comm_selftest(void) {
 int pa_world_rank(void) { return g_rank; }
 int pa_world_size(void) { return g_size; }
 
+/* collectives handed to the all-reduce hook so far (preAlps_hip_get_stat "allreduces") */
+static long long g_allreduces = 0;
+long long pa_allreduce_count(void) { return g_allreduces; }
+
 int pa_allreduce(double* dev_buf, int count) {
   if (g_size == 1 || count <= 0) return 0;
   if (!g_allreduce) return PA_FAIL("%d processes but no all-reduce hook (preAlps_hip_set_comm)", g_size);
+  ++g_allreduces;
   pa_time_begin(PA_T_COMM);
   int rc = g_allreduce(g_comm_ctx, dev_buf, count);
   pa_time_end(PA_T_COMM);

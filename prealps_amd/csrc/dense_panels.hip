@@ -240,14 +240,11 @@ __global__ __launch_bounds__(WG) void k_guess_start(int m, int k, int s, const d
   block_sum_cols<TS>(accr, rsums + (size_t)blockIdx.x * TS);
 }
 
-// The per-system sums of the stopping test: out[j] = sum over the s columns of system j (ascending) of the sum over
-// the blocks of rtr[blk*ts + c] (the column sums of R^2 an update kernel or k_colnorm2 left).  One workgroup; 16
-// threads per column take the blocks b = l, l + 16, ... in turn and are folded by a fixed tree, so the k values are
-// reproducible.  The values go to device memory and to pinned host words, which the host reads once the launch or
-// event behind this one has completed (it keys on nothing this kernel writes).
-__global__ __launch_bounds__(WG) void k_group_norms(const double* __restrict__ rtr, int nblk, int ts, int k, int s,
-                                                    double* __restrict__ out, double* host) {
-  __shared__ double red[WG];
+// The per-system sums of the stopping test: the sum over the s columns of system j (ascending) of the sum over the
+// blocks of rtr[blk*ts + c] (the column sums of R^2 an update kernel or k_colnorm2 left).  One workgroup; 16 threads
+// per column take the blocks b = l, l + 16, ... in turn and are folded by a fixed tree, so the k values are
+// reproducible.  group_fold: that sum in thread j < k (0 elsewhere); called by the whole workgroup, red: WG doubles.
+__device__ __forceinline__ double group_fold(const double* __restrict__ rtr, int nblk, int ts, int k, int s, double* red) {
   const int c = threadIdx.x >> 4, l = threadIdx.x & 15;
   double v = 0.0;
   if (c < k * s)
@@ -258,13 +255,46 @@ __global__ __launch_bounds__(WG) void k_group_norms(const double* __restrict__ r
     if (l < off) red[threadIdx.x] += red[threadIdx.x + off];
     __syncthreads();
   }
-  if (threadIdx.x < k) {
-    double g = 0.0;
+  double g = 0.0;
+  if (threadIdx.x < k)
     for (int q = 0; q < s; ++q) g += red[(threadIdx.x * s + q) << 4];
+  return g;
+}
+
+// One process: the values go to device memory and to pinned host words, which the host reads once the launch or
+// event behind this one has completed (it keys on nothing this kernel writes).
+__global__ __launch_bounds__(WG) void k_group_norms(const double* __restrict__ rtr, int nblk, int ts, int k, int s,
+                                                    double* __restrict__ out, double* host) {
+  __shared__ double red[WG];
+  const double g = group_fold(rtr, nblk, ts, k, s, red);
+  if (threadIdx.x < k) {
     out[threadIdx.x] = g;
     if (host) __hip_atomic_store(host + threadIdx.x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
   __threadfence_system();
+}
+
+// Several processes: the k sums are this process's share, so they go neither to the host nor to a buffer of their
+// own but behind the two words a collective of the iteration carries anyway: buf[0] = the local sum of squares of all
+// of R (g_0 + g_1 + ... in ascending j), buf[1] = the Cholesky status (*info, what k_trace_finish puts there),
+// buf[2 + j] = g_j.  One all-reduce of 2 + k words (or of the block in front of buf and these) then leaves the global
+// values on every process.
+__global__ __launch_bounds__(WG) void k_group_norms_ride(const double* __restrict__ rtr, int nblk, int ts, int k, int s,
+                                                         const int* __restrict__ info, double* __restrict__ buf) {
+  __shared__ double red[WG];
+  __shared__ double grp[16];
+  const double g = group_fold(rtr, nblk, ts, k, s, red);
+  if (threadIdx.x < k) {
+    grp[threadIdx.x] = g;
+    buf[2 + threadIdx.x] = g;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double all = 0.0;
+    for (int j = 0; j < k; ++j) all += grp[j];
+    buf[0] = all;
+    buf[1] = info ? (double)info[0] : 0.0;
+  }
 }
 
 // The finish: sol[row + j*ld] = sum of X(row, c) over the columns of system j, added in ascending c as k_rowsum does.
@@ -381,6 +411,13 @@ int pa_k_group_norms(const double* rtr_partials, int nblk, int ts, int k, int s,
   if (multi_args_bad("pa_k_group_norms", ts, k, s)) return 1;
   PA_LAUNCH(k_group_norms, dim3(1), dim3(WG), 0, cur_stream(), rtr_partials, nblk, ts, k, s, out, host);
   return kfail("k_group_norms");
+}
+
+int pa_k_group_norms_ride(const double* rtr_partials, int nblk, int ts, int k, int s, const int* info, double* buf) {
+  if (multi_args_bad("pa_k_group_norms_ride", ts, k, s)) return 1;
+  if (!buf) { pa_rt_set_error("pa_k_group_norms_ride: no buffer for the %d sums", k); return 1; }
+  PA_LAUNCH(k_group_norms_ride, dim3(1), dim3(WG), 0, cur_stream(), rtr_partials, nblk, ts, k, s, info, buf);
+  return kfail("k_group_norms_ride");
 }
 
 int pa_k_rowsum_groups(int m, int ts, int k, int s, const double* X, double* sol, int ld) {

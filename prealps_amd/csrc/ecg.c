@@ -113,6 +113,13 @@ typedef struct {
    * reaches the host through a later launch or event of the same stream.  h_grp[16..]: the start's ||b_j||^2. */
   int nrhs, sgrp;
   double* d_grp; double* h_grp;
+  /* Several systems on several processes (ride; a preAlps_hip_loopback shard of such a group too): the sums are this process's share.
+   * pa_k_group_norms_ride leaves them behind the pair [norm^2, potrf status] that a collective of the iteration
+   * carries anyway -- grp_dst: where it last wrote, the slot behind beta with the lazy stopping test, d_res2
+   * otherwise -- so that all-reduce grows by nrhs words and the iteration gains no collective; behind it the
+   * nrhs global sums are copied to h_grp ahead of the event the host waits for. */
+  int ride;
+  double* grp_dst;
   double sys_res[16], sys_normb[16];
   /* 1: started from an initial guess (preAlps_ECGInitializeGuess): X0 is in X and R0 = split(B - A X0).  The
    * iteration is unchanged; graphs and polling are off, and preAlps_ECGAdvance, which restarts from the right-hand
@@ -194,7 +201,7 @@ int _preAlps_ECGMalloc(preAlps_ECG_t* ecg) {
    * Orthomin needs no P_prev / AP_prev slots (ecg.c:55-61) */
   size_t panel = (size_t)(m > 0 ? m : 1) * ts;
   int nv = (ecg->ortho_alg == ORTHOMIN) ? 1 : 2;
-  size_t small = 5 * (size_t)T * T + 2 * (size_t)T * T /* q, scratch */ + 8 + 2 * (size_t)T * T /* uu */;
+  size_t small = 5 * (size_t)T * T + 2 * (size_t)T * T /* q, scratch */ + 24 /* res2: the pair + 16 sums */ + 2 * (size_t)T * T /* uu */;
   size_t parts = (size_t)pa_gram_max_blocks() * (2 * (size_t)ts * ts + ts);
   /* T = 4: the library's SpMM can form [AP | R]^T P while it computes AP (one block per workgroup) */
   pv->spmm_cap = (T == 4 && ts == 4) ? pa_operator_gram_blocks(ts) : 0;
@@ -218,7 +225,7 @@ int _preAlps_ECGMalloc(preAlps_ECG_t* ecg) {
   pv->d_F = w; pv->d_alpha = w; pv->d_beta = w + (size_t)T * T; pv->d_mu = w + 3 * (size_t)T * T;
   pv->d_rtr = w + 4 * (size_t)T * T; w += 5 * (size_t)T * T;
   pv->d_q = w; w += 2 * (size_t)T * T;
-  pv->d_res2 = w; w += 8;
+  pv->d_res2 = w; w += 24;
   pv->d_uu = w; w += 2 * (size_t)T * T;
   pv->d_partials = w; w += (size_t)pa_gram_max_blocks() * 2 * ts * ts;
   pv->d_rtr_part = w; w += (size_t)pa_gram_max_blocks() * ts;
@@ -259,6 +266,10 @@ static void request_gram_from_spmm(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
  * from an initial guess; metric: its stopping test is the caller's (preAlps_ECGSolveSystem). */
 static int reset_state(preAlps_ECG_t* ecg, ecg_priv_t* pv, int nrhs, int guess, int metric) {
   pv->nrhs = nrhs; pv->sgrp = ecg->enlFac / nrhs; pv->guess = guess; pv->metric = metric; pv->d_dl = NULL;
+  /* (a loopback shard of a group of ONE is a single process in every branch of the iteration -- pa_world_size() is
+   * what they read -- and has nothing to reduce: it keeps pa_k_group_norms and the pinned mirror) */
+  pv->ride = nrhs > 1 && !metric && pa_world_size() > 1;
+  pv->grp_dst = NULL;
   ecg->tot_t = ecg->comm_t = ecg->trsm_t = ecg->gemm_t = ecg->potrf_t = ecg->pstrf_t = 0.0;
   ecg->lapmt_t = ecg->gesvd_t = ecg->geqrf_t = ecg->ormqr_t = ecg->copy_t = 0.0;
   int M = ecg->globPbSize, m = ecg->locPbSize, t = ecg->enlFac, ts = pv->ts;
@@ -414,15 +425,53 @@ int preAlps_ECGInitialize(preAlps_ECG_t* ecg, double* rhs, int* rci_request) {
  * asked of it; pa_k_guess_start writes R0 = the split of b_j - (the sum of system j's columns of A X0) and leaves the
  * sums of b_j^2 and of R0(:, c)^2; the Z panel and the partial sums are zeroed again, so the pool is what reset_state
  * leaves but for X and R.  Every later update keeps sum_c R(:, c) = b_j - A sum_c X(:, c).  who: the entry point the
- * refusals name. */
+ * refusals name.
+ *   Several processes: every rank passes its own rows, A X0 is the distributed product, the start's local sums are
+ * reduced in one all-reduce, and in the iteration the per-system sums ride on the collective of the residual norm
+ * (pv->ride); what one rank alone can find wrong is agreed on before any rank returns (ranks_agree). */
 #define FAIL_AS(who, ...) pa_fail_at(who, __VA_ARGS__)
-static int queue_group_norms(preAlps_ECG_t* ecg, ecg_priv_t* pv);
+static int queue_group_norms(preAlps_ECG_t* ecg, ecg_priv_t* pv, double* dst);
 /* The caller's own system (preAlps_ECGSolveSystem, preAlps_OperatorSystemResiduals): b and x0 hold the rows in the order
  * and units of the matrix the operator was built from, on the host or (device) on the device.  pa_k_sys_gather fills
  * the staging arrays d_B / d_X0 that the host path uploads into -- b' = dl * b[src], x0' = x0[src] / dl -- and leaves
  * the caller's ||b_j||^2; what follows the uploads is the same code.  metric: the stopping test is the caller's;
  * probe: only the start's norms are wanted, so a system that starts at exactly zero is no refusal. */
 typedef struct { const double* b; int ldb; const double* x0; int ldx0; int device, metric, probe; } sys_in_t;
+/* The column of its system that every local row starts in: p % s for a row of part p, p the GLOBAL index of the part
+ * (part0 .. part1 - 1 on this process; rowPos is global, row_off the first row owned), so that the shards of several
+ * processes together hold the placement of one process.  pcol: m ints. */
+static void system_columns(const pa_operator_info_t* op, int s, int* pcol) {
+  for (int p = op->part0; p < op->part1; ++p) {
+    int base = op->rowPos[p] - op->row_off, l = op->rowPos[p + 1] - op->rowPos[p];
+    for (int i = 0; i < l; ++i) pcol[base + i] = p % s;
+  }
+}
+int preAlps_hip_system_columns(int s, int* pcol) {
+  const pa_operator_info_t* op = pa_operator_info();
+  if (!op) return PA_FAIL("the operator must be built first");
+  if (s < 1 || !pcol) return PA_FAIL(" wrong test 's >= 1 && pcol != NULL'");
+  system_columns(op, s, pcol);
+  return 0;
+}
+/* Collective over the process group: 1 on every process as soon as `bad` is nonzero on one (a max of one flag, as a
+ * sum through the all-reduce hook; pa_mpi_agree when the library runs under its own MPI binding).  One process, and
+ * the rehearsal of one shard, have nobody to ask.  The word is device memory like everything the hook is handed; in
+ * plan-only mode, where there is no device, it is a host word.  word: a device word the caller already holds (the
+ * solver's pool), NULL: one is allocated.  The collective is entered whatever the upload of the flag returned -- a
+ * process whose copy failed reports its failure afterwards, its peers are not left waiting for it; only a process
+ * that holds no word and cannot allocate one (8 bytes) has nothing to hand to the hook and fails alone. */
+static int ranks_agree(int bad, double* word) {
+  if (pa_world_size() == 1 || pa_comm_is_loopback()) return bad != 0;
+  if (pa_mpi_active()) return pa_mpi_agree(bad);
+  double h = bad ? 1.0 : 0.0;
+  if (pa_operator_plan_only()) return pa_allreduce(&h, 1) || h != 0.0;
+  double* d = word ? word : (double*)pa_rt_malloc(sizeof(double));
+  if (!d) return 1;
+  const int up = pa_rt_h2d(d, &h, sizeof(double));
+  const int rc = pa_allreduce(d, 1) || up || pa_rt_d2h(&h, d, sizeof(double));
+  if (!word) pa_rt_free(d);
+  return rc || h != 0.0;
+}
 static int start_systems(const char* who, preAlps_ECG_t* ecg, int nrhs, const double* rhs, int ldrhs,
                          const double* x0, int ldx0, int* rci_request, const sys_in_t* sys) {
   const pa_operator_info_t* op = pa_operator_info();
@@ -435,16 +484,40 @@ static int start_systems(const char* who, preAlps_ECG_t* ecg, int nrhs, const do
   if (op->nparts < s)
     return FAIL_AS(who, "Enlarging factor per system must be lower than the number of processors"
                    " in the MPI communicator! size: %d ; enlarging factor per system: %d", op->nparts, s);
-  if (!sys && ldrhs < m) return FAIL_AS(who, "ldrhs = %d is smaller than the %d local rows", ldrhs, m);
-  if (!sys && x0 && ldx0 < m) return FAIL_AS(who, "ldx0 = %d is smaller than the %d local rows", ldx0, m);
+  /* Several processes (multi; the one-shard rehearsal of preAlps_hip_loopback counts as one of several): every rank
+   * passes its own rows.  What a rank finds wrong with ITS arguments or resources is a local verdict (bad): it does
+   * not return on it but takes it to ranks_agree, so that either every rank goes on or every rank returns the refusal
+   * and none is left waiting in a collective.  One process: every refusal returns at once, as it always did. */
+  const int multi = pa_world_size() > 1 || pa_comm_is_loopback();
+  int bad = 0;
+  if (!sys && ldrhs < m) bad = FAIL_AS(who, "ldrhs = %d is smaller than the %d local rows", ldrhs, m);
+  else if (!sys && x0 && ldx0 < m) bad = FAIL_AS(who, "ldx0 = %d is smaller than the %d local rows", ldx0, m);
+  if (bad && !multi) return 1;
   if (ecg->ortho_alg == ORTHODIR_FUSED)
     return FAIL_AS(who, "ORTHODIR_FUSED decides inside preAlps_ECGIterate on one sum: no per-system stopping test");
-  if (pa_world_size() > 1 || pa_comm_is_loopback())
-    return FAIL_AS(who, "%s need a single process (%d processes%s)",
+  /* the caller's own system states global rows; and a shard cut for another process group (the operator was built
+   * before preAlps_hip_set_world / preAlps_hip_loopback changed it) holds other rows than the sums would assume */
+  if (multi && (sys || op->world != pa_world_size() || op->rank != pa_world_rank() || op->loopback != pa_comm_is_loopback()))
+    return FAIL_AS(who, "%s need a single process (%d processes%s)%s",
                    sys ? "the caller's own system, its row map and its norms"
                        : x0 ? "an initial guess and several right-hand sides" : "several right-hand sides", pa_world_size(),
+                   pa_comm_is_loopback() ? ", preAlps_hip_loopback shard" : "",
+                   sys ? "" : " or an operator built by the process group as it is now");
+  if (multi && ecg->bs_red != NO_BS_RED && (k > 1 || x0))
+    return FAIL_AS(who, "block-size reduction (ADAPT_BS) with %s needs a single process (%d processes%s)",
+                   x0 ? "an initial guess" : "several right-hand sides", pa_world_size(),
                    pa_comm_is_loopback() ? ", preAlps_hip_loopback shard" : "");
-  if (_preAlps_ECGMalloc(ecg)) return 1;
+  if (multi) {
+    if (!bad && ecg->locPbSize != m) bad = FAIL_AS(who, "locPbSize %d differs from the operator's %d rows", ecg->locPbSize, m);
+    /* (plan-only mode has no device: the verdicts on the arguments are agreed on, then the start is refused) */
+    const int have = !bad && !pa_operator_plan_only() && _preAlps_ECGMalloc(ecg) == 0;
+    if (!bad && !pa_operator_plan_only() && !have) bad = 1;
+    if (ranks_agree(bad, have ? priv_of(ecg)->d_grp + 47 : NULL)) {    /* (a word of the pool; reset_state zeroes it again) */
+      if (have) _preAlps_ECGFree(ecg);
+      return bad ? 1 : FAIL_AS(who, "another process of the group refused this start (its own message says why)");
+    }
+    if (pa_operator_plan_only()) return FAIL_AS(who, "the operator was built in plan-only mode (no GPU)");
+  } else if (_preAlps_ECGMalloc(ecg)) return 1;
   ecg_priv_t* pv = priv_of(ecg);
   if (k == 1 && !x0 && !sys) {
     if (_preAlps_ECGReset(ecg, (double*)rhs, rci_request)) { _preAlps_ECGFree(ecg); return 1; }
@@ -458,7 +531,11 @@ static int start_systems(const char* who, preAlps_ECG_t* ecg, int nrhs, const do
     _preAlps_ECGFree(ecg);
     return FAIL_AS(who, "locPbSize %d differs from the operator's %d rows", ecg->locPbSize, m);
   }
-  if (reset_state(ecg, pv, k, x0 != NULL, sys && sys->metric)) { _preAlps_ECGFree(ecg); return 1; }
+  /* from here on every process of several holds a solver, and a failure of its own (rc) travels: to ranks_agree ahead
+   * of the product of a guess, whose halo exchange the peers would wait in, and as the first word of the one
+   * all-reduce of the start's sums */
+  int rc = reset_state(ecg, pv, k, x0 != NULL, sys && sys->metric) ? 1 : 0, nblk = 0;
+  if (rc && !multi) { _preAlps_ECGFree(ecg); return 1; }
   const int* d_src = NULL;
   if (sys) {
     if (pa_operator_system_map(&d_src, &pv->d_dl)) { _preAlps_ECGFree(ecg); return 1; }
@@ -471,16 +548,15 @@ static int start_systems(const char* who, preAlps_ECG_t* ecg, int nrhs, const do
   /* the caller's host arrays go up as they are, then through the gather; device arrays are gathered where they lie */
   double* d_raw = (sys && !sys->device) ? (double*)pa_rt_malloc(mm * cols * sizeof(double)) : NULL;
   double* h_b1 = (sys && k == 1) ? (double*)malloc(mm * sizeof(double)) : NULL;    /* (see the sum of one system below) */
-  int rc = 0, nblk = 0;
-  if (!pcol || !d_B || (sys && !sys->device && !d_raw) || (sys && k == 1 && !h_b1))
+  /* several processes: the local sums of b_j^2 and of R0(:, c)^2 go into d_red[1 ..) (device only), where one
+   * all-reduce takes them; one process: into d_grp and its pinned mirror, as ever */
+  double* const d_red = pv->d_grp;
+  if (!rc && (!pcol || !d_B || (sys && !sys->device && !d_raw) || (sys && k == 1 && !h_b1)))
     rc = FAIL_AS(who, "staging %d right-hand sides: %s", k, pcol ? pa_rt_error() : "out of host memory");
   if (!rc) {
     int* d_pcol = (int*)(d_B + mm * cols);
     double* d_X0 = x0 ? d_B + mm * k : NULL;
-    for (int p = op->part0; p < op->part1; ++p) {
-      int base = op->rowPos[p] - op->row_off, l = op->rowPos[p + 1] - op->rowPos[p];
-      for (int i = 0; i < l; ++i) pcol[base + i] = p % s;
-    }
+    system_columns(op, s, pcol);
     rc = pa_rt_h2d(d_pcol, pcol, (size_t)m * sizeof(int));
     if (sys) {
       const double* gb = sys->b; const double* gx = x0;
@@ -497,47 +573,71 @@ static int start_systems(const char* who, preAlps_ECG_t* ecg, int nrhs, const do
     else for (int j = 0; j < k && !rc; ++j) rc = pa_rt_h2d(d_B + (size_t)j * m, rhs + (size_t)j * ldrhs, (size_t)m * sizeof(double));
     if (!x0) {
       rc = rc || pa_k_multi_start(m, pv->ts, k, s, d_B, m, d_pcol, pv->d_R, pv->d_rtr_part, &nblk) ||
-           pa_k_group_norms(pv->d_rtr_part, nblk, pv->ts, k, 1, pv->d_grp + 16, pv->h_grp + 16) || pa_rt_sync();
+           pa_k_group_norms(pv->d_rtr_part, nblk, pv->ts, k, 1, multi ? d_red + 1 : pv->d_grp + 16, multi ? NULL : pv->h_grp + 16) ||
+           pa_rt_sync();
       if (rc) rc = FAIL_AS(who, "%s", pa_rt_error());
     } else {
-      const size_t panel = mm * pv->ts;
       /* (the caller's system: the gather has filled d_X0) */
       if (!sys && ldx0 == m) rc = rc || pa_rt_h2d(d_X0, x0, (size_t)m * k * sizeof(double));
       else if (!sys) for (int j = 0; j < k && !rc; ++j) rc = pa_rt_h2d(d_X0 + (size_t)j * m, x0 + (size_t)j * ldx0, (size_t)m * sizeof(double));
       rc = rc || pa_k_guess_split(m, pv->ts, k, s, d_X0, m, d_pcol, pv->d_X);
       if (rc) rc = FAIL_AS(who, "%s", pa_rt_error());
-      /* a plain product: nothing is armed for X -> Z, and reset_done has not asked the SpMM for a block yet */
-      if (!rc) rc = preAlps_BlockOperator(ecg->X, ecg->Z);
-      if (!rc) {
-        rc = pa_k_guess_start(m, pv->ts, k, s, d_B, m, d_pcol, pv->buf_z, pv->d_R, pv->d_partials, pv->d_rtr_part, &nblk) ||
-             pa_k_group_norms(pv->d_partials, nblk, pv->ts, k, 1, pv->d_grp + 16, pv->h_grp + 16) ||
-             pa_k_group_norms(pv->d_rtr_part, nblk, pv->ts, k, s, pv->d_grp, pv->h_grp) ||
-             /* the scratch as reset_state left it: the first update relies on empty panels, padding included */
-             pa_rt_memset(pv->buf_z, 0, panel * sizeof(double)) ||
-             pa_rt_memset(pv->d_partials, 0, (size_t)nblk * pv->ts * sizeof(double)) || pa_rt_sync();
-        if (rc) rc = FAIL_AS(who, "%s", pa_rt_error());
-      }
     }
-    /* one system: its scaled right-hand side comes back for the host sum below (m doubles, once per solve) */
-    if (!rc && h_b1 && pa_rt_d2h(h_b1, d_B, (size_t)m * sizeof(double))) rc = FAIL_AS(who, "%s", pa_rt_error());
   }
+  if (x0) {
+    /* A X0 is the distributed product, with its halo exchange: no process enters it unless all of them do */
+    if (multi && ranks_agree(rc, d_red + 47)) {
+      if (!rc) FAIL_AS(who, "another process of the group could not stage its rows (its own message says why)");
+      pa_rt_free(d_B); pa_rt_free(d_raw); free(pcol); free(h_b1);
+      _preAlps_ECGFree(ecg);
+      return 1;
+    }
+    /* a plain product: nothing is armed for X -> Z, and reset_done has not asked the SpMM for a block yet */
+    if (!rc) rc = preAlps_BlockOperator(ecg->X, ecg->Z);
+    if (!rc) {
+      const size_t panel = mm * pv->ts;
+      const int* d_pcol = (const int*)(d_B + mm * cols);
+      rc = pa_k_guess_start(m, pv->ts, k, s, d_B, m, d_pcol, pv->buf_z, pv->d_R, pv->d_partials, pv->d_rtr_part, &nblk) ||
+           pa_k_group_norms(pv->d_partials, nblk, pv->ts, k, 1, multi ? d_red + 1 : pv->d_grp + 16, multi ? NULL : pv->h_grp + 16) ||
+           pa_k_group_norms(pv->d_rtr_part, nblk, pv->ts, k, s, multi ? d_red + 1 + k : pv->d_grp, multi ? NULL : pv->h_grp) ||
+           /* the scratch as reset_state left it: the first update relies on empty panels, padding included */
+           pa_rt_memset(pv->buf_z, 0, panel * sizeof(double)) ||
+           pa_rt_memset(pv->d_partials, 0, (size_t)nblk * pv->ts * sizeof(double)) || pa_rt_sync();
+      if (rc) rc = FAIL_AS(who, "%s", pa_rt_error());
+    }
+  }
+  /* one system: its scaled right-hand side comes back for the host sum below (m doubles, once per solve) */
+  if (!rc && h_b1 && pa_rt_d2h(h_b1, d_B, (size_t)m * sizeof(double))) rc = FAIL_AS(who, "%s", pa_rt_error());
   pa_rt_free(d_B);
   pa_rt_free(d_raw);
   free(pcol);
-  double r2 = 0.0;
+  double r2 = 0.0, nb1 = 0.0;
+  if (!rc && k == 1) {   /* one system: the sum of _preAlps_ECGReset, part by part on the host, so ecg->normb has its bits */
+    const double* hb = sys ? h_b1 : rhs;
+    for (int p = op->part0; p < op->part1; ++p) {
+      int base = op->rowPos[p] - op->row_off, l = op->rowPos[p + 1] - op->rowPos[p];
+      double sp = 0.0;
+      for (int i = 0; i < l; ++i) { double v = hb[base + i]; sp += v * v; }
+      nb1 += sp;
+    }
+    if (!multi) pv->h_grp[16] = nb1;
+  }
+  if (multi) {
+    /* ONE all-reduce of [a process failed | b_0^2 .. b_k-1^2 | with a guess: r0_0^2 .. r0_k-1^2]: behind it every
+     * process holds the same words, and every verdict below -- a right-hand side or a start residual that is zero or
+     * not finite (a NaN in one process's rows is a NaN in the sum) -- falls alike on all of them */
+    double h[1 + 2 * 16];
+    const int nred = 1 + k * (x0 ? 2 : 1), mine = rc;
+    h[0] = mine ? 1.0 : 0.0; h[1] = nb1;
+    /* (the collective is entered whatever the upload returned: a process whose copy failed says so afterwards) */
+    const int up = pa_rt_h2d(d_red, h, (k == 1 && !mine ? 2 : 1) * sizeof(double));
+    if (pa_allreduce(d_red, nred) || up || pa_rt_d2h(h, d_red, (size_t)nred * sizeof(double)))
+      rc = mine ? 1 : FAIL_AS(who, "%s", pa_rt_error());
+    else if (h[0] != 0.0) rc = mine ? 1 : FAIL_AS(who, "another process of the group could not form its start (its own message says why)");
+    for (int j = 0; j < k && !rc; ++j) { pv->h_grp[16 + j] = h[1 + j]; if (x0) pv->h_grp[j] = h[1 + k + j]; }
+  }
   if (!rc) {
     double nb2 = 0.0;
-    if (k == 1) {   /* one system: the sum of _preAlps_ECGReset, part by part on the host, so ecg->normb has its bits */
-      const double* hb = sys ? h_b1 : rhs;
-      for (int p = op->part0; p < op->part1; ++p) {
-        int base = op->rowPos[p] - op->row_off, l = op->rowPos[p + 1] - op->rowPos[p];
-        double sp = 0.0;
-        for (int i = 0; i < l; ++i) { double v = hb[base + i]; sp += v * v; }
-        nb2 += sp;
-      }
-      pv->h_grp[16] = nb2;
-      nb2 = 0.0;
-    }
     for (int j = 0; j < k && !rc; ++j) {
       const double b2 = pv->h_grp[16 + j];
       if (sys && !(b2 - b2 == 0.0)) rc = FAIL_AS(who, "right-hand side %d is not finite (NaN or Inf in b)", j);
@@ -565,7 +665,7 @@ static int start_systems(const char* who, preAlps_ECG_t* ecg, int nrhs, const do
   }
   if (!rc && pv->metric) {
     /* the caller's metric: both sides of every test in the caller's units, the start's included */
-    if (queue_group_norms(ecg, pv) || pa_rt_sync()) rc = FAIL_AS(who, "%s", pa_rt_error());
+    if (queue_group_norms(ecg, pv, NULL) || pa_rt_sync()) rc = FAIL_AS(who, "%s", pa_rt_error());
     for (int j = 0; j < k && !rc; ++j) {
       pv->sys_normb[j] = sqrt(pv->h_grp[32 + j]);
       pv->sys_res[j] = sqrt(pv->h_grp[j]);
@@ -656,8 +756,13 @@ static int stopping_end(preAlps_ECG_t* ecg, ecg_priv_t* pv, int* stop);
  * iteration's R, on the same stream (the update kernels of fused_update, update_iterate and solve_first_step; in
  * stopping_queue nothing has touched R since); R never takes part in the rotation of the direction panels, and its
  * pointer is taken from the descriptor at the moment of the launch. */
-static int queue_group_norms(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
-  if (pv->metric) {
+/* Several processes (pv->ride): the sums are local, and go behind the pair [norm^2, status] at `dst` that the next
+ * collective carries (d_res2, or the slot behind beta when the norm is summed with beta); dst is unused otherwise. */
+static int queue_group_norms(preAlps_ECG_t* ecg, ecg_priv_t* pv, double* dst) {
+  if (pv->ride) {
+    PA_CHECK(pa_k_group_norms_ride(pv->d_rtr_part, pv->rtr_nblk, pv->ts, pv->nrhs, pv->sgrp, pv->d_info, dst));
+    pv->grp_dst = dst;
+  } else if (pv->metric) {
     int nb = 0;
     const int k = pv->nrhs > 1 ? pv->nrhs : 1;
     PA_CHECK(pa_k_sys_norms(pv->m, pv->ts, k, pv->sgrp, ecg->R->val, pv->d_dl, pv->d_sys_part, &nb));
@@ -669,10 +774,29 @@ static int queue_group_norms(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
 static int stopping_queue(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
   int T = ecg->enlFac;
   int single = pa_world_size() == 1;
+  if (pv->ride) {
+    /* several systems on several processes: pa_k_group_norms_ride has left [norm^2, status | g_0^2 .. g_k-1^2] of
+     * this process at grp_dst behind the last update (from R itself when nothing is left of one); ONE all-reduce
+     * of 2 + k words where one system reduces its norm, and the k global sums follow the pair to the host */
+    if (!pv->rtr_valid) {
+      PA_CHECK(pa_k_colnorm2(pv->m, pv->ts, pv->d_R, pv->d_rtr_part, &pv->rtr_nblk));
+      if (queue_group_norms(ecg, pv, pv->d_res2)) return 1;
+    }
+    double* src = pv->grp_dst;
+    double t0;
+    TIC(PA_T_COMM);
+    if (pa_allreduce(src, 2 + pv->nrhs)) return 1;
+    TAC(PA_T_COMM, comm_t);
+    PA_CHECK(pa_rt_d2h_async(pv->h_pin, src, 2 * sizeof(double)));
+    PA_CHECK(pa_rt_d2h_async(pv->h_grp, src + 2, (size_t)pv->nrhs * sizeof(double)));
+    pv->wait_seq = pv->sent_seq = 0.0;
+    pv->rtr_valid = 0;
+    return 0;
+  }
   if (pv->rtr_valid < 2) {
     if (!pv->rtr_valid) {
       PA_CHECK(pa_k_colnorm2(pv->m, pv->ts, pv->d_R, pv->d_rtr_part, &pv->rtr_nblk));
-      if (queue_group_norms(ecg, pv)) return 1;
+      if (queue_group_norms(ecg, pv, NULL)) return 1;
     }
     if (single && pv->rtr_valid == 1) {
       /* column sums left by the update kernel (lazy stopping test), one process: the sum goes straight to
@@ -912,7 +1036,7 @@ static int fused_update(preAlps_ECG_t* ecg, ecg_priv_t* pv, int t, const double*
                             pv->lazy_ptr ? pv->lazy_ptr : pv->d_res2, pv->d_info, single ? pv->h_pin : NULL,
                             gram, pv->lazy_norm ? pv->d_uu + (size_t)pv->uu_cur * T * T : NULL));
   pv->rtr_nblk = nb;
-  if (queue_group_norms(ecg, pv)) return 1;
+  if (queue_group_norms(ecg, pv, defer ? pv->lazy_ptr : pv->d_res2)) return 1;
   TAC(PA_T_UPDATE, trsm_t);
   pv->rtr_valid = defer ? 1 : 2;
   return 0;
@@ -927,7 +1051,7 @@ static int update_iterate(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
   PA_CHECK(pa_k_update_xr(pv->m, pv->ts, ecg->P->info.n, ecg->X->info.n, pv->d_alpha, ecg->P->val,
                           ecg->AP->val, pv->d_X, pv->d_R, pv->d_rtr_part, &pv->rtr_nblk, ecg->enlFac,
                           pv->d_res2, pv->d_info, pa_world_size() == 1 ? pv->h_pin : NULL));
-  if (queue_group_norms(ecg, pv)) return 1;
+  if (queue_group_norms(ecg, pv, pv->d_res2)) return 1;
   TAC(PA_T_UPDATE, gemm_t);
   pv->rtr_valid = 2;
   pv->lazy_ptr = NULL;
@@ -1006,14 +1130,18 @@ static int orthogonalise_z(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
     if (pv->rtr_valid == 2 && pv->lazy_ptr == pv->d_beta + cnt) {
       /* the norm of the new residual (and the Cholesky status) ride along; the update kernel
        * below passes them on to the pinned words the host reads (a copy here costs a launch and
-       * 8 us of idle stream behind it) */
-      if (pa_allreduce(pv->d_beta, cnt + 2)) return 1;
+       * 8 us of idle stream behind it);
+       * several systems on several processes: their k local sums lie right behind the pair
+       * (pa_k_group_norms_ride), ride in the same collective, and reach h_grp ahead of the event below */
+      if (pa_allreduce(pv->d_beta, cnt + 2 + (pv->ride ? pv->nrhs : 0))) return 1;
+      if (pv->ride) PA_CHECK(pa_rt_d2h_async(pv->h_grp, pv->lazy_ptr + 2, (size_t)pv->nrhs * sizeof(double)));
       note = pv->lazy_ptr;
       pv->rtr_valid = 0;
     } else {
       if (pa_allreduce(pv->d_beta, cnt)) return 1;
       if (pv->lazy_ptr && pv->rtr_valid == 2) {   /* (beta not where expected: reduce the norm by itself) */
-        if (pa_allreduce(pv->lazy_ptr, 1)) return 1;
+        if (pa_allreduce(pv->lazy_ptr, pv->ride ? 2 + pv->nrhs : 1)) return 1;
+        if (pv->ride) PA_CHECK(pa_rt_d2h_async(pv->h_grp, pv->lazy_ptr + 2, (size_t)pv->nrhs * sizeof(double)));
         PA_CHECK(pa_rt_d2h_async(pv->h_pin, pv->lazy_ptr, 2 * sizeof(double)));
         PA_CHECK(pa_rt_event_record(pv->ev_res));
         pv->wait_seq = 0.0;
@@ -1386,7 +1514,7 @@ void preAlps_ECGPrint(preAlps_ECG_t* ecg, int verbosity) {
  * that order forms the first alpha of the next call with pa_k_gram_finish, and so must this one to give the same
  * bits; a call therefore returns in the state "AP = A P is queued" of the RCI protocol (rci 0), as it always did. */
 static int solve_first_applies(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
-  return g_own_loop > 0 && ecg->P->info.n == 4 && pv->ts == 4 &&
+  return g_own_loop > 0 && ecg->P->info.n == 4 && pv->ts == 4 && !pv->ride &&      /* (ride: several processes) */
          solve_first_rule(pv->solve_first, pa_world_size(), ecg->ortho_alg, ecg->bs_red, ecg->enlFac, pv->fuse,
                           pv->lazy_norm, pv->lazy_stop, pv->bj_cap > 0, pv->spmm_cap > 0, pv->use_graphs);
 }
@@ -1432,7 +1560,7 @@ static int solve_first_step(preAlps_ECG_t* ecg, ecg_priv_t* pv, int ahead, int* 
                            ecg->beta->info.lda, pv->d_uu + (size_t)(1 - pv->uu_cur) * T * T));
   TAC(PA_T_UPDATE, trsm_t);
   pv->rtr_nblk = nb;
-  if (queue_group_norms(ecg, pv)) return 1;
+  if (queue_group_norms(ecg, pv, NULL)) return 1;      /* (never pv->ride: solve_first_applies) */
   pv->uu_cur ^= 1;
   ecg->iter++;
   /* the norm of the new residual (and the Cholesky status) straight to the pinned words the host reads */

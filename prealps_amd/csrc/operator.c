@@ -290,6 +290,7 @@ static int build_panel(pa_operator_t* o, const int* rp, const int* ci, const dou
   const int N = in->N, nparts = in->nparts, rank = pa_world_rank(), size = pa_world_size();
   in->part0 = (int)((long long)rank * nparts / size);
   in->part1 = (int)((long long)(rank + 1) * nparts / size);
+  in->rank = rank; in->world = size; in->loopback = pa_comm_is_loopback();
   in->row_off = in->rowPos[in->part0];
   int m = in->rowPos[in->part1] - in->row_off;
   in->m = m;
@@ -1297,6 +1298,7 @@ int preAlps_hip_get_stat(const char* key, double* value) {
   else if (!strcmp(key, "ecg_graph_captures")) *value = (double)pa_ecg_graph_count(0);
   else if (!strcmp(key, "ecg_graph_replays")) *value = (double)pa_ecg_graph_count(1);
   else if (!strcmp(key, "packs_fused")) *value = (double)g_packs_fused;
+  else if (!strcmp(key, "allreduces")) *value = (double)pa_allreduce_count();
   else if (!strcmp(key, "spmm_slices")) *value = o->plan.nslices;
   else if (!strcmp(key, "spmm_stored_entries")) *value = o->sell_entries;
   else if (!strcmp(key, "spmm_stream_bytes")) *value = o->stream_bytes;

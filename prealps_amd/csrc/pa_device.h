@@ -247,6 +247,9 @@ int pa_k_guess_start(int m, int ts, int k, int s, const double* B, int ldb, cons
 /* out[j] = sum over the columns of system j (ascending) of the sum over the blocks of rtr_partials[blk*ts + c],
  * one workgroup, fixed order; host (pinned, device-visible, may be NULL) receives the same k values. */
 int pa_k_group_norms(const double* rtr_partials, int nblk, int ts, int k, int s, double* out, double* host);
+/* The same k sums for a collective to carry (several processes): buf[2 + j] = the sum of system j, buf[0] = their sum
+ * in ascending j (the local sum of squares of all of R), buf[1] = *info (NULL: 0); buf: 2 + k doubles on the device. */
+int pa_k_group_norms_ride(const double* rtr_partials, int nblk, int ts, int k, int s, const int* info, double* buf);
 /* sol[i + j*ld] = sum of X[i][c] over the columns of system j, ascending c (pa_k_rowsum per system). */
 int pa_k_rowsum_groups(int m, int ts, int k, int s, const double* X, double* sol, int ld);
 /* ---- the caller's own system (dense_system.hip; preAlps_ECGSolveSystem) ----

@@ -33,6 +33,7 @@ int pa_world_size(void);
 int pa_comm_is_loopback(void);
 /* sum a device buffer over the processes (no-op for one process) */
 int pa_allreduce(double* dev_buf, int count);
+long long pa_allreduce_count(void);   /* calls of the all-reduce hook so far */
 int pa_exchange(const double* dev_send, const int* send_counts, double* dev_recv,
                 const int* recv_counts, const int* peers, int npeers);
 
@@ -65,6 +66,8 @@ typedef struct {
   int N;            /* global rows */
   int nparts;       /* subdomains (the reference's ranks) */
   int part0, part1; /* parts owned by this process: [part0, part1) */
+  int rank, world;  /* the process group the shard was cut for (pa_world_rank / pa_world_size at the build) ... */
+  int loopback;     /* ... and whether it was a preAlps_hip_loopback rehearsal */
   int row_off;      /* first global row owned */
   int m;            /* local rows */
   int* rowPos;      /* nparts + 1, global */

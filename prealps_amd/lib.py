@@ -82,7 +82,7 @@ EXPORTS = [
     "preAlps_hip_nd_selfcheck", "preAlps_hip_loopback", "preAlps_hip_graphs", "preAlps_hip_ecg_solve_first",
     "preAlps_hip_set_nd_precision", "preAlps_hip_set_band_precision",
     "preAlps_ECGInitializeMulti", "preAlps_ECGSystemResiduals", "preAlps_ECGFinalizeMulti", "preAlps_ECGSolveMulti",
-    "preAlps_ECGInitializeGuess", "preAlps_ECGSolveGuess",
+    "preAlps_ECGInitializeGuess", "preAlps_ECGSolveGuess", "preAlps_hip_system_columns",
     "preAlps_OperatorUpdateValues", "preAlps_BlockJacobiUpdateValues",
     "preAlps_OperatorGetScalingPtr", "preAlps_ECGSolveSystem", "preAlps_OperatorSystemResiduals",
     "preAlps_BlockJacobiSetCoarseSpace", "preAlps_BlockJacobiClearCoarseSpace",
@@ -127,6 +127,7 @@ def load():
     L.preAlps_ECGInitializeGuess.argtypes = [pe, C.c_int, pd, C.c_int, pd, C.c_int, pi]
     L.preAlps_ECGSolveGuess.argtypes = [pe, C.c_int, pd, C.c_int, pd, C.c_int, pd, C.c_int, pd, pi, pd, pd, pd,
                                         C.c_int, pi]
+    L.preAlps_hip_system_columns.argtypes = [C.c_int, pi]
     # b, x0, x: host or device addresses (PREALPS_SYS_DEVICE), so plain pointers
     L.preAlps_ECGSolveSystem.argtypes = [pe, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                          C.c_int, pd, pi, pd, pd, pd, C.c_int, pi]

@@ -621,7 +621,12 @@ class EcgProblem:
         stopping test uses.  ||b_j - A x_j|| <= sqrt(t / k) * sys_res[j] in exact arithmetic.
         X0 (m x k): a starting value for every system (preAlps_ECGSolveGuess); sys_res0 then holds the k residual
         norms the iteration starts from, and a guess that already meets every threshold comes back as x after no
-        iteration.  X0 = None is preAlps_ECGSolveMulti as before."""
+        iteration.  X0 = None is preAlps_ECGSolveMulti as before.
+        On a distributed problem B, X0 and x hold this rank's m rows; sys_normb, sys_hist, sys_res0, res and normb are
+        global and equal on all ranks.  What the library refuses (PreAlpsError) is raised on every rank.  The shape
+        checks of this method (ValueError) are made before the library is entered and are this rank's alone: a rank
+        that fails them never joins the collective start, so the caller must pass well-shaped arrays on every rank
+        (each rank can test its own against prob.m beforehand)."""
         Bs = np.shape(B)
         if len(Bs) != 2:
             raise ValueError("B must be two-dimensional (m x k), not of shape %r" % (Bs,))
