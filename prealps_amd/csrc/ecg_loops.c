@@ -1,0 +1,411 @@
+/*
+ * ecg_loops.c -- the library's own driver loops around the RCI iteration of ecg.c: the graph segments, the
+ * iteration with the block solve first, and preAlps_ECGSolve / SolveMulti / SolveGuess / SolveSystem / Advance.
+ */
+#include <string.h>
+
+#include "ecg_priv.h"
+
+/* Z = M^-1 R for Orthomin, Z = M^-1 AP otherwise */
+static int apply_preconditioner(preAlps_ECG_t* ecg) {
+  return preAlps_BlockJacobiApply(ecg->ortho_alg == ORTHOMIN ? ecg->R : ecg->AP, ecg->Z);
+}
+
+/* ---- graph segments ------------------------------------------------------------------------
+ * seg_begin .. seg_end bracket the host code of one segment.  First pass of a (segment, phase): the
+ * code runs as it is.  Second pass: the stream is captured while it runs (nothing executes), the
+ * graph is instantiated and launched.  From then on the host code still runs -- it rotates
+ * pointers and counts -- with every launch suppressed (pa_rt_skip), and the graph is launched in
+ * its place: one launch instead of three to six per segment. */
+static long long g_graph_captures, g_graph_replays;     /* segments captured / graphs launched so far, all solvers */
+long long pa_ecg_graph_count(int which) { return which ? g_graph_replays : g_graph_captures; }
+static int seg_begin(ecg_priv_t* pv, int seg) {
+  if (!pv->use_graphs || pa_timing_enabled()) return 0;    /* (phase timers put events between the launches) */
+  if (pv->bj_epoch != pa_bj_apply_epoch()) {
+    /* the preconditioner was created again, or its coarse space set or cleared, since the capture: the graphs hold
+     * the old launches and pointers (the entry that changed them has drained the stream), so capture anew */
+    for (int a = 0; a < 2; ++a) for (int b = 0; b < 6; ++b) { pa_rt_graph_free(pv->graph[a][b]); pv->graph[a][b] = NULL; pv->seen[a][b] = 0; }
+    pv->bj_epoch = pa_bj_apply_epoch();
+  }
+  if (pv->graph[seg][pv->phase]) { pa_rt_skip(1); return 2; }
+  if (pv->seen[seg][pv->phase]++ == 0) return 0;
+  if (pa_rt_capture_begin()) { pv->use_graphs = 0; return 0; }   /* (nothing queued yet: go on without graphs) */
+  return 1;
+}
+static int seg_end(ecg_priv_t* pv, int seg, int mode, int body_rc) {
+  if (mode == 2) pa_rt_skip(0);
+  if (mode == 1) {
+    void* exec = NULL;
+    int rc = pa_rt_capture_end(&exec);
+    if (rc || body_rc) { pa_rt_graph_free(exec); return PA_FAIL("capturing an iteration segment failed: %s", pa_rt_error()); }
+    pv->graph[seg][pv->phase] = exec;
+    ++g_graph_captures;
+  }
+  if (body_rc) return 1;
+  if (mode && pa_rt_graph_launch(pv->graph[seg][pv->phase])) return PA_FAIL("%s", pa_rt_error());
+  if (mode) ++g_graph_replays;
+  return 0;
+}
+/* One full iteration from the state "AP = A P is there" (rci 0) to the same state: the order of
+ * examples/test_ecg_prealps_op.c:208-221 with the apply, the second half and the product queued
+ * before the host looks at the residual norm (they do not touch X or R and are unused after a stop). */
+static int graph_iteration(preAlps_ECG_t* ecg, ecg_priv_t* pv, int* rci_request, int* stop) {
+  int mode = seg_begin(pv, 0);
+  int rc = preAlps_ECGIterate(ecg, rci_request) || pa_ecg_stopping_queue(ecg, pv);
+  if (seg_end(pv, 0, mode, rc)) return 1;
+  PA_CHECK(pa_rt_event_record(pv->ev_res));
+  mode = seg_begin(pv, 1);
+  rc = apply_preconditioner(ecg) || preAlps_ECGIterate(ecg, rci_request) || preAlps_BlockOperator(ecg->P, ecg->AP);
+  if (seg_end(pv, 1, mode, rc)) return 1;
+  pv->phase = (pv->phase + 1) % 6;
+  return pa_ecg_stopping_end(ecg, pv, stop);
+}
+
+/* ---- solve first ---------------------------------------------------------------------------------------------
+ * With lazy normalisation the block solve Z = M^-1 AP reads the raw AP, which the update of X and R does not touch,
+ * and both Gram blocks come from raw panels: [AP | R]^T P from the SpMM, [AP | AP_prev]^T Z from the block solve.
+ * So the library's own loops can run an Orthodir iteration as
+ *   SpMM + Gram -> block solve + Gram -> one finish (U, alpha, beta) -> one row pass (X, R, Z and the column sums
+ *   of R^2) -> the norm to the host,
+ * five launches instead of six, with P read once.  Every operation and every sum is that of _preAlps_ECGIterateOdir,
+ * in the same order: the results are bitwise the same.  The host must know the norm of R_k+1 before it queues the
+ * row pass of the next iteration (it overwrites X and R), so the product, the block solve and the finish of that
+ * iteration go out behind the norm before the host waits for it (pv->sf_ready).  After a stop they are unused: they
+ * only wrote AP, Z and the Gram blocks, which a restart writes anew.  The last step of a call queues the product
+ * only, as the other order does: leaving the library's loop ends the Gram request of the SpMM (pa_ecg_leave_own_loop), so
+ * that order forms the first alpha of the next call with pa_k_gram_finish, and so must this one to give the same
+ * bits; a call therefore returns in the state "AP = A P is queued" of the RCI protocol (rci 0), as it always did. */
+static int solve_first_applies(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
+  return pa_ecg_in_own_loop() > 0 && ecg->P->info.n == 4 && pv->ts == 4 && !pv->ride &&      /* (ride: several processes) */
+         pa_ecg_solve_first_rule(pv->solve_first, pa_world_size(), ecg->ortho_alg, ecg->bs_red, ecg->enlFac, pv->fuse,
+                                 pv->lazy_norm, pv->lazy_stop, pv->bj_cap > 0, pv->spmm_cap > 0, pv->use_graphs);
+}
+/* From "AP = A P is queued": the block solve and one launch that sums both Gram blocks -- U = chol(W) and alpha
+ * (fused_gram) and beta (orthogonalise_z).  A product or a block solve that did not leave its block behind: the
+ * block is formed here, as those two do it. */
+static int sf_queue_solve(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
+  int m = pv->m, ts = pv->ts, t = 4, T = ecg->enlFac;
+  double t0;
+  pa_k_bj_gram_arm(pv->buf_av[0], pv->buf_z, pv->buf_av[1], pv->d_bj_parts, pv->bj_cap);
+  if (preAlps_BlockJacobiApply(ecg->AP, ecg->Z)) return 1;
+  int from_spmm = pa_k_spmm_gram_take(ecg->P->val, ecg->AP->val);
+  int from_bj = pa_k_bj_gram_take(pv->buf_av[0], pv->buf_z);
+  double* spmm_scratch = pv->d_spmm_parts + (size_t)pv->spmm_cap * 32;
+  double* bj_scratch = pv->d_bj_parts + (size_t)pv->bj_cap * 32;
+  TIC(PA_T_GRAM);
+  if (from_spmm && from_bj) {
+    PA_CHECK(pa_k_finish32_pair(pv->d_spmm_parts, from_spmm, spmm_scratch, t, T, pv->d_q, pv->d_mu, pv->d_alpha,
+                                pv->d_info, pv->d_bj_parts, from_bj, bj_scratch, pv->d_beta));
+  } else {
+    if (from_spmm) PA_CHECK(pa_k_finish32(pv->d_spmm_parts, from_spmm, spmm_scratch, t, T, pv->d_q, pv->d_mu, pv->d_alpha,
+                                         pv->d_info));
+    else PA_CHECK(pa_k_gram_finish(m, ts, ecg->AP->val, pv->d_R, ecg->P->val, pv->d_partials, t, T, t, pv->d_q, t + T,
+                                   t, T, pv->d_mu, pv->d_alpha, pv->d_info));
+    if (from_bj) PA_CHECK(pa_k_finish32(pv->d_bj_parts, from_bj, bj_scratch, 0, 0, pv->d_beta, NULL, NULL, NULL));
+    else PA_CHECK(pa_k_gram_finish(m, ts, pv->buf_av[0], pv->buf_av[1], pv->buf_z, pv->d_partials, t, t, t,
+                                   pv->d_beta, 2 * t, 0, 0, NULL, NULL, NULL));
+  }
+  TAC(PA_T_GRAM, gemm_t);
+  pv->sf_ready = 1;
+  return 0;
+}
+/* One full iteration: the row pass, the norm to the host, the next iteration's product (ahead: and its block solve
+ * and finish), then the stopping test. */
+static int solve_first_step(preAlps_ECG_t* ecg, ecg_priv_t* pv, int ahead, int* stop) {
+  int t = 4, T = ecg->enlFac, nb = 0;
+  double tg = pa_wtime(), t0;
+  if (!pv->sf_ready && sf_queue_solve(ecg, pv)) return 1;
+  pv->sf_ready = 0;
+  TIC(PA_T_UPDATE);
+  PA_CHECK(pa_k_update_xrz(pv->m, pv->ts, t, pv->d_mu, pv->d_alpha, ecg->P->val, ecg->AP->val, pv->buf_v[1], pv->d_X,
+                           pv->d_R, pv->buf_z, pv->d_rtr_part, &nb, pv->d_uu + (size_t)pv->uu_cur * T * T, pv->d_beta,
+                           ecg->beta->info.lda, pv->d_uu + (size_t)(1 - pv->uu_cur) * T * T));
+  TAC(PA_T_UPDATE, trsm_t);
+  pv->rtr_nblk = nb;
+  if (pa_ecg_queue_group_norms(ecg, pv, NULL)) return 1;      /* (never pv->ride: solve_first_applies) */
+  pv->uu_cur ^= 1;
+  ecg->iter++;
+  /* the norm of the new residual (and the Cholesky status) straight to the pinned words the host reads */
+  pv->wait_seq = 0.0;
+  if (pv->poll) { pv->wait_seq = (pv->seq += 1.0); pa_k_note_seq(pv->wait_seq); }
+  PA_CHECK(pa_k_trace_finish(pv->d_rtr_part, nb, pv->ts, T, pv->d_res2, pv->d_info, pv->h_pin));
+  if (!pv->poll) PA_CHECK(pa_rt_event_record(pv->ev_res));
+  pv->rtr_valid = RTR_NONE; pv->sent_seq = 0.0; pv->lazy_ptr = NULL;
+  if (pa_ecg_shift_directions(ecg, pv, t)) return 1;
+  pa_ecg_request_gram_from_spmm(ecg, pv);
+  if (preAlps_BlockOperator(ecg->P, ecg->AP)) return 1;
+  if (ahead && sf_queue_solve(ecg, pv)) return 1;
+  ecg->tot_t += pa_wtime() - tg;
+  return pa_ecg_stopping_end(ecg, pv, stop);
+}
+
+/* one entry of the histories after a stopping test */
+static void record_hist(preAlps_ECG_t* ecg, const multi_args_t* mu, double* res_hist, int* bs_hist, int max_hist,
+                        int nh) {
+  if (nh >= max_hist) return;
+  if (res_hist) { res_hist[nh] = ecg->res; if (bs_hist) bs_hist[nh] = ecg->bs; }
+  if (mu->nrhs > 0 && mu->sys_hist) {
+    ecg_priv_t* pv = priv_of(ecg);
+    for (int j = 0; j < mu->nrhs; ++j)
+      mu->sys_hist[nh + (size_t)j * max_hist] = (pv && (pv->nrhs > 1 || pv->metric)) ? pv->sys_res[j] : ecg->res;
+  }
+}
+/* The start's norms go where the caller asked for them; *live becomes 1 when a system is above its threshold. */
+static int start_norms(preAlps_ECG_t* ecg, const multi_args_t* mu, int* live) {
+  double g0[16], nb[16];
+  if (preAlps_ECGSystemResiduals(ecg, g0, nb)) return 1;
+  for (int j = 0; j < mu->nrhs; ++j) {
+    if (mu->sys_normb) mu->sys_normb[j] = nb[j];
+    if (mu->sys_res0) mu->sys_res0[j] = g0[j];
+    if (g0[j] > nb[j] * ecg->tol) *live = 1;
+  }
+  return 0;
+}
+/* The driver loop of examples/test_ecg_prealps_op.c:203-223 (fused:
+ * examples/test_ecg_bench_fused.c:243-259). */
+static int ecg_solve_loop(preAlps_ECG_t* ecg, double* rhs, double* sol, double* res_hist, int* bs_hist,
+                          int max_hist, int* n_hist, const multi_args_t* mu) {
+  int rci = 0, stop = 0, nh = 0;
+  if (mu->sys) {
+    int live = mu->sys->x0 == NULL;
+    if (pa_ecg_start_systems("preAlps_ECGSolveSystem", ecg, mu->nrhs, NULL, 0, mu->sys->x0, mu->sys->ldx0, &rci, mu->sys)) return 1;
+    if (start_norms(ecg, mu, &live)) return 1;
+    if (!live) {
+      /* every system meets its threshold, in the metric of the test, as it stands: x0 is the answer, bit for bit */
+      if (n_hist) *n_hist = 0;
+      return pa_ecg_finish_system(ecg, mu, 1);
+    }
+  } else if (mu->nrhs > 0 && mu->x0) {
+    int live = 0;
+    if (preAlps_ECGInitializeGuess(ecg, mu->nrhs, rhs, mu->ldrhs, mu->x0, mu->ldx0, &rci)) return 1;
+    if (start_norms(ecg, mu, &live)) return 1;
+    if (!live) {
+      /* every system meets its threshold as it stands: x0 is the answer, bit for bit, and nothing is queued */
+      if (n_hist) *n_hist = 0;
+      if (sol) {
+        const size_t m = (size_t)ecg->locPbSize;
+        for (int j = 0; j < mu->nrhs; ++j)
+          memcpy(sol + (size_t)j * mu->ldsol, mu->x0 + (size_t)j * mu->ldx0, m * sizeof(double));
+        _preAlps_ECGFree(ecg);
+      }
+      return 0;
+    }
+  } else if (mu->nrhs > 0) {
+    if (preAlps_ECGInitializeMulti(ecg, mu->nrhs, rhs, mu->ldrhs, &rci)) return 1;
+    if (mu->sys_normb && preAlps_ECGSystemResiduals(ecg, NULL, mu->sys_normb)) return 1;
+    if (mu->sys_res0 && preAlps_ECGSystemResiduals(ecg, NULL, mu->sys_res0)) return 1;   /* (a cold start: ||b_j||) */
+  } else if (preAlps_ECGInitialize(ecg, rhs, &rci)) return 1;
+  if (preAlps_BlockJacobiApply(ecg->R, ecg->P)) return 1;
+  ecg_priv_t* pvg = priv_of(ecg);
+  if (pvg && pvg->use_graphs) {
+    if (preAlps_BlockOperator(ecg->P, ecg->AP)) return 1;
+    while (stop != 1) {
+      if (graph_iteration(ecg, pvg, &rci, &stop)) return 1;
+      record_hist(ecg, mu, res_hist, bs_hist, max_hist, nh);
+      ++nh;
+    }
+  } else if (pvg && ecg->ortho_alg != ORTHODIR_FUSED && solve_first_applies(ecg, pvg)) {
+    if (preAlps_BlockOperator(ecg->P, ecg->AP)) return 1;
+    while (stop != 1) {
+      if (solve_first_step(ecg, pvg, 1, &stop)) return 1;
+      record_hist(ecg, mu, res_hist, bs_hist, max_hist, nh);
+      ++nh;
+    }
+  } else if (ecg->ortho_alg != ORTHODIR_FUSED) {
+    if (preAlps_BlockOperator(ecg->P, ecg->AP)) return 1;
+    while (stop != 1) {
+      if (preAlps_ECGIterate(ecg, &rci)) return 1;
+      if (rci == 0) {
+        if (preAlps_BlockOperator(ecg->P, ecg->AP)) return 1;
+      } else if (rci == 1) {
+        /* same calls as the reference loop; the apply is queued before the host waits for
+         * the residual norm (it does not depend on it and is simply unused after a stop) */
+        ecg_priv_t* pv = priv_of(ecg);
+        if (!pv) return PA_FAIL("solver not initialised");
+        if (pv->z_ready) {
+          /* D-Odir at full width: the first half already queued the block solve (behind which the host looked at
+           * alpha); the second half and the product go out before the host waits for the norm, as below */
+          pv->z_ready = 0;
+          if (pa_ecg_stopping_begin(ecg, pv)) return 1;
+          if (preAlps_ECGIterate(ecg, &rci)) return 1;
+          if (preAlps_BlockOperator(ecg->P, ecg->AP)) return 1;
+        } else if (pv->lazy_stop && pv->lazy_ptr) {
+          /* several processes: the norm travels with the beta all-reduce of the second half;
+           * the half-step and the product queued before the decision are unused after a stop */
+          if (apply_preconditioner(ecg)) return 1;
+          if (preAlps_ECGIterate(ecg, &rci)) return 1;
+          if (preAlps_BlockOperator(ecg->P, ecg->AP)) return 1;
+        } else {
+          if (pa_ecg_stopping_begin(ecg, pv)) return 1;
+          if (apply_preconditioner(ecg)) return 1;
+        }
+        if (pa_ecg_stopping_end(ecg, pv, &stop)) return 1;
+        record_hist(ecg, mu, res_hist, bs_hist, max_hist, nh);
+        ++nh;
+        if (stop == 1) break;
+      }
+    }
+  } else {
+    while (rci != 1) {
+      if (preAlps_BlockOperator(ecg->P, ecg->AP)) return 1;
+      if (preAlps_BlockJacobiApply(ecg->AP, ecg->Z)) return 1;
+      if (preAlps_ECGIterate(ecg, &rci)) return 1;
+      record_hist(ecg, mu, res_hist, bs_hist, max_hist, nh);
+      ++nh;
+    }
+  }
+  if (n_hist) *n_hist = nh < max_hist ? nh : max_hist;
+  if (mu->sys) return pa_ecg_finish_system(ecg, mu, 0);
+  if (sol) return mu->nrhs > 0 ? preAlps_ECGFinalizeMulti(ecg, sol, mu->ldsol) : preAlps_ECGFinalize(ecg, sol);
+  return 0;
+}
+/* ecg_solve_loop as the library's own loop (see g_own_loop in ecg.c) */
+static int solve_in_own_loop(preAlps_ECG_t* ecg, double* rhs, double* sol, double* res_hist, int* bs_hist,
+                             int max_hist, int* n_hist, const multi_args_t* mu) {
+  pa_ecg_enter_own_loop();
+  int rc = ecg_solve_loop(ecg, rhs, sol, res_hist, bs_hist, max_hist, n_hist, mu);
+  pa_ecg_leave_own_loop();
+  return rc;
+}
+
+int preAlps_ECGSolve(preAlps_ECG_t* ecg, double* rhs, double* sol, double* res_hist, int* bs_hist,
+                     int max_hist, int* n_hist) {
+  const multi_args_t one = {.nrhs = 0};
+  return solve_in_own_loop(ecg, rhs, sol, res_hist, bs_hist, max_hist, n_hist, &one);
+}
+/* preAlps_ECGInitializeMulti, the loop of preAlps_ECGSolve (the same body, so the same branch of it for the same
+ * settings), preAlps_ECGFinalizeMulti. */
+int preAlps_ECGSolveMulti(preAlps_ECG_t* ecg, int nrhs, const double* rhs, int ldrhs, double* sol, int ldsol,
+                          double* res_hist, int* bs_hist, double* sys_hist, double* sys_normb,
+                          int max_hist, int* n_hist) {
+  const pa_operator_info_t* op = pa_operator_info();
+  if (nrhs < 1) return PA_FAIL("nrhs = %d: at least one right-hand side is needed", nrhs);
+  if (sol && op && ldsol < op->m) return PA_FAIL("ldsol = %d is smaller than the %d local rows", ldsol, op->m);
+  const multi_args_t mu = {.nrhs = nrhs, .ldrhs = ldrhs, .ldsol = ldsol, .sys_hist = sys_hist, .sys_normb = sys_normb};
+  return solve_in_own_loop(ecg, (double*)rhs, sol, res_hist, bs_hist, max_hist, n_hist, &mu);
+}
+/* The same around preAlps_ECGInitializeGuess; x0 = NULL: preAlps_ECGSolveMulti (sys_res0 then receives ||b_j||).
+ * A guess under which every system already meets its threshold comes back as the solution, with no iteration. */
+int preAlps_ECGSolveGuess(preAlps_ECG_t* ecg, int nrhs, const double* rhs, int ldrhs, const double* x0, int ldx0,
+                          double* sol, int ldsol, double* res_hist, int* bs_hist, double* sys_hist, double* sys_normb,
+                          double* sys_res0, int max_hist, int* n_hist) {
+  const pa_operator_info_t* op = pa_operator_info();
+  if (nrhs < 1) return PA_FAIL("nrhs = %d: at least one right-hand side is needed", nrhs);
+  if (sol && op && ldsol < op->m) return PA_FAIL("ldsol = %d is smaller than the %d local rows", ldsol, op->m);
+  const multi_args_t mu = {.nrhs = nrhs, .ldrhs = ldrhs, .ldsol = ldsol, .sys_hist = sys_hist, .sys_normb = sys_normb,
+                           .x0 = x0, .ldx0 = ldx0, .sys_res0 = sys_res0};
+  return solve_in_own_loop(ecg, (double*)rhs, sol, res_hist, bs_hist, max_hist, n_hist, &mu);
+}
+/* preAlps_ECGSolveGuess around the gather and the scatter: A x = b as the caller stated it (one process: N = m). */
+int preAlps_ECGSolveSystem(preAlps_ECG_t* ecg, int nrhs, const double* b, int ldb, const double* x0, int ldx0, double* x,
+                           int ldx, int flags, double* res_hist, int* bs_hist, double* sys_hist, double* sys_normb,
+                           double* sys_res, int max_hist, int* n_hist) {
+  const pa_operator_info_t* op = pa_operator_info();
+  if (!op) return PA_FAIL("the operator must be built before the solver");
+  if (!ecg || !b || !x) return PA_FAIL(" wrong test 'ecg != NULL && b != NULL && x != NULL'");
+  if (nrhs < 1) return PA_FAIL("nrhs = %d: at least one right-hand side is needed", nrhs);
+  if (flags & ~(PREALPS_SYS_DEVICE | PREALPS_SYS_STOP_ORIGINAL)) return PA_FAIL("flags = %d holds unknown bits", flags);
+  if (ldb < op->N) return PA_FAIL("ldb = %d is smaller than the %d rows of the matrix", ldb, op->N);
+  if (x0 && ldx0 < op->N) return PA_FAIL("ldx0 = %d is smaller than the %d rows of the matrix", ldx0, op->N);
+  if (ldx < op->N) return PA_FAIL("ldx = %d is smaller than the %d rows of the matrix", ldx, op->N);
+  const sys_in_t in = {b, ldb, x0, ldx0, (flags & PREALPS_SYS_DEVICE) != 0, (flags & PREALPS_SYS_STOP_ORIGINAL) != 0, 0};
+  const multi_args_t mu = {.nrhs = nrhs, .sys_hist = sys_hist, .sys_normb = sys_normb, .sys = &in, .sys_x = x, .sys_ldx = ldx,
+                           .sys_res = sys_res};
+  return solve_in_own_loop(ecg, NULL, NULL, res_hist, bs_hist, max_hist, n_hist, &mu);
+}
+
+/* The tail of a restart in preAlps_ECGAdvance: count it, keep what the finished solve reached, start again from the
+ * same rhs up to "AP = A P is queued"; fused: Orthodir fused, whose loop queues the product itself. */
+static int restart(preAlps_ECG_t* ecg, double* rhs, int* rci_request, int* restarts, int* last_iters, double* last_res,
+                   int fused) {
+  if (restarts) ++*restarts;
+  if (last_iters) *last_iters = ecg->iter;
+  if (last_res) *last_res = ecg->res;
+  if (_preAlps_ECGReset(ecg, rhs, rci_request)) return 1;
+  if (preAlps_BlockJacobiApply(ecg->R, ecg->P)) return 1;
+  if (!fused && preAlps_BlockOperator(ecg->P, ecg->AP)) return 1;
+  return 0;
+}
+/* Advance the driver loop (examples/test_ecg_prealps_op.c:208-221) by nsteps full
+ * iterations, restarting from the same rhs (as after preAlps_ECGInitialize) whenever the
+ * stopping test fires; what bench.py times. */
+static int ecg_advance_loop(preAlps_ECG_t* ecg, double* rhs, int* rci_request, int nsteps, int* restarts,
+                            int* last_iters, double* last_res) {
+  int stop = 0, done = 0;
+  if (ecg->ortho_alg == ORTHODIR_FUSED) {
+    /* the loop of examples/test_ecg_bench_fused.c:252-259: one reduction per iteration; *rci_request
+     * becomes 1 when converged (then: restart from the same rhs) */
+    while (done < nsteps) {
+      if (preAlps_BlockOperator(ecg->P, ecg->AP)) return 1;
+      if (preAlps_BlockJacobiApply(ecg->AP, ecg->Z)) return 1;
+      if (preAlps_ECGIterate(ecg, rci_request)) return 1;
+      ++done;
+      if (*rci_request == 1 && restart(ecg, rhs, rci_request, restarts, last_iters, last_res, 1)) return 1;
+    }
+    return 0;
+  }
+  {
+    ecg_priv_t* pvg = priv_of(ecg);
+    if (pvg && pvg->use_graphs && *rci_request == 0) {
+      while (done < nsteps) {
+        if (graph_iteration(ecg, pvg, rci_request, &stop)) return 1;
+        ++done;
+        if (stop == 1 && restart(ecg, rhs, rci_request, restarts, last_iters, last_res, 0)) return 1;
+      }
+      return 0;
+    }
+    if (pvg && *rci_request == 0 && solve_first_applies(ecg, pvg)) {
+      while (done < nsteps) {
+        if (solve_first_step(ecg, pvg, done + 1 < nsteps, &stop)) return 1;
+        ++done;
+        if (stop == 1 && restart(ecg, rhs, rci_request, restarts, last_iters, last_res, 0)) return 1;
+      }
+      return 0;
+    }
+  }
+  while (done < nsteps) {
+    if (preAlps_ECGIterate(ecg, rci_request)) return 1;
+    if (*rci_request == 0) {
+      if (preAlps_BlockOperator(ecg->P, ecg->AP)) return 1;
+      ++done;
+    } else {
+      /* queue the stopping test, then the preconditioner apply of this iteration, and only
+       * then wait for the norm: the apply does not depend on it and is discarded on stop */
+      ecg_priv_t* pv = priv_of(ecg);
+      if (!pv) return PA_FAIL("solver not initialised");
+      int early = pv->z_ready;
+      int lazy = early || (pv->lazy_stop && pv->lazy_ptr);
+      if (lazy) {   /* see preAlps_ECGSolve */
+        if (early) { pv->z_ready = 0; if (pa_ecg_stopping_begin(ecg, pv)) return 1; }
+        else if (apply_preconditioner(ecg)) return 1;
+        if (preAlps_ECGIterate(ecg, rci_request)) return 1;
+        if (preAlps_BlockOperator(ecg->P, ecg->AP)) return 1;
+      } else {
+        if (pa_ecg_stopping_begin(ecg, pv)) return 1;
+        if (apply_preconditioner(ecg)) return 1;
+      }
+      if (pa_ecg_stopping_end(ecg, pv, &stop)) return 1;
+      if (lazy && stop != 1) ++done;
+      if (stop == 1) {
+        if (restart(ecg, rhs, rci_request, restarts, last_iters, last_res, 0)) return 1;
+        ++done;
+        continue;
+      }
+    }
+  }
+  return 0;
+}
+int preAlps_ECGAdvance(preAlps_ECG_t* ecg, double* rhs, int* rci_request, int nsteps, int* restarts,
+                       int* last_iters, double* last_res) {
+  ecg_priv_t* pvm = priv_of(ecg);
+  if (pvm && pvm->guess)
+    return PA_FAIL("the solver was started from an initial guess: a restart from the right-hand side alone would drop "
+                   "x0 (use preAlps_ECGSolveGuess or the caller's own loop, or _preAlps_ECGReset for a cold start)");
+  if (pvm && pvm->nrhs > 1)
+    return PA_FAIL("the solver holds %d systems: restarts from one right-hand side are not defined for it "
+                   "(use preAlps_ECGSolveMulti or the caller's own loop)", pvm->nrhs);
+  pa_ecg_enter_own_loop();
+  int rc = ecg_advance_loop(ecg, rhs, rci_request, nsteps, restarts, last_iters, last_res);
+  pa_ecg_leave_own_loop();
+  return rc;
+}

@@ -1,7 +1,7 @@
 /*
  * pa_host.h -- internal declarations shared by the C host sources of
- * libprealps_hip.so (context.c, operator.c, block_jacobi.c, ecg.c).  spmm_plan.c stands apart: it
- * includes spmm_plan.h only.
+ * libprealps_hip.so (context.c, operator.c, block_jacobi.c, and the solver: ecg.c, ecg_start.c, ecg_loops.c,
+ * which share ecg_priv.h).  spmm_plan.c and ecg_plan.c stand apart: each includes its own header only.
  */
 #ifndef PA_HOST_H
 #define PA_HOST_H
@@ -124,7 +124,7 @@ double pa_bj_setup_seconds(int which);   /* 0: ordering + band Cholesky, 1: swee
 int pa_bj_nparts(void);
 int pa_bj_nd_blocks(void);
 int pa_bj_nd_precision(void);       /* storage of the sparse factors (64 / 32), 0 if no block has one */
-long long pa_ecg_graph_count(int which);   /* 0: iteration segments captured so far, 1: graphs launched (ecg.c) */
+long long pa_ecg_graph_count(int which);   /* 0: iteration segments captured so far, 1: graphs launched (ecg_loops.c) */
 int pa_bj_apply_epoch(void);       /* + 1 per change of what preAlps_BlockJacobiApply launches or reads (create, free, coarse space) */
 int pa_bj_gram_blocks(void);       /* blocks of an apply that can leave [in | prev]^T out behind (0: cannot) */
 double pa_bj_g4_bytes(void);        /* bytes of the one-copy records of bj_g4.hip as stored (fp64 / fp32), 0 if absent */
