@@ -5,10 +5,8 @@
  * Reference behaviour kept (all under /root/reference):
  *   preAlps_OperatorBuild      utils/operator.c:38-134    load -> scale ->
  *                              partition -> permute -> row panels
- *   MatrixMarket reader        utils/cplm_light/cplm_matcsr.c:96-243
- *   SymRACScaling              utils/cplm_light/cplm_matcsr.c:1461-1554
- *   ordering from a partition  utils/cplm_v0/cplm_v0_metis_utils.c:22-43,197-222
- *   symmetric permutation      utils/cplm_v0/cplm_v0_matcsr.c:941-1022
+ *   MatrixMarket reader        mtx_read.c
+ *   scaling, ordering, panel   op_build.c (the shard of this process on the host; adopt_shard takes it over)
  *   preAlps_BlockOperator      utils/operator.c:334-351 ->
  *                              utils/cplm_v0/cplm_v0_matmult_v2.c:108-343
  *   getters                    utils/operator.c:353-393
@@ -19,16 +17,16 @@
  * whole panels); the O(m*P) colPos table is replaced by row blocks with an
  * interior / halo-reading split so the exchange overlaps the interior SpMM.
  */
-#include <ctype.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
-#include <sys/mman.h>
 #include <stdlib.h>
 #include <string.h>
-#include <strings.h>
 
 #include "pa_host.h"
+#include "mtx_read.h"
+#include "op_build.h"
+#include "pa_alloc.h"
 #include "spmm_plan.h"
 
 typedef struct {
@@ -88,29 +86,6 @@ static size_t g_dbg_val_bytes, g_dbg_slot_bytes;   /* device bytes of the run pl
 static int env_int(const char* name, int dflt) {
   const char* s = getenv(name);
   return (s && *s) ? atoi(s) : dflt;
-}
-
-typedef struct { int c; int k; double v; } cv_t;   /* k: where the value came from (preAlps_OperatorUpdateValues) */
-static int cmp_cv(const void* a, const void* b) {
-  int ca = ((const cv_t*)a)->c, cb = ((const cv_t*)b)->c;
-  return (ca > cb) - (ca < cb);
-}
-
-static int owner_of_part(int p, int nparts, int size) {
-  /* process g owns parts [g*nparts/size, (g+1)*nparts/size) */
-  int g = (int)(((long long)p * size) / nparts);
-  while (g + 1 < size && (long long)(g + 1) * nparts / size <= p) ++g;
-  while (g > 0 && (long long)g * nparts / size > p) --g;
-  return g;
-}
-
-static int part_of_row(const int* rowPos, int nparts, int row) {
-  int lo = 0, hi = nparts; /* rowPos[lo] <= row < rowPos[hi] */
-  while (hi - lo > 1) {
-    int mid = (lo + hi) / 2;
-    if (rowPos[mid] <= row) lo = mid; else hi = mid;
-  }
-  return lo;
 }
 
 /* --------------------------------------------------------------- free ---- */
@@ -204,506 +179,103 @@ static int g_plan_only = 0;
 void preAlps_hip_plan_only(int on) { g_plan_only = on ? 1 : 0; }
 int pa_operator_plan_only(void) { return g_plan_only; }
 
-/* ---- the build, in three steps ------------------------------------------------------------
- * (1) order_and_scale: what needs the whole matrix -- the diagonal check, the scaling vector of
+/* ---- the build, in three steps (op_build.c: the shard on the host) --------------------------
+ * (1) pa_op_order: what needs the whole matrix -- the diagonal check, the scaling vector of
  *     SymRACScaling and the ordering that groups rows part by part (rank 0 only when the set-up is
  *     distributed);
- * (2) build_panel: this process's row panel from its raw rows (scaled, renumbered, sorted), the
+ * (2) pa_op_panel: this process's row panel from its raw rows (scaled, renumbered, sorted), the
  *     halo slots and who owns them;
- * (3) the send lists: from the whole matrix when every process holds it, else by asking the
- *     owners (pa_mpi_swap_lists);  then the upload. */
-#define TRACE_DECL double t_tr = pa_wtime(); const int tr = getenv("PREALPS_SETUP_TRACE") != NULL
+ * (3) the send lists: from the whole matrix when every process holds it (pa_op_peers_whole), else by
+ *     asking the owners (pa_mpi_swap_lists, pa_op_finish_peers);
+ * then adopt_shard: the upload, and the finished shard into g_op. */
+static int setup_trace(void) { return getenv("PREALPS_SETUP_TRACE") != NULL; }
+#define TRACE_DECL double t_tr = pa_wtime(); const int tr = setup_trace()
 #define TRACE(what) do { if (tr) { double n_ = pa_wtime(); fprintf(stderr, "[setup] %-28s %.3f s\n", what, n_ - t_tr); t_tr = n_; } } while (0)
 
-static int order_and_scale(int N, const int* rowPtr, const int* colInd, const double* val, int nparts,
-                           const int* part, int scale, pa_operator_info_t* in, double** d_out, int** iperm_out) {
-  TRACE_DECL;
-  {
-    int bad_row = -1;
-#pragma omp parallel for num_threads(pa_host_threads()) schedule(static)
-    for (int i = 0; i < N; ++i) {
-      int seen = 0;
-      for (int k = rowPtr[i]; k < rowPtr[i + 1] && !seen; ++k) seen = colInd[k] == i;
-      if (!seen) {
-#pragma omp critical
-        { if (bad_row < 0 || i < bad_row) bad_row = i; }
-      }
+/* The one place where a shard becomes the operator: whatever can fail comes first (the scratch of the
+ * exchange, the send list on the device), then the pointers move and *sh is left empty.  A failure leaves
+ * g_op as preAlps_OperatorFree leaves it and *sh to the caller.  src_rowptr (taken over on success): the
+ * caller's rowPtr when the values keep the caller's order, else NULL. */
+static int adopt_shard(pa_operator_t* o, pa_op_shard_t* sh, int size, long long nnz_global, int* src_rowptr, int scaled,
+                       double t_build0) {
+  const size_t room = (size_t)(size > 0 ? size : 1);
+  int* send_cnt = (int*)calloc(room, sizeof(int));
+  int* recv_cnt = (int*)calloc(room, sizeof(int));
+  int* d_send_idx = NULL;
+  if (!send_cnt || !recv_cnt) { free(send_cnt); free(recv_cnt); return PA_FAIL("out of host memory"); }
+  if (!g_plan_only && sh->nsend > 0) {
+    d_send_idx = (int*)pa_rt_malloc((size_t)sh->nsend * sizeof(int));
+    if (!d_send_idx || pa_rt_h2d(d_send_idx, sh->send_idx, (size_t)sh->nsend * sizeof(int))) {
+      pa_rt_free(d_send_idx); free(send_cnt); free(recv_cnt);
+      return PA_FAIL("uploading the operator failed: %s", pa_rt_error());
     }
-    if (bad_row >= 0) return PA_FAIL("Diagonal is not set correctly (row %d)", bad_row);
   }
-  TRACE("diagonal check");
-  /* SymRACScaling: d_i = 1/sqrt(max_j |a_ij|) */
-  double* d = NULL;
-  if (scale) {
-    d = (double*)malloc((size_t)N * sizeof(double));
-    if (!d) return PA_FAIL("out of host memory");
-    int zero_row = 0;
-#pragma omp parallel for num_threads(pa_host_threads()) schedule(static) reduction(|| : zero_row)
-    for (int i = 0; i < N; ++i) {
-      double mx = 0.0;
-      for (int k = rowPtr[i]; k < rowPtr[i + 1]; ++k) { double a = fabs(val[k]); if (a > mx) mx = a; }
-      if (mx == 0.0) zero_row = 1;
-      d[i] = mx > 0.0 ? sqrt(1.0 / mx) : 0.0;
-    }
-    if (zero_row) { free(d); return PA_FAIL("Impossible to scale the matrix, rcmin=0"); }
-  }
-  TRACE("scaling");
-  /* ordering: rows grouped part by part, original order inside a part */
-  in->N = N; in->nparts = nparts;
-  in->rowPos = (int*)calloc((size_t)nparts + 1, sizeof(int));
-  in->perm = (int*)malloc((size_t)N * sizeof(int));
-  int* iperm = (int*)malloc((size_t)N * sizeof(int));
-  if (!in->rowPos || !in->perm || !iperm) { free(d); free(iperm); return PA_FAIL("out of host memory"); }
-  for (int i = 0; i < N; ++i) {
-    int p = part ? part[i] : (int)(((long long)i * nparts) / N);
-    if (p < 0 || p >= nparts) { free(d); free(iperm); return PA_FAIL("partition entry %d of row %d out of range", p, i); }
-    in->rowPos[p + 1]++;
-  }
-  for (int p = 0; p < nparts; ++p) {
-    if (in->rowPos[p + 1] == 0) { free(d); free(iperm); return PA_FAIL("part %d is empty", p); }
-    in->rowPos[p + 1] += in->rowPos[p];
-  }
-  {
-    int* fill = (int*)malloc((size_t)nparts * sizeof(int));
-    memcpy(fill, in->rowPos, (size_t)nparts * sizeof(int));
-    for (int i = 0; i < N; ++i) {
-      int p = part ? part[i] : (int)(((long long)i * nparts) / N);
-      in->perm[fill[p]] = i;
-      iperm[i] = fill[p]++;
-    }
-    free(fill);
-  }
-  TRACE("ordering");
-  *d_out = d; *iperm_out = iperm;
-  return 0;
-}
-
-/* Rows [row_off, row_off + m) of the permuted, scaled matrix from their raw form: row i of the panel
- * is row (whole ? perm[row_off + i] : i) of (rp, ci, v), columns in the ORIGINAL numbering.  Leaves the
- * panel (global permuted column ids, sorted), the halo slots (halo_cols ascending, lcol) and the
- * receive counts per process in `o`; `mark_out` (N ints: halo slot + 1) is handed to the caller.
- * keep_src: also o->src, the index into v of every panel entry -- the sort makes it for nothing. */
-static int build_panel(pa_operator_t* o, const int* rp, const int* ci, const double* v, int whole, int keep_src,
-                       const double* d, const int* iperm, long long nnz_global, int** recv_by_proc_out) {
   pa_operator_info_t* in = &o->info;
-  TRACE_DECL;
-  const int N = in->N, nparts = in->nparts, rank = pa_world_rank(), size = pa_world_size();
-  in->part0 = (int)((long long)rank * nparts / size);
-  in->part1 = (int)((long long)(rank + 1) * nparts / size);
-  in->rank = rank; in->world = size; in->loopback = pa_comm_is_loopback();
-  in->row_off = in->rowPos[in->part0];
-  int m = in->rowPos[in->part1] - in->row_off;
-  in->m = m;
-#define SRC(i) (whole ? in->perm[in->row_off + (i)] : (i))
-  size_t lnnz = 0;
-  for (int i = 0; i < m; ++i) { int r = SRC(i); lnnz += (size_t)(rp[r + 1] - rp[r]); }
-  if (lnnz > 2147483000u) return PA_FAIL("local panel has too many nonzeros for int32 indices");
+  in->N = sh->N; in->nparts = sh->nparts; in->part0 = sh->part0; in->part1 = sh->part1;
+  in->rank = pa_world_rank(); in->world = size; in->loopback = pa_comm_is_loopback();
+  in->row_off = sh->row_off; in->m = sh->m; in->halo = sh->halo;
+  in->rowPos = sh->rowPos; in->perm = sh->perm;
+  in->scaling = sh->d;     /* (kept: preAlps_OperatorGetScalingPtr, the row map of preAlps_ECGSolveSystem) */
   CPLM_Mat_CSR_t* A = &in->A;
-  A->rowPtr = (int*)malloc((size_t)(m + 1) * sizeof(int));
-  A->colInd = (int*)pa_big_alloc((lnnz ? lnnz : 1) * sizeof(int));
-  A->val = (double*)pa_big_alloc((lnnz ? lnnz : 1) * sizeof(double));
-  int* src = keep_src ? (o->src = (int*)pa_big_alloc((lnnz ? lnnz : 1) * sizeof(int))) : NULL;
-  if (!A->rowPtr || !A->colInd || !A->val || (keep_src && !src))
-    return PA_FAIL("out of host memory for the row panel (%zu entries)", lnnz);
-  A->rowPtr[0] = 0;
-  {
-    int maxlen = 0;
-    for (int i = 0; i < m; ++i) {
-      int r = SRC(i); int l = rp[r + 1] - rp[r];
-      if (l > maxlen) maxlen = l;
-      A->rowPtr[i + 1] = A->rowPtr[i] + l;
-    }
-    /* rows are independent: scale, renumber the columns and sort each one (threads as available) */
-    int dup_row = -1;   /* (benign race: any offending row will do for the message) */
-#pragma omp parallel num_threads(pa_host_threads())
-    {
-      cv_t* buf = (cv_t*)malloc((maxlen ? maxlen : 1) * sizeof(cv_t));
-#pragma omp for schedule(static)
-      for (int i = 0; i < m; ++i) {
-        int old = in->perm[in->row_off + i], r = whole ? old : i;
-        int l = 0, sorted = 1;
-        for (int k = rp[r]; k < rp[r + 1]; ++k, ++l) {
-          buf[l].c = iperm[ci[k]];
-          buf[l].k = k;
-          buf[l].v = d ? d[old] * v[k] * d[ci[k]] : v[k];
-          if (l > 0 && buf[l].c < buf[l - 1].c) sorted = 0;
-        }
-        if (!sorted) qsort(buf, l, sizeof(cv_t), cmp_cv);
-        for (int q = 1; q < l; ++q) if (buf[q].c == buf[q - 1].c) dup_row = old;
-        int base = A->rowPtr[i];
-        for (int q = 0; q < l; ++q) { A->colInd[base + q] = buf[q].c; A->val[base + q] = buf[q].v; }
-        if (src) for (int q = 0; q < l; ++q) src[base + q] = buf[q].k;
-      }
-      free(buf);
-    }
-    if (dup_row >= 0)
-      return PA_FAIL("row %d holds the same column twice: sum duplicate entries before building the operator", dup_row);
-  }
-#undef SRC
-  TRACE("permute + sort rows");
-  A->info.M = N; A->info.N = N; A->info.nnz = (int)(nnz_global > 2147483647LL ? 2147483647LL : nnz_global);
-  A->info.m = m; A->info.n = N;
-  A->info.lnnz = (int)lnnz; A->info.blockSize = 1; A->info.format = FORMAT_CSR;
+  A->rowPtr = sh->rowPtr; A->colInd = sh->colInd; A->val = sh->val;
+  A->info.M = sh->N; A->info.N = sh->N; A->info.nnz = (int)(nnz_global > 2147483647LL ? 2147483647LL : nnz_global);
+  A->info.m = sh->m; A->info.n = sh->N;
+  A->info.lnnz = sh->lnnz; A->info.blockSize = 1; A->info.format = FORMAT_CSR;
   A->info.structure = UNSYMMETRIC;
-  o->lnnz = (int)lnnz;
-  /* halo: off-process columns, grouped by owner (ascending global index) */
-  int lo = in->row_off, hi = in->row_off + m;
-  int* mark = (int*)calloc((size_t)N, sizeof(int)); /* halo slot + 1 */
-  if (!mark) return PA_FAIL("out of host memory");
-  int halo = 0;
-  for (size_t k = 0; k < lnnz; ++k) { int c = A->colInd[k]; if ((c < lo || c >= hi) && !mark[c]) { mark[c] = 1; ++halo; } }
-  int* halo_cols = (int*)malloc((halo ? halo : 1) * sizeof(int));
-  { int q = 0; for (int c = 0; c < N; ++c) if (mark[c]) { halo_cols[q] = c; mark[c] = ++q; } }
-  in->halo = halo;
-  TRACE("halo marks");
-  o->peers = (int*)malloc((size > 0 ? size : 1) * sizeof(int));
-  o->recv_rows = (int*)calloc(size, sizeof(int));
-  o->send_rows = (int*)calloc(size, sizeof(int));
-  o->send_cnt = (int*)calloc(size, sizeof(int));
-  o->recv_cnt = (int*)calloc(size, sizeof(int));
-  int* recv_by_proc = (int*)calloc(size, sizeof(int));
-  for (int q = 0; q < halo; ++q)
-    recv_by_proc[owner_of_part(part_of_row(in->rowPos, nparts, halo_cols[q]), nparts, size)]++;
-  /* device CSR with local column ids */
-  int* lcol = (int*)pa_big_alloc((lnnz + 8) * sizeof(int));
-  if (!lcol) { free(mark); free(recv_by_proc); return PA_FAIL("out of host memory"); }
-#pragma omp parallel for num_threads(pa_host_threads()) schedule(static)
-  for (long long k = 0; k < (long long)lnnz; ++k) { int c = A->colInd[k]; lcol[k] = (c >= lo && c < hi) ? c - lo : m + mark[c] - 1; }
-  for (size_t k = lnnz; k < lnnz + 8; ++k) lcol[k] = 0;
-  free(mark);
-  o->halo_cols = halo_cols;
-  o->lcol = lcol;
-  TRACE("local columns");
-  *recv_by_proc_out = recv_by_proc;
-  return 0;
-}
-
-/* peers / send_rows / recv_rows / send_idx from need-lists: asked[] = for every process g (in rank
- * order) the local rows of ours it reads, asked_cnt[g] of them, ascending. */
-static int finish_peers(pa_operator_t* o, const int* recv_by_proc, int* asked_local, const int* asked_cnt) {
-  int size = pa_world_size();
-  o->nsend = 0; o->npeers = 0;
-  for (int g = 0; g < size; ++g) {
-    if (asked_cnt[g] || recv_by_proc[g]) {
-      o->peers[o->npeers] = g; o->recv_rows[o->npeers] = recv_by_proc[g]; o->send_rows[o->npeers] = asked_cnt[g];
-      o->npeers++;
-    }
-    o->nsend += asked_cnt[g];
-  }
-  o->send_idx = asked_local;
-  return 0;
-}
-
-static int upload_operator(pa_operator_t* o, double t_build0) {
-  pa_operator_info_t* in = &o->info;
+  o->lnnz = sh->lnnz; o->lcol = sh->lcol; o->src = sh->src; o->halo_cols = sh->halo_cols;
+  o->npeers = sh->npeers; o->nsend = sh->nsend;
+  o->peers = sh->peers; o->send_rows = sh->send_rows; o->recv_rows = sh->recv_rows; o->send_idx = sh->send_idx;
+  o->send_cnt = send_cnt; o->recv_cnt = recv_cnt; o->d_send_idx = d_send_idx;
+  if (src_rowptr) { o->src_rowptr = src_rowptr; o->from_csr = 1; o->scaled = scaled; }
+  free(sh->iperm); free(sh->recv_by_proc);
+  memset(sh, 0, sizeof(*sh));
   ++g_op_builds;
-  if (g_plan_only) { in->built = 1; return 0; }
-  int rc = 0;
-  if (o->nsend > 0) {
-    o->d_send_idx = (int*)pa_rt_malloc((size_t)o->nsend * sizeof(int));
-    rc = !o->d_send_idx || pa_rt_h2d(o->d_send_idx, o->send_idx, (size_t)o->nsend * sizeof(int));
-  }
-  if (rc) return PA_FAIL("uploading the operator failed: %s", pa_rt_error());
   in->built = 1;
-  g_setup_build_s = pa_wtime() - t_build0;
+  if (!g_plan_only) g_setup_build_s = pa_wtime() - t_build0;
   return 0;
 }
 
-static int g_keep_value_order = 1;   /* 0 while preAlps_OperatorBuild builds from a file: that value order is not the caller's */
-
-int preAlps_OperatorBuildFromCSR(int N, const int* rowPtr, const int* colInd, const double* val,
-                                 int nparts, const int* part, int scale) {
+/* keep_src: the values keep the caller's order (preAlps_OperatorUpdateValues may follow); 0 when the matrix came
+ * from a file, whose value order is not the caller's. */
+static int build_from_csr(int N, const int* rowPtr, const int* colInd, const double* val, int nparts, const int* part,
+                          int scale, int keep_src) {
   if (!g_plan_only) PA_REQUIRE_GPU();
   if (g_op.info.built) preAlps_OperatorFree();
   double t_build0 = pa_wtime();
-  pa_operator_t* o = &g_op;
-  pa_operator_info_t* in = &o->info;
-  int rank = pa_world_rank(), size = pa_world_size();
+  const int size = pa_world_size();
   if (N < 1 || nparts < 1 || nparts > N) return PA_FAIL("invalid sizes N=%d nparts=%d", N, nparts);
   if (nparts < size)
     return PA_FAIL("Each process needs at least one block (nparts = %d < %d = processes)", nparts, size);
-  double* d = NULL; int* iperm = NULL; int* recv_by_proc = NULL;
-  if (order_and_scale(N, rowPtr, colInd, val, nparts, part, scale, in, &d, &iperm)) return 1;
-  if (build_panel(o, rowPtr, colInd, val, 1, g_keep_value_order, d, iperm, (long long)rowPtr[N], &recv_by_proc)) { free(d); free(iperm); return 1; }
-  in->scaling = d;     /* (kept: preAlps_OperatorGetScalingPtr, the row map of preAlps_ECGSolveSystem) */
-  TRACE_DECL;
-  int m = in->m, lo = in->row_off, hi = in->row_off + m;
-  /* Send lists, exactly: process g receives from us the rows of ours that occur as columns in
-   * ITS rows (ascending) -- which is how g numbers its halo slots.  Every process holds the
-   * whole matrix here, so this needs no communication and, unlike taking "our rows that touch a
-   * column of g", it stays right for a pattern that is not structurally symmetric (a `general`
-   * .mtx with explicit zeros dropped on one side). */
-  unsigned char* need = NULL;   /* need[g * m + i]: process g reads our local row i */
-  if (size > 1) {
-    need = (unsigned char*)calloc((size_t)size * (m ? m : 1), 1);
-    if (!need) { free(iperm); free(recv_by_proc); return PA_FAIL("out of host memory for the halo plan"); }
-#pragma omp parallel for num_threads(pa_host_threads()) schedule(dynamic, 4096)
-    for (int i = 0; i < N; ++i) {
-      int r = iperm[i];
-      if (r >= lo && r < hi) continue;
-      unsigned char* ng = need + (size_t)owner_of_part(part_of_row(in->rowPos, nparts, r), nparts, size) * m;
-      for (int k = rowPtr[i]; k < rowPtr[i + 1]; ++k) {
-        int c = iperm[colInd[k]];
-        if (c >= lo && c < hi) ng[c - lo] = 1;   /* (all writers store the same value) */
-      }
-    }
+  const pa_op_in_t bin = {.N = N, .rowPtr = rowPtr, .colInd = colInd, .val = val, .nparts = nparts, .part = part,
+                          .scale = scale, .rank = pa_world_rank(), .size = size, .threads = pa_host_threads(),
+                          .trace = setup_trace()};
+  pa_op_shard_t sh;
+  char err[256];
+  if (pa_op_order(&bin, &sh, err, sizeof(err)) || pa_op_panel(&bin, &sh, 1, keep_src, err, sizeof(err)) ||
+      pa_op_peers_whole(&bin, &sh, err, sizeof(err)))
+    return PA_FAIL("%s", err);
+  int* src_rowptr = NULL;
+  if (keep_src) {
+    src_rowptr = (int*)malloc(((size_t)N + 1) * sizeof(int));
+    if (!src_rowptr) { pa_op_shard_free(&sh); return PA_FAIL("out of host memory"); }
+    memcpy(src_rowptr, rowPtr, ((size_t)N + 1) * sizeof(int));
   }
-  free(iperm);
-  size_t send_cap = 1024, nsend = 0;
-  int* send_idx = (int*)malloc(send_cap * sizeof(int));
-  int* asked_cnt = (int*)calloc(size, sizeof(int));
-  for (int g = 0; g < size; ++g) {
-    if (!need || g == rank) continue;
-    for (int i = 0; i < m; ++i) if (need[(size_t)g * m + i]) {
-      if (nsend + 1 > send_cap) { send_cap *= 2; send_idx = (int*)realloc(send_idx, send_cap * sizeof(int)); }
-      send_idx[nsend++] = i; asked_cnt[g]++;
-    }
+  if (adopt_shard(&g_op, &sh, size, (long long)rowPtr[N], src_rowptr, scale != 0, t_build0)) {
+    pa_op_shard_free(&sh); free(src_rowptr);
+    return 1;
   }
-  free(need);
-  finish_peers(o, recv_by_proc, send_idx, asked_cnt);
-  free(recv_by_proc); free(asked_cnt);
-  TRACE("peer lists");
-  if (g_keep_value_order) {
-    o->src_rowptr = (int*)malloc(((size_t)N + 1) * sizeof(int));
-    if (!o->src_rowptr) return PA_FAIL("out of host memory");
-    memcpy(o->src_rowptr, rowPtr, ((size_t)N + 1) * sizeof(int));
-    o->from_csr = 1; o->scaled = scale != 0;
-  }
-  return upload_operator(o, t_build0);
+  return 0;
 }
 
-/* ---- MatrixMarket reader (utils/cplm_light/cplm_matcsr.c:96-243) ----------------------------------
- * coordinate real general|symmetric; 0-based files are detected from the first entry like the reference
- * does; symmetric files are expanded; repeated (i, j) entries are summed (in file order).  The file is
- * mapped and the host threads parse it in line-aligned pieces (an 81 M-nonzero matrix is 1.3 GB of text:
- * minutes through fscanf, seconds this way); values go through strtod, so they are the doubles
- * fscanf("%lf") would have produced. */
-typedef struct { int c; double v; } mm_ent_t;
-
-static void mm_sort_row(mm_ent_t* e, int n, mm_ent_t* tmp) {   /* stable, by column */
-  if (n <= 96) {
-    for (int a = 1; a < n; ++a) { mm_ent_t x = e[a]; int q = a; while (q > 0 && e[q - 1].c > x.c) { e[q] = e[q - 1]; --q; } e[q] = x; }
-    return;
-  }
-  int h = n / 2;
-  mm_sort_row(e, h, tmp); mm_sort_row(e + h, n - h, tmp);
-  memcpy(tmp, e, (size_t)h * sizeof(mm_ent_t));
-  int i = 0, j = h, k = 0;
-  while (i < h && j < n) e[k++] = (e[j].c < tmp[i].c) ? e[j++] : tmp[i++];
-  while (i < h) e[k++] = tmp[i++];
+int preAlps_OperatorBuildFromCSR(int N, const int* rowPtr, const int* colInd, const double* val,
+                                 int nparts, const int* part, int scale) {
+  return build_from_csr(N, rowPtr, colInd, val, nparts, part, scale, 1);
 }
 
-/* one "i j v" line starting at p (p < end); returns the position behind the line, NULL on a bad line */
-static const char* mm_parse_line(const char* p, const char* end, int* I, int* J, double* V) {
-  long val[2];
-  for (int f = 0; f < 2; ++f) {
-    while (p < end && (*p == ' ' || *p == '\t')) ++p;
-    int neg = 0;
-    if (p < end && (*p == '-' || *p == '+')) { neg = *p == '-'; ++p; }
-    if (p >= end || *p < '0' || *p > '9') return NULL;
-    long x = 0;
-    while (p < end && *p >= '0' && *p <= '9') { x = 10 * x + (*p - '0'); ++p; }
-    val[f] = neg ? -x : x;
-  }
-  while (p < end && (*p == ' ' || *p == '\t')) ++p;
-  /* the number's characters, NUL terminated for strtod (never reads past the mapping) */
-  char buf[64];
-  int l = 0;
-  while (p + l < end && l < 63 && p[l] != '\n' && p[l] != '\r' && p[l] != ' ' && p[l] != '\t') { buf[l] = p[l]; ++l; }
-  buf[l] = 0;
-  if (l == 0) return NULL;
-  char* stop = NULL;
-  *V = strtod(buf, &stop);
-  if (stop == buf) return NULL;
-  p += l;
-  while (p < end && *p != '\n') ++p;
-  *I = (int)val[0]; *J = (int)val[1];
-  return p < end ? p + 1 : end;
-}
-
-static int load_mtx(const char* file, int* N_out, int** rp_out, int** ci_out, double** v_out) {
-  FILE* fd = fopen(file, "r");
-  if (!fd) return PA_FAIL("Impossible to open the file %s", file);
-  char line[1025], banner[64], mtx[64], crd[64], dt[64], sym[64];
-  if (!fgets(line, sizeof(line), fd) ||
-      sscanf(line, "%63s %63s %63s %63s %63s", banner, mtx, crd, dt, sym) != 5 ||
-      strcasecmp(banner, "%%MatrixMarket") || strcasecmp(mtx, "matrix") ||
-      strcasecmp(crd, "coordinate") || strcasecmp(dt, "real") ||
-      (strcasecmp(sym, "general") && strcasecmp(sym, "symmetric"))) {
-    fclose(fd);
-    return PA_FAIL("Only sparse real < symmetric | general > matrix are currently supported (%s)", file);
-  }
-  int is_sym = !strcasecmp(sym, "symmetric");
-  do { if (!fgets(line, sizeof(line), fd)) { fclose(fd); return PA_FAIL("truncated file %s", file); } } while (line[0] == '%');
-  int M = 0, Nc = 0; long long nz = 0;
-  if (sscanf(line, "%d %d %lld", &M, &Nc, &nz) != 3 || M < 1 || Nc != M || nz < 1) {
-    fclose(fd);
-    return PA_FAIL("[LoadMatrixMarket] Error: Invalid matrix dimensions in %s", file);
-  }
-  long body = ftell(fd);
-  fseek(fd, 0, SEEK_END);
-  long fsize = ftell(fd);
-  if (body < 0 || fsize <= body) { fclose(fd); return PA_FAIL("truncated file %s", file); }
-  const char* map = (const char*)mmap(NULL, (size_t)fsize, PROT_READ, MAP_PRIVATE, fileno(fd), 0);
-  fclose(fd);
-  if (map == MAP_FAILED) return PA_FAIL("cannot map %s", file);
-  (void)madvise((void*)map, (size_t)fsize, MADV_SEQUENTIAL);
-  const char* beg = map + body;
-  const char* end = map + fsize;
-  TRACE_DECL;
-  int T = pa_host_threads();
-  if ((long long)T > nz / 4096 + 1) T = (int)(nz / 4096 + 1);
-  if (T < 1) T = 1;
-  /* pieces that start behind a newline */
-  const char** cut = (const char**)malloc(((size_t)T + 1) * sizeof(char*));
-  long long* first = (long long*)calloc((size_t)T + 1, sizeof(long long));
-  int* I = (int*)malloc((size_t)nz * sizeof(int));
-  int* J = (int*)malloc((size_t)nz * sizeof(int));
-  double* V = (double*)malloc((size_t)nz * sizeof(double));
-  if (!cut || !first || !I || !J || !V) { free(cut); free(first); free(I); free(J); free(V); munmap((void*)map, (size_t)fsize); return PA_FAIL("out of host memory for %lld entries", nz); }
-  cut[0] = beg; cut[T] = end;
-  for (int t = 1; t < T; ++t) {
-    const char* p = beg + (size_t)((double)(end - beg) * t / T);
-    if (p < cut[t - 1]) p = cut[t - 1];
-    const char* nl = (const char*)memchr(p, '\n', (size_t)(end - p));
-    cut[t] = nl ? nl + 1 : end;
-  }
-  /* lines per piece (blank lines do not count) */
-#pragma omp parallel for num_threads(T) schedule(static, 1)
-  for (int t = 0; t < T; ++t) {
-    long long n = 0;
-    const char* p = cut[t];
-    while (p < cut[t + 1]) {
-      const char* nl = (const char*)memchr(p, '\n', (size_t)(cut[t + 1] - p));
-      const char* le = nl ? nl : cut[t + 1];
-      const char* q = p;
-      while (q < le && (*q == ' ' || *q == '\t' || *q == '\r')) ++q;
-      if (q < le && *q != '%') ++n;           /* (blank lines and comment lines inside the body do not count) */
-      p = nl ? nl + 1 : cut[t + 1];
-    }
-    first[t + 1] = n;
-  }
-  for (int t = 0; t < T; ++t) first[t + 1] += first[t];
-  TRACE("  mtx: count lines");
-  int bad = first[T] < nz;     /* (extra lines behind the nz announced are ignored, like fscanf would) */
-  long long bad_line = -1;
-  if (!bad) {
-#pragma omp parallel for num_threads(T) schedule(static, 1)
-    for (int t = 0; t < T; ++t) {
-      long long k = first[t];
-      const char* p = cut[t];
-      while (p && p < cut[t + 1] && k < nz) {
-        const char* q = p;
-        while (q < cut[t + 1] && (*q == ' ' || *q == '\t' || *q == '\r')) ++q;
-        if (q < cut[t + 1] && *q == '\n') { p = q + 1; continue; }
-        if (q >= cut[t + 1]) break;
-        if (*q == '%') {                         /* a comment line in the body: skipped */
-          const char* nl = (const char*)memchr(q, '\n', (size_t)(cut[t + 1] - q));
-          p = nl ? nl + 1 : cut[t + 1];
-          continue;
-        }
-        p = mm_parse_line(q, cut[t + 1], &I[k], &J[k], &V[k]);
-        if (!p) {
-#pragma omp critical
-          { if (bad_line < 0 || k < bad_line) bad_line = k; }
-          break;
-        }
-        ++k;
-      }
-    }
-  }
-  munmap((void*)map, (size_t)fsize);
-  free(cut);
-  TRACE("  mtx: parse");
-  if (bad || bad_line >= 0) {
-    long long k = bad ? first[T] : bad_line;
-    free(first); free(I); free(J); free(V);
-    return PA_FAIL("bad entry %lld in %s", k, file);
-  }
-  free(first);
-  int base = (I[0] == 0 || J[0] == 0) ? 0 : 1;
-  /* row histograms per thread (thread t owns entries [t nz / T, (t+1) nz / T)): positions that keep
-   * the file order inside every row, without atomics */
-  int oob = 0;
-#pragma omp parallel for num_threads(pa_host_threads()) schedule(static) reduction(|| : oob)
-  for (long long k = 0; k < nz; ++k) {
-    I[k] -= base; J[k] -= base;
-    if (I[k] < 0 || I[k] >= M || J[k] < 0 || J[k] >= M) oob = 1;
-  }
-  if (oob) { free(I); free(J); free(V); return PA_FAIL("index out of range in %s", file); }
-  int TH = pa_host_threads();
-  while (TH > 1 && (size_t)TH * (size_t)M * sizeof(int) > ((size_t)1 << 30)) TH /= 2;
-  int* hist = (int*)calloc((size_t)TH * (size_t)M, sizeof(int));
-  int* rp = (int*)malloc(((size_t)M + 1) * sizeof(int));
-  if (!hist || !rp) { free(hist); free(rp); free(I); free(J); free(V); return PA_FAIL("out of host memory"); }
-#pragma omp parallel for num_threads(TH) schedule(static, 1)
-  for (int t = 0; t < TH; ++t) {
-    int* h = hist + (size_t)t * M;
-    long long k0 = nz * t / TH, k1 = nz * (t + 1) / TH;
-    for (long long k = k0; k < k1; ++k) { h[I[k]]++; if (is_sym && I[k] != J[k]) h[J[k]]++; }
-  }
-  long long tot = 0;
-  for (int i = 0; i < M; ++i) {
-    rp[i] = (int)tot;
-    for (int t = 0; t < TH; ++t) { int c = hist[(size_t)t * M + i]; hist[(size_t)t * M + i] = (int)tot; tot += c; }
-    if (tot > 2147483000LL) { free(hist); free(rp); free(I); free(J); free(V); return PA_FAIL("%s has too many nonzeros for int32 indices", file); }
-  }
-  rp[M] = (int)tot;
-  mm_ent_t* ent = (mm_ent_t*)pa_big_alloc((size_t)(tot ? tot : 1) * sizeof(mm_ent_t));
-  if (!ent) { free(hist); free(rp); free(I); free(J); free(V); return PA_FAIL("out of host memory for %lld entries", tot); }
-#pragma omp parallel for num_threads(TH) schedule(static, 1)
-  for (int t = 0; t < TH; ++t) {
-    int* h = hist + (size_t)t * M;
-    long long k0 = nz * t / TH, k1 = nz * (t + 1) / TH;
-    for (long long k = k0; k < k1; ++k) {
-      ent[h[I[k]]].c = J[k]; ent[h[I[k]]++].v = V[k];
-      if (is_sym && I[k] != J[k]) { ent[h[J[k]]].c = I[k]; ent[h[J[k]]++].v = V[k]; }
-    }
-  }
-  free(hist); free(I); free(J); free(V);
-  TRACE("  mtx: rows (histograms, scatter)");
-  /* sort every row by column (stable), sum repeated entries, compact */
-  int* len = (int*)malloc((size_t)M * sizeof(int));
-  if (!len) { free(ent); free(rp); return PA_FAIL("out of host memory"); }
-  int no_mem = 0;        /* a thread could not get its sort buffer: the rows it met stay unsorted, the build fails */
-#pragma omp parallel num_threads(pa_host_threads())
-  {
-    int cap = 256;
-    mm_ent_t* tmp = (mm_ent_t*)malloc((size_t)cap * sizeof(mm_ent_t));
-#pragma omp for schedule(dynamic, 1024)
-    for (int i = 0; i < M; ++i) {
-      int k0 = rp[i], n = rp[i + 1] - k0;
-      if (n / 2 + 1 > cap || !tmp) { cap = n > cap ? n : cap; free(tmp); tmp = (mm_ent_t*)malloc((size_t)cap * sizeof(mm_ent_t)); }
-      int sorted = 1;
-      for (int k = 1; k < n && sorted; ++k) sorted = ent[k0 + k - 1].c <= ent[k0 + k].c;
-      if (!sorted && !tmp) {
-#pragma omp atomic write
-        no_mem = 1;
-      }
-      if (!sorted && tmp) mm_sort_row(ent + k0, n, tmp);
-      int out = 0;
-      for (int k = 0; k < n; ++k) {
-        if (out > 0 && ent[k0 + k].c == ent[k0 + out - 1].c) ent[k0 + out - 1].v += ent[k0 + k].v;
-        else ent[k0 + out++] = ent[k0 + k];
-      }
-      len[i] = out;
-    }
-    free(tmp);
-  }
-  if (no_mem) { free(len); free(ent); free(rp); return PA_FAIL("out of host memory while sorting the rows of %s", file); }
-  int* rp2 = (int*)malloc(((size_t)M + 1) * sizeof(int));
-  long long out = 0;
-  for (int i = 0; rp2 && i < M; ++i) { rp2[i] = (int)out; out += len[i]; }
-  int* ci = (int*)pa_big_alloc((size_t)(out ? out : 1) * sizeof(int));
-  double* vv = (double*)pa_big_alloc((size_t)(out ? out : 1) * sizeof(double));
-  if (!rp2 || !ci || !vv) { free(rp2); free(ci); free(vv); free(len); free(ent); free(rp); return PA_FAIL("out of host memory"); }
-  rp2[M] = (int)out;
-#pragma omp parallel for num_threads(pa_host_threads()) schedule(static)
-  for (int i = 0; i < M; ++i)
-    for (int k = 0; k < len[i]; ++k) { ci[rp2[i] + k] = ent[rp[i] + k].c; vv[rp2[i] + k] = ent[rp[i] + k].v; }
-  free(len); free(ent); free(rp);
-  TRACE("  mtx: sort + compact");
-  *N_out = M; *rp_out = rp2; *ci_out = ci; *v_out = vv;
+/* The MatrixMarket reader (mtx_read.c) with the host threads of this process; its reason through PA_FAIL. */
+static int load_mtx(const char* file, pa_mtx_t* A) {
+  char err[600];
+  if (pa_mtx_read(file, pa_host_threads(), setup_trace(), A, err, sizeof(err))) return PA_FAIL("%s", err);
   return 0;
 }
 
@@ -736,153 +308,183 @@ static int choose_partition(int N, const int* rp, const int* ci, int nparts, int
   return 0;
 }
 
+/* rows [r0, r0 + mg) of the new order make up the panel of process g */
+static void panel_rows(const pa_op_shard_t* sh, int g, int size, int* r0, int* mg) {
+  const int p0 = (int)((long long)g * sh->nparts / size), p1 = (int)((long long)(g + 1) * sh->nparts / size);
+  *r0 = sh->rowPos[p0]; *mg = sh->rowPos[p1] - *r0;
+}
+
 /* One MPI rank per GPU (the reference's own mode: utils/operator.c:38-134).  Rank 0 reads, scales
  * and partitions the matrix -- with the whole CPU share of the node, the other ranks sleep --
  * broadcasts the ordering and the scaling vector (12 bytes per row) and sends every rank the raw
  * rows of its panel (CPLM_MatCSRGetRowPanel + CPLM_MatCSRSend, utils/operator.c:99-108;
  * utils/cplm_light/cplm_matcsr.c:382-497); each rank then scales, renumbers and sorts its own rows,
  * finds its halo and asks the owners for exactly those rows.  No rank but 0 ever holds more than
- * its panel. */
+ * its panel.
+ *
+ * Six stages -- header, vectors, row panels, panel build, send lists, upload -- under one rule: a rank that
+ * fails records it in `rc`, skips the rest of that stage's own work and still enters every collective and
+ * message of the stage, in the order of the success path; the pa_mpi_agree that closes the stage makes the
+ * verdict common and every rank leaves through `done`, which releases whatever is set.  A failing pa_mpi_bcast
+ * or pa_mpi_swap_lists is itself a failed collective: what the other ranks then do is beyond this rule; this
+ * rank still leaves through `done`. */
 static int build_distributed(const char* file, int rank, int size) {
   double t_build0 = pa_wtime();
-  pa_operator_t* o = &g_op;
-  pa_operator_info_t* in = &o->info;
   TRACE_DECL;
-  int N = 0; int* rp = NULL; int* ci = NULL; double* v = NULL;
-  double* d = NULL; int* iperm = NULL;
+  int rc = 0, adopted = 0;
+  pa_mtx_t A = {0};                         /* rank 0: the whole matrix */
+  pa_op_shard_t sh = {0};
+  char err[256];
   long long hdr[4] = {0, 0, 0, 0};          /* rc, N, nparts, nnz */
-  const int abort_mode_rc = 1;
+  long long* nzs = NULL;                    /* entries of every rank's panel */
+  int* bl = NULL; int* bc = NULL; double* bv = NULL;   /* the raw rows of one panel: sent by rank 0, received by the others */
+  int* asked = NULL; int* asked_cnt = NULL;
+  pa_op_in_t bin = {.scale = 1, .rank = rank, .size = size, .threads = pa_host_threads(), .trace = tr};
+
+  /* ---- header: rank 0 reads, partitions, scales and orders */
   if (rank == 0) {
     pa_host_solo(1);
-    int rc = load_mtx(file, &N, &rp, &ci, &v);
+    bin.threads = pa_host_threads();
+    rc = load_mtx(file, &A);
     TRACE("rank 0: read the matrix");
     int nparts = env_int("PREALPS_NPARTS", size);
     int* part = NULL;
-    if (!rc && (nparts < size || nparts > N))
-      rc = PA_FAIL("Each process needs at least one block (nparts = %d, %d processes, %d rows)", nparts, size, N);
-    rc = rc || choose_partition(N, rp, ci, nparts, &part);
+    if (!rc && (nparts < size || nparts > A.N))
+      rc = PA_FAIL("Each process needs at least one block (nparts = %d, %d processes, %d rows)", nparts, size, A.N);
+    rc = rc || choose_partition(A.N, A.rowPtr, A.colInd, nparts, &part);
     TRACE("rank 0: partition");
-    rc = rc || order_and_scale(N, rp, ci, v, nparts, part, 1, in, &d, &iperm);
+    bin.N = A.N; bin.rowPtr = A.rowPtr; bin.colInd = A.colInd; bin.val = A.val; bin.nparts = nparts; bin.part = part;
+    if (!rc && pa_op_order(&bin, &sh, err, sizeof(err))) rc = PA_FAIL("%s", err);
     free(part);
+    bin.part = NULL;
     pa_host_solo(0);
-    hdr[0] = rc ? abort_mode_rc : 0; hdr[1] = N; hdr[2] = nparts; hdr[3] = rc ? 0 : rp[N];
+    bin.threads = pa_host_threads();
+    hdr[0] = rc ? 1 : 0; hdr[1] = A.N; hdr[2] = nparts; hdr[3] = rc ? 0 : A.rowPtr[A.N];
   }
-  if (pa_mpi_bcast(hdr, sizeof(hdr), 0)) return 1;
+  if (pa_mpi_bcast(hdr, sizeof(hdr), 0)) { rc = 1; goto done; }
   if (hdr[0]) {
-    free(rp); free(ci); free(v); free(d); free(iperm);
-    return rank == 0 ? 1 : PA_FAIL("rank 0 could not read or partition %s", file);
+    if (rank != 0) rc = PA_FAIL("rank 0 could not read or partition %s", file);
+    goto done;
   }
-  N = (int)hdr[1];
-  int nparts = (int)hdr[2];
+  const int N = (int)hdr[1], nparts = (int)hdr[2];
+
+  /* ---- vectors: the ordering and the scaling vector to every rank */
   if (rank != 0) {
-    in->N = N; in->nparts = nparts;
-    in->rowPos = (int*)malloc(((size_t)nparts + 1) * sizeof(int));
-    in->perm = (int*)malloc((size_t)N * sizeof(int));
-    iperm = (int*)malloc((size_t)N * sizeof(int));
-    d = (double*)malloc((size_t)N * sizeof(double));
+    bin.N = N; bin.nparts = nparts;
+    sh.N = N; sh.nparts = nparts;
+    sh.rowPos = (int*)malloc(((size_t)nparts + 1) * sizeof(int));
+    sh.perm = (int*)malloc((size_t)N * sizeof(int));
+    sh.iperm = (int*)malloc((size_t)N * sizeof(int));
+    sh.d = (double*)malloc((size_t)N * sizeof(double));
+    rc = !sh.rowPos || !sh.perm || !sh.iperm || !sh.d;
   }
-  {
-    /* (a rank that cannot hold the vectors must not leave the others inside the broadcasts) */
-    const int mine = rank != 0 && (!in->rowPos || !in->perm || !iperm || !d);
-    if (pa_mpi_agree(mine)) return mine ? PA_FAIL("out of host memory") : PA_FAIL("another rank ran out of host memory");
-  }
-  if (pa_mpi_bcast(in->rowPos, ((size_t)nparts + 1) * sizeof(int), 0) || pa_mpi_bcast(in->perm, (size_t)N * sizeof(int), 0) ||
-      pa_mpi_bcast(d, (size_t)N * sizeof(double), 0))
-    return 1;
+  /* (a rank that cannot hold the vectors must not leave the others inside the broadcasts) */
+  if (pa_mpi_agree(rc)) { rc = rc ? PA_FAIL("out of host memory") : PA_FAIL("another rank ran out of host memory"); goto done; }
+  if (pa_mpi_bcast(sh.rowPos, ((size_t)nparts + 1) * sizeof(int), 0) || pa_mpi_bcast(sh.perm, (size_t)N * sizeof(int), 0) ||
+      pa_mpi_bcast(sh.d, (size_t)N * sizeof(double), 0)) { rc = 1; goto done; }
   if (rank != 0)
-    for (int k = 0; k < N; ++k) iperm[in->perm[k]] = k;
+    for (int k = 0; k < N; ++k) sh.iperm[sh.perm[k]] = k;
   TRACE("ordering + scaling vector (broadcast)");
-  int* recv_by_proc = NULL;
-  int prc = 0;
-  /* entries of every rank's panel, announced before the rows travel: every buffer of the exchange exists (and
-   * the ranks have agreed that it does) before the first message */
-  long long* nzs = (long long*)calloc((size_t)size, sizeof(long long));
-  if (pa_mpi_agree(nzs == NULL)) { free(nzs); return PA_FAIL("out of host memory"); }
+
+  /* ---- row panels: the raw rows of every other panel travel from rank 0 -- row lengths, column ids, values,
+   * three messages per rank.  The entries of every panel are announced first: every buffer of the exchange
+   * exists (and the ranks have agreed that it does) before the first message, so the ranks that wait for their
+   * rows hear about a failure instead of waiting for ever */
+  int r0 = 0, mg = 0;                       /* this rank's rows (rank 0: the rank it is sending to) */
+  panel_rows(&sh, rank, size, &r0, &mg);
+  nzs = (long long*)calloc((size_t)size, sizeof(long long));
+  if (pa_mpi_agree(nzs == NULL)) { rc = PA_FAIL("out of host memory"); goto done; }
+  size_t cap = 0, capm = 0;                 /* rank 0: the largest panel; else: this rank's */
   if (rank == 0) {
-    /* raw rows of every other panel: row lengths, column ids, values -- three messages per rank */
-    /* buffers for the largest panel, made before the first message: the ranks that wait for their rows
-     * hear about a failure here (pa_mpi_agree below) instead of waiting for ever */
-    size_t cap = 0, capm = 0;
     for (int g = 1; g < size; ++g) {
-      int p0 = (int)((long long)g * nparts / size), p1 = (int)((long long)(g + 1) * nparts / size);
-      int r0 = in->rowPos[p0], mg = in->rowPos[p1] - r0;
+      panel_rows(&sh, g, size, &r0, &mg);
       size_t nz = 0;
-      for (int i = 0; i < mg; ++i) { int old = in->perm[r0 + i]; nz += (size_t)(rp[old + 1] - rp[old]); }
+      for (int i = 0; i < mg; ++i) { int old = sh.perm[r0 + i]; nz += (size_t)(A.rowPtr[old + 1] - A.rowPtr[old]); }
       if (nz > cap) cap = nz;
       if ((size_t)mg > capm) capm = (size_t)mg;
       nzs[g] = (long long)nz;
     }
-    if (pa_mpi_bcast(nzs, (size_t)size * sizeof(long long), 0)) { free(nzs); return 1; }
-    int* bl = (int*)malloc((capm + 1) * sizeof(int));
-    int* bc = (int*)pa_big_alloc((cap + 16) * sizeof(int));
-    double* bv = (double*)pa_big_alloc((cap + 16) * sizeof(double));
-    if (pa_mpi_agree(!bl || !bc || !bv)) { free(bl); free(bc); free(bv); free(nzs); return PA_FAIL("out of host memory for the row panels"); }
+    cap += 16;
+  }
+  if (pa_mpi_bcast(nzs, (size_t)size * sizeof(long long), 0)) { rc = rank == 0 ? 1 : PA_FAIL("receiving the panel sizes failed"); goto done; }
+  if (rank != 0) { cap = (size_t)nzs[rank] ? (size_t)nzs[rank] : 1; capm = (size_t)mg; }
+  bl = (int*)malloc((capm + 1) * sizeof(int));
+  bc = (int*)pa_big_alloc(cap * sizeof(int));
+  bv = (double*)pa_big_alloc(cap * sizeof(double));
+  if (pa_mpi_agree(!bl || !bc || !bv)) {
+    rc = rank == 0 ? PA_FAIL("out of host memory for the row panels")
+                   : PA_FAIL("out of host memory for the row panels (%zu entries here)", (size_t)nzs[rank]);
+    goto done;
+  }
+  if (rank == 0) {
+    const int* rp = A.rowPtr;
     for (int g = 1; g < size; ++g) {
-      int p0 = (int)((long long)g * nparts / size), p1 = (int)((long long)(g + 1) * nparts / size);
-      int r0 = in->rowPos[p0], mg = in->rowPos[p1] - r0;
-      size_t nz = 0;
-      for (int i = 0; i < mg; ++i) { int old = in->perm[r0 + i]; nz += (size_t)(rp[old + 1] - rp[old]); }
+      panel_rows(&sh, g, size, &r0, &mg);
+      const size_t nz = (size_t)nzs[g];
       bl[0] = 0;
-      for (int i = 0; i < mg; ++i) { int old = in->perm[r0 + i]; bl[i + 1] = bl[i] + (rp[old + 1] - rp[old]); }
+      for (int i = 0; i < mg; ++i) { int old = sh.perm[r0 + i]; bl[i + 1] = bl[i] + (rp[old + 1] - rp[old]); }
 #pragma omp parallel for num_threads(pa_host_threads()) schedule(static)
       for (int i = 0; i < mg; ++i) {
-        int old = in->perm[r0 + i];
-        memcpy(bc + bl[i], ci + rp[old], (size_t)(rp[old + 1] - rp[old]) * sizeof(int));
-        memcpy(bv + bl[i], v + rp[old], (size_t)(rp[old + 1] - rp[old]) * sizeof(double));
+        int old = sh.perm[r0 + i];
+        memcpy(bc + bl[i], A.colInd + rp[old], (size_t)(rp[old + 1] - rp[old]) * sizeof(int));
+        memcpy(bv + bl[i], A.val + rp[old], (size_t)(rp[old + 1] - rp[old]) * sizeof(double));
       }
+      /* (after a failed send the other ranks still get their rows: none of them waits in vain) */
       if (pa_mpi_send(bl, ((size_t)mg + 1) * sizeof(int), g, 41) || pa_mpi_send(bc, nz * sizeof(int), g, 42) ||
           pa_mpi_send(bv, nz * sizeof(double), g, 43))
-        return 1;
+        rc = 1;
     }
-    free(bl); free(bc); free(bv);
     TRACE("rank 0: panels sent");
-    prc = build_panel(o, rp, ci, v, 1, 0, d, iperm, hdr[3], &recv_by_proc);
-    free(rp); free(ci); free(v);
   } else {
-    int p0 = (int)((long long)rank * nparts / size), p1 = (int)((long long)(rank + 1) * nparts / size);
-    int mg = in->rowPos[p1] - in->rowPos[p0];
-    if (pa_mpi_bcast(nzs, (size_t)size * sizeof(long long), 0)) { free(nzs); return PA_FAIL("receiving the panel sizes failed"); }
-    size_t nz = (size_t)nzs[rank];
-    int* lrp = (int*)malloc(((size_t)mg + 1) * sizeof(int));
-    int* lci = (int*)pa_big_alloc((nz ? nz : 1) * sizeof(int));
-    double* lv = (double*)pa_big_alloc((nz ? nz : 1) * sizeof(double));
-    if (pa_mpi_agree(!lrp || !lci || !lv)) {      /* (pairs with rank 0's) */
-      free(lrp); free(lci); free(lv); free(nzs);
-      return PA_FAIL("out of host memory for the row panels (%zu entries here)", nz);
-    }
-    if (pa_mpi_recv(lrp, ((size_t)mg + 1) * sizeof(int), 0, 41) || (size_t)lrp[mg] != nz) return PA_FAIL("receiving the panel failed");
-    if (pa_mpi_recv(lci, nz * sizeof(int), 0, 42) || pa_mpi_recv(lv, nz * sizeof(double), 0, 43)) return 1;
+    const size_t nz = (size_t)nzs[rank];
+    if (pa_mpi_recv(bl, ((size_t)mg + 1) * sizeof(int), 0, 41) || (size_t)bl[mg] != nz) rc = PA_FAIL("receiving the panel failed");
+    if (pa_mpi_recv(bc, nz * sizeof(int), 0, 42)) rc = 1;
+    if (pa_mpi_recv(bv, nz * sizeof(double), 0, 43)) rc = 1;
     TRACE("panel received");
-    int rc = build_panel(o, lrp, lci, lv, 0, 0, d, iperm, hdr[3], &recv_by_proc);
-    free(lrp); free(lci); free(lv);
-    prc = rc;
   }
-  free(nzs);
-  if (pa_mpi_agree(prc)) return prc ? 1 : PA_FAIL("another rank could not build its row panel");
-  in->scaling = d;     /* (every rank holds the whole vector) */
-  /* send lists: every rank asks the owners for the rows behind its halo slots (halo_cols is
+
+  /* ---- panel build: every rank scales, renumbers and sorts its own rows */
+  if (!rc) {
+    if (rank == 0) { free(bl); free(bc); free(bv); bl = NULL; bc = NULL; bv = NULL; }
+    else { bin.rowPtr = bl; bin.colInd = bc; bin.val = bv; }
+    if (pa_op_panel(&bin, &sh, rank == 0, 0, err, sizeof(err))) rc = PA_FAIL("%s", err);
+    pa_mtx_free(&A);
+    free(bl); free(bc); free(bv); bl = NULL; bc = NULL; bv = NULL;
+  }
+  if (pa_mpi_agree(rc)) { if (!rc) rc = PA_FAIL("another rank could not build its row panel"); goto done; }
+
+  /* ---- send lists: every rank asks the owners for the rows behind its halo slots (halo_cols is
    * ascending, hence grouped by owner); what a rank is asked for, in that order, is what it packs */
-  int* asked = NULL;
-  int* asked_cnt = (int*)calloc((size_t)size, sizeof(int));
-  if (pa_mpi_agree(asked_cnt == NULL)) { free(asked_cnt); return PA_FAIL("out of host memory"); }
-  if (pa_mpi_swap_lists(o->halo_cols, recv_by_proc, &asked, asked_cnt)) return 1;
+  asked_cnt = (int*)calloc((size_t)size, sizeof(int));
+  if (pa_mpi_agree(asked_cnt == NULL)) { rc = PA_FAIL("out of host memory"); goto done; }
+  if (pa_mpi_swap_lists(sh.halo_cols, sh.recv_by_proc, &asked, asked_cnt)) { rc = 1; goto done; }
   {
     long long tot = 0;
     for (int g = 0; g < size; ++g) tot += asked_cnt[g];
     for (long long k = 0; k < tot; ++k) {
-      int r = asked[k] - in->row_off;
-      if (r < 0 || r >= in->m) { prc = PA_FAIL("a neighbour asked for row %d, which this rank does not own", asked[k]); break; }
+      int r = asked[k] - sh.row_off;
+      if (r < 0 || r >= sh.m) { rc = PA_FAIL("a neighbour asked for row %d, which this rank does not own", asked[k]); break; }
       asked[k] = r;
     }
   }
-  free(iperm);
-  if (!prc) finish_peers(o, recv_by_proc, asked, asked_cnt);
-  free(recv_by_proc); free(asked_cnt);
+  if (!rc) {
+    if (pa_op_finish_peers(&sh, size, asked, asked_cnt, err, sizeof(err))) rc = PA_FAIL("%s", err);
+    asked = NULL;   /* (taken over) */
+  }
   TRACE("peer lists (exchanged)");
-  if (!prc) prc = upload_operator(o, t_build0);
+
+  /* ---- upload, and the shard becomes the operator (every rank holds the whole scaling vector) */
+  if (!rc) { rc = adopt_shard(&g_op, &sh, size, hdr[3], NULL, 0, t_build0); adopted = !rc; }
   /* every rank leaves with the same answer: the solver's collectives come next */
-  if (pa_mpi_agree(prc)) return prc ? 1 : PA_FAIL("another rank could not finish its part of the operator");
-  return 0;
+  if (pa_mpi_agree(rc)) {
+    if (!rc) rc = PA_FAIL("another rank could not finish its part of the operator");
+    if (adopted) preAlps_OperatorFree();
+  }
+done:
+  pa_mtx_free(&A);
+  pa_op_shard_free(&sh);
+  free(nzs); free(bl); free(bc); free(bv); free(asked); free(asked_cnt);
+  return rc ? 1 : 0;
 }
 
 /* The number of subdomains is PREALPS_NPARTS (default: the process count, as in the
@@ -905,18 +507,15 @@ int preAlps_OperatorBuild(const char* matrixFilename, MPI_Comm comm) {
     if (!g_plan_only && pa_mpi_bind()) return 1;
     return build_distributed(matrixFilename, mrank, msize);
   }
-  int N = 0; int* rp = NULL; int* ci = NULL; double* v = NULL;
+  pa_mtx_t A;
   TRACE_DECL;
-  int rc = load_mtx(matrixFilename, &N, &rp, &ci, &v);
-  if (rc) return rc;
+  if (load_mtx(matrixFilename, &A)) return 1;
   TRACE("read the matrix");
   int nparts = env_int("PREALPS_NPARTS", pa_world_size());
   int* part = NULL;
-  if (choose_partition(N, rp, ci, nparts, &part)) { free(rp); free(ci); free(v); return 1; }
-  g_keep_value_order = 0;
-  rc = preAlps_OperatorBuildFromCSR(N, rp, ci, v, nparts, part, 1);
-  g_keep_value_order = 1;
-  free(part); free(rp); free(ci); free(v);
+  int rc = choose_partition(A.N, A.rowPtr, A.colInd, nparts, &part);
+  rc = rc || build_from_csr(A.N, A.rowPtr, A.colInd, A.val, nparts, part, 1, 0);
+  free(part); pa_mtx_free(&A);
   return rc;
 }
 
@@ -1028,13 +627,7 @@ static int ensure_halo_buffers(pa_operator_t* o, int ts) {
  * Returns 1 and the inverse send list (row -> slots of the send buffer, rows of `ts` doubles) when this process has
  * neighbours; the operator then skips its own pack for exactly that panel pointer, once.  The caller promises that
  * nothing else writes X in between (the library's own loops, PREALPS_RCI_FUSE=1). */
-/* off (m + 2 ints, zero on entry; m + 1 used on return), slot (nsend ints): row r is packed into the send-buffer
- * slots slot[off[r] .. off[r + 1]), ascending (a row goes to every neighbour that reads it) */
-static void inverse_send_list(int m, int nsend, const int* send_idx, int* off, int* slot) {
-  for (int i = 0; i < nsend; ++i) ++off[send_idx[i] + 2];
-  for (int r = 0; r < m; ++r) off[r + 2] += off[r + 1];       /* off[r + 1] = first slot entry of row r */
-  for (int i = 0; i < nsend; ++i) slot[off[send_idx[i] + 1]++] = i;   /* ... now off[r + 1] = end of row r */
-}
+/* (the inverse send list itself: pa_op_inverse_send_list, op_build.h) */
 /* The same list on the host, for tests without a GPU (plan-only mode): off_out[m + 1], slot_out[nsend]. */
 int preAlps_hip_pack_map(int* off_out, int* slot_out) {
   pa_operator_t* o = &g_op;
@@ -1042,7 +635,7 @@ int preAlps_hip_pack_map(int* off_out, int* slot_out) {
   int m = o->info.m;
   int* off = (int*)calloc((size_t)m + 2, sizeof(int));
   if (!off) return PA_FAIL("out of host memory");
-  inverse_send_list(m, o->nsend, o->send_idx, off, slot_out);
+  pa_op_inverse_send_list(m, o->nsend, o->send_idx, off, slot_out);
   memcpy(off_out, off, ((size_t)m + 1) * sizeof(int));
   free(off);
   return 0;
@@ -1061,7 +654,7 @@ int pa_operator_pack_hint(int ts, const double* X, const int** pk_off, const int
     int* slot = (int*)malloc((size_t)o->nsend * sizeof(int));
     int ok = off && slot;
     if (ok) {
-      inverse_send_list(m, o->nsend, o->send_idx, off, slot);
+      pa_op_inverse_send_list(m, o->nsend, o->send_idx, off, slot);
       o->d_pk_off = (int*)pa_rt_malloc(((size_t)m + 1) * sizeof(int));
       o->d_pk_slot = (int*)pa_rt_malloc((size_t)o->nsend * sizeof(int));
       ok = o->d_pk_off && o->d_pk_slot && !pa_rt_h2d(o->d_pk_off, off, ((size_t)m + 1) * sizeof(int)) &&
@@ -1132,22 +725,13 @@ int preAlps_OperatorUpdateValues(const double* val) {
   if (!val) return PA_FAIL(" wrong test 'val != NULL'");
   double t0 = pa_wtime();
   g_update_copy_s = g_update_kernel_s = 0.0;
-  const int N = in->N, m = in->m;
-  const int* rp = o->src_rowptr;
+  const int N = in->N;
   double* d = NULL;
   if (o->scaled && !in->scaling) return PA_FAIL("the operator is scaled but holds no scaling vector");
-  if (o->scaled) {   /* the scaling vector of order_and_scale, from the new values */
+  if (o->scaled) {   /* the scaling vector of the build, from the new values */
     d = (double*)malloc((size_t)N * sizeof(double));
     if (!d) return PA_FAIL("out of host memory");
-    int zero_row = 0;
-#pragma omp parallel for num_threads(pa_host_threads()) schedule(static) reduction(|| : zero_row)
-    for (int i = 0; i < N; ++i) {
-      double mx = 0.0;
-      for (int k = rp[i]; k < rp[i + 1]; ++k) { double a = fabs(val[k]); if (a > mx) mx = a; }
-      if (mx == 0.0) zero_row = 1;
-      d[i] = mx > 0.0 ? sqrt(1.0 / mx) : 0.0;
-    }
-    if (zero_row) { free(d); return PA_FAIL("Impossible to scale the matrix, rcmin=0"); }
+    if (pa_op_scaling(N, o->src_rowptr, val, pa_host_threads(), d)) { free(d); return PA_FAIL("Impossible to scale the matrix, rcmin=0"); }
   }
   const int on_device = !g_plan_only && o->plan_ts != 0;
   double* d_pv = NULL;
@@ -1160,16 +744,9 @@ int preAlps_OperatorUpdateValues(const double* val) {
     d_pv = (double*)pa_rt_malloc((size_t)(o->lnnz ? o->lnnz : 1) * sizeof(double));
     if (!d_pv) { free(d); return PA_FAIL("no device memory for the new panel values: %s", pa_rt_error()); }
   }
-  /* the panel, as build_panel forms it: d[old row] * v * d[old column], in that order */
+  /* the panel, as the build forms it (pa_op_panel_value) */
   const CPLM_Mat_CSR_t* A = &in->A;
-#pragma omp parallel for num_threads(pa_host_threads()) schedule(static)
-  for (int i = 0; i < m; ++i) {
-    const int old = in->perm[in->row_off + i];
-    for (int e = A->rowPtr[i]; e < A->rowPtr[i + 1]; ++e) {
-      const double v = val[o->src[e]];
-      A->val[e] = d ? d[old] * v * d[in->perm[A->colInd[e]]] : v;
-    }
-  }
+  pa_op_panel_values(in->m, in->row_off, A->rowPtr, A->colInd, o->src, in->perm, d, val, pa_host_threads(), A->val);
   /* the last refusal is behind us: the new vector into the allocation the getter handed out */
   if (d) memcpy(in->scaling, d, (size_t)N * sizeof(double));
   free(d);
@@ -1346,7 +923,8 @@ int preAlps_hip_reference_rhs(double* rhs_local) {
   if (!in->built) return PA_FAIL("operator not built");
   int mmax = 0;
   for (int p = 0; p < in->nparts; ++p) { int l = in->rowPos[p + 1] - in->rowPos[p]; if (l > mmax) mmax = l; }
-  double* stream = (double*)malloc((size_t)mmax * sizeof(double));
+  double* stream = (double*)malloc((size_t)(mmax > 0 ? mmax : 1) * sizeof(double));
+  if (!stream) return PA_FAIL("out of host memory");
   srand(0);
   for (int i = 0; i < mmax; ++i) stream[i] = ((double)rand() / (double)RAND_MAX);
   double normb = 0.0;

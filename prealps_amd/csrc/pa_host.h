@@ -1,7 +1,8 @@
 /*
  * pa_host.h -- internal declarations shared by the C host sources of
  * libprealps_hip.so (context.c, operator.c, block_jacobi.c, and the solver: ecg.c, ecg_start.c, ecg_loops.c,
- * which share ecg_priv.h).  spmm_plan.c and ecg_plan.c stand apart: each includes its own header only.
+ * which share ecg_priv.h).  spmm_plan.c, ecg_plan.c, mtx_read.c and op_build.c stand apart: each includes its own
+ * header only (and pa_alloc.h, the allocation of large host arrays).
  */
 #ifndef PA_HOST_H
 #define PA_HOST_H
@@ -74,7 +75,7 @@ typedef struct {
   int* perm;        /* N: perm[new] = old */
   CPLM_Mat_CSR_t A; /* local row panel, global column ids (host) */
   int halo;         /* halo rows */
-  double* scaling;  /* N: d[i] of row i in the caller's (original) order, order_and_scale's d; NULL: built with scale = 0 */
+  double* scaling;  /* N: d[i] of row i in the caller's (original) order, pa_op_order's d; NULL: built with scale = 0 */
 } pa_operator_info_t;
 const pa_operator_info_t* pa_operator_info(void);
 /* Workgroups of the SpMM at panel stride ts when it can leave the ECG Gram block behind

@@ -9,17 +9,8 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
-#include <sys/mman.h>
 
-/* Large host arrays (hundreds of MB, written once): 2 MiB alignment + a transparent-huge-page
- * hint, so that filling them is not dominated by 4 KiB page faults.  Release with free(). */
-static inline void* pa_big_alloc(size_t bytes) {
-  void* p = NULL;
-  if (bytes < ((size_t)8 << 20)) return malloc(bytes ? bytes : 1);
-  if (posix_memalign(&p, (size_t)2 << 20, bytes)) return NULL;
-  (void)madvise(p, bytes, MADV_HUGEPAGE);
-  return p;
-}
+#include "pa_alloc.h"   /* pa_big_alloc */
 
 /* What a plan is cut from; every pointer is borrowed. */
 typedef struct {

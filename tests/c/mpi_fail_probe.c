@@ -1,5 +1,5 @@
 /* Test helper (built by tests/test_mpi_cpu.py with gcc + libmpi): what happens to an MPI run when the set-up
- * fails on rank 0 only (a file that does not exist: only rank 0 reads it).  usage:
+ * fails on rank 0 only (a file that does not exist, or one whose matrix the build refuses: only rank 0 reads it).  usage:
  *   mpiexec -n P mpi_fail_probe <file.mtx> <abort_mode 0|1>
  * abort_mode 1 (the library's default): the failing rank prints the reference's abort banner and the whole run
  * ends through MPI_Abort(MPI_COMM_WORLD, 1), as CPLM_Abort does (utils/cplm_core/cplm_utils.c:42-58).

@@ -162,6 +162,27 @@ def test_failure_on_rank_zero_ends_every_rank(tmp_path, abort_mode):
         assert sorted(r.stdout.split("\n")[:3]) == ["rank 0: rc 1", "rank 1: rc 1", "rank 2: rc 1"]
 
 
+@pytest.mark.skipif(not have_mpi, reason="no MPI launcher in this image")
+def test_a_matrix_rank_zero_refuses_ends_every_rank(tmp_path):
+    """The file exists and reads well, but a row has no diagonal entry: rank 0 fails after the reader, inside the
+    ordering.  In return-code mode all three ranks come back with 1 through the common exit of the distributed build."""
+    rp, ci, v = gen.poisson3d_csr(5)
+    keep = np.ones(len(ci), bool)
+    keep[rp[9] + int(np.flatnonzero(ci[rp[9]:rp[10]] == 9)[0])] = False
+    rows = np.repeat(np.arange(len(rp) - 1), np.diff(rp))[keep]
+    mtx = str(tmp_path / "no_diagonal.mtx")
+    with open(mtx, "w") as f:
+        f.write("%%%%MatrixMarket matrix coordinate real general\n%d %d %d\n" % (len(rp) - 1, len(rp) - 1, keep.sum()))
+        for r, c, x in zip(rows, ci[keep], v[keep]):
+            f.write("%d %d %.17g\n" % (r + 1, c + 1, x))
+    exe = str(tmp_path / "mpi_fail_probe")
+    _cc(os.path.join(ROOT, "tests", "c", "mpi_fail_probe.c"), exe)
+    r = subprocess.run([MPIEXEC, "-n", "3", exe, mtx, "0"], env=dict(os.environ, OMP_NUM_THREADS="2", PREALPS_MPI_TIMEOUT="60"),
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.stdout, r.stderr[-2000:])
+    assert sorted(r.stdout.split("\n")[:3]) == ["rank 0: rc 1", "rank 1: rc 1", "rank 2: rc 1"]
+
+
 def test_open_mpi_launcher_is_refused_in_return_code_mode(tmp_path):
     """Under an Open MPI launcher (its communicators are pointers, the run-time binding speaks the MPICH ABI)
     preAlps_OperatorBuild must fail -- also when the library returns error codes instead of aborting: going on

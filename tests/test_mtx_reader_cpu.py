@@ -1,4 +1,4 @@
-"""The MatrixMarket reader of preAlps_OperatorBuild (operator.c: mapped file, parsed by the host threads in
+"""The MatrixMarket reader of preAlps_OperatorBuild (mtx_read.c: mapped file, parsed by the host threads in
 line-aligned pieces) against scipy on the cases of utils/cplm_light/cplm_matcsr.c:96-243: general and
 symmetric files, 1- and 0-based indices, repeated entries (summed), blank lines, CRLF line ends, a last
 line without newline, and a file large enough that every thread gets a piece."""
