@@ -28,6 +28,7 @@
 #include "op_build.h"
 #include "pa_alloc.h"
 #include "spmm_plan.h"
+#include "spmm_pack.h"
 
 typedef struct {
   pa_operator_info_t info;
@@ -63,7 +64,12 @@ typedef struct {
   int* src_rowptr;     /* the caller's rowPtr (N + 1): the rows of the scaling vector */
   int* src;            /* panel entry -> index into the caller's val (lnnz) */
   int plan_staged_sw, plan_runs_sw, plan_cus;   /* what build_plan gave the builders for the current plan */
-  size_t plan_val_n;   /* values the upload copied */
+  size_t plan_val_n;   /* values of the host plan's value array (packed or not: what the value map counts) */
+  /* the packed value array of a run plan (spmm_pack.h): plan.val holds pk_nval values and the slack, plan.pk_meta
+   * the masks and offsets; the unpacked array is then not on the device */
+  size_t pk_nval;
+  double pk_stream_bytes;   /* bytes of matrix data one product streams from the packed plan */
+  int repacks;              /* updates of the values that had to pack anew */
   unsigned* d_vmap;    /* device: stored value -> panel entry + 1, 0 = padding (plan_val_n entries; NULL: not cut yet) */
   int values_epoch;    /* 0 after a build, + 1 per update */
   int vmap_builds;     /* value maps cut for this operator */
@@ -91,10 +97,12 @@ static int env_int(const char* name, int dflt) {
 /* --------------------------------------------------------------- free ---- */
 static void free_plan(pa_operator_t* o) {
   for (int i = 0; i < PA_PL_COUNT; ++i) { pa_rt_free(o->d_plan[i]); o->d_plan[i] = NULL; }
-  memset(&o->plan, 0, sizeof(o->plan));
   o->plan_ts = 0;
+  pa_rt_free((void*)o->plan.pk_meta);
+  memset(&o->plan, 0, sizeof(o->plan));
   pa_rt_free(o->d_vmap); o->d_vmap = NULL;   /* the value map belongs to the plan */
   o->plan_val_n = 0;
+  o->pk_nval = 0; o->pk_stream_bytes = 0.0;
 }
 
 void preAlps_OperatorFree(void) {
@@ -114,16 +122,37 @@ void preAlps_OperatorFree(void) {
 }
 
 /* ------------------------------------------------------------ the plan ---- */
+/* The packed value array and its masks into fresh device arrays (pk may be released afterwards). */
+static int upload_pack(const pa_spmm_pack_t* pk, void** d_val, void** d_meta) {
+  *d_val = pa_rt_malloc(pk->nval_alloc * sizeof(double));
+  *d_meta = pa_rt_malloc(pk->nsteps_alloc * 4 * sizeof(uint64_t));
+  if (!*d_val || !*d_meta || pa_rt_h2d(*d_val, pk->val, pk->nval_alloc * sizeof(double)) ||
+      pa_rt_h2d(*d_meta, pk->meta, pk->nsteps_alloc * 4 * sizeof(uint64_t))) {
+    pa_rt_free(*d_val); pa_rt_free(*d_meta);
+    *d_val = *d_meta = NULL;
+    return 1;
+  }
+  return 0;
+}
+
 /* The plan is cut on the host (spmm_plan.c); here it goes to the device: every array of the host
- * plan into a device array of its own, owned by o->d_plan[], and the pointers into o->plan. */
-static int upload_plan(pa_operator_t* o, const pa_spmm_host_plan_t* hp) {
+ * plan into a device array of its own, owned by o->d_plan[], and the pointers into o->plan.
+ * pk != NULL: the values go up packed (spmm_pack.h) and the host plan's own value array stays on the host. */
+static int upload_plan(pa_operator_t* o, const pa_spmm_host_plan_t* hp, const pa_spmm_pack_t* pk) {
   for (int i = 0; i < PA_PL_COUNT; ++i) {
     const pa_plan_array_t* a = &hp->a[i];
-    if (!a->p) continue;
+    if (!a->p || (pk && i == PA_PL_VAL)) continue;
     o->d_plan[i] = pa_rt_malloc(a->n_alloc * a->elem);
     if (!o->d_plan[i] || pa_rt_h2d(o->d_plan[i], a->p, a->n * a->elem)) return 1;
   }
   pa_spmm_plan_t* pl = &o->plan;
+  if (pk) {
+    void* d_meta = NULL;
+    if (upload_pack(pk, &o->d_plan[PA_PL_VAL], &d_meta)) return 1;
+    pl->packed = 1; pl->pk_meta = (const unsigned long long*)d_meta;
+    o->pk_nval = pk->nval;
+    o->pk_stream_bytes = hp->stream_bytes - pk->unpacked_bytes + pk->packed_bytes;
+  }
   pl->m = hp->m; pl->nslices = hp->nslices; pl->nblk = hp->nblk; pl->n_interior = hp->n_interior;
   pl->win_cap = hp->win_cap; pl->staged = hp->staged; pl->stage_cap = hp->stage_cap;
   pl->runs = hp->runs; pl->runs_cols = hp->runs_cols;
@@ -137,7 +166,7 @@ static int upload_plan(pa_operator_t* o, const pa_spmm_host_plan_t* hp) {
   o->stream_bytes = hp->stream_bytes;
   o->plan_val_n = hp->a[PA_PL_VAL].n;
   if (hp->runs) {   /* what preAlps_hip_debug_move_plan copies */
-    g_dbg_val_bytes = hp->a[PA_PL_VAL].n_alloc * hp->a[PA_PL_VAL].elem;
+    g_dbg_val_bytes = pk ? pk->nval_alloc * sizeof(double) : hp->a[PA_PL_VAL].n_alloc * hp->a[PA_PL_VAL].elem;
     g_dbg_slot_bytes = hp->a[PA_PL_COL16].n_alloc * hp->a[PA_PL_COL16].elem;
   }
   return 0;
@@ -164,7 +193,21 @@ static int build_plan(pa_operator_t* o, int ts) {
   if (pa_spmm_plan_build(&pin, &hp))
     return hp.oom_entries ? PA_FAIL("out of host memory for %zu SELL entries", hp.oom_entries)
                           : PA_FAIL("out of host memory for the SpMM plan");
-  int rc = upload_plan(o, &hp);
+  /* A run plan at up to 4 columns goes up without its stored +0.0 values (spmm_pack.h) when that takes a tenth
+   * off the matrix stream: whole element matrices assembled into the pattern (Q1 elasticity: 37 % zeros) and the
+   * padding.  PREALPS_SPMM_PACK=0 / 1 forces. */
+  pa_spmm_pack_t pk;
+  int packed = 0;
+  const int pack_sw = env_int("PREALPS_SPMM_PACK", -1);
+  if (hp.runs && hp.runs_cols == ts && ts <= 4 && pack_sw != 0) {
+    int prc = pa_spmm_pack_build((const double*)hp.a[PA_PL_VAL].p, (const long long*)hp.a[PA_PL_SL_OFF].p,
+                                 (const int*)hp.a[PA_PL_SL_LEN].p, hp.nslices, 0, &pk);
+    if (prc == -1) { pa_spmm_plan_free(&hp); return PA_FAIL("out of host memory for the packed values of the SpMM plan"); }
+    packed = prc == 0 && (pack_sw > 0 || hp.stream_bytes - pk.unpacked_bytes + pk.packed_bytes < 0.9 * hp.stream_bytes);
+    if (prc == 0 && !packed) pa_spmm_pack_free(&pk);
+  }
+  int rc = upload_plan(o, &hp, packed ? &pk : NULL);
+  if (packed) pa_spmm_pack_free(&pk);
   pa_spmm_plan_free(&hp);
   if (rc) return PA_FAIL("uploading the SpMM plan failed: %s", pa_rt_error());
   o->plan_ts = ts;
@@ -712,10 +755,45 @@ static int ensure_value_map(pa_operator_t* o) {
   return rc;
 }
 
+/* The packed values of the current run plan anew, from the host panel as it stands: the plan a build would cut
+ * for it (the same slices, slots and blocks: no decision of a builder reads a value), packed and uploaded into
+ * fresh arrays; the old ones go only when the new ones are on the device. */
+static int repack_plan(pa_operator_t* o) {
+  pa_spmm_plan_in_t pin = plan_input(o, o->plan_ts);
+  pa_spmm_host_plan_t hp;
+  if (pa_spmm_plan_build(&pin, &hp)) return PA_FAIL("out of host memory for the SpMM plan");
+  pa_spmm_pack_t pk;
+  int rc = 0;
+  if (!hp.runs || hp.nslices != o->plan.nslices || hp.a[PA_PL_VAL].n != o->plan_val_n) {
+    pa_spmm_plan_free(&hp);
+    return PA_FAIL("the SpMM plan cut for the new values does not fit the plan on the device");
+  }
+  if (pa_spmm_pack_build((const double*)hp.a[PA_PL_VAL].p, (const long long*)hp.a[PA_PL_SL_OFF].p,
+                         (const int*)hp.a[PA_PL_SL_LEN].p, hp.nslices, 0, &pk)) {
+    pa_spmm_plan_free(&hp);
+    return PA_FAIL("out of host memory for the packed values of the SpMM plan");
+  }
+  void *d_val = NULL, *d_meta = NULL;
+  if (upload_pack(&pk, &d_val, &d_meta)) rc = PA_FAIL("uploading the packed values failed: %s", pa_rt_error());
+  else {
+    pa_rt_free(o->d_plan[PA_PL_VAL]); pa_rt_free((void*)o->plan.pk_meta);
+    o->d_plan[PA_PL_VAL] = d_val; o->plan.val = (const double*)d_val;
+    o->plan.pk_meta = (const unsigned long long*)d_meta;
+    o->pk_nval = pk.nval;
+    o->pk_stream_bytes = hp.stream_bytes - pk.unpacked_bytes + pk.packed_bytes;
+    g_dbg_val_bytes = pk.nval_alloc * sizeof(double);
+    ++o->repacks;
+  }
+  pa_spmm_pack_free(&pk);
+  pa_spmm_plan_free(&hp);
+  return rc;
+}
+
 /* The operator that a fresh preAlps_OperatorBuildFromCSR with these values (same pattern, partition and scale) would
  * give, bit for bit, without the build: the host panel is rewritten through o->src, the plan on the device through
  * its value map (k_plan_set_values); every address stays.  Every refusal and every allocation comes before the first
- * write. */
+ * write.  A packed run plan (spmm_pack.h) is written through its masks (k_pack_set_values); only when a value that
+ * the pack dropped as +0.0 becomes something else are the values packed anew, into new arrays (repack_plan). */
 int preAlps_OperatorUpdateValues(const double* val) {
   pa_operator_t* o = &g_op;
   pa_operator_info_t* in = &o->info;
@@ -735,6 +813,7 @@ int preAlps_OperatorUpdateValues(const double* val) {
   }
   const int on_device = !g_plan_only && o->plan_ts != 0;
   double* d_pv = NULL;
+  unsigned* d_miss = NULL;
   if (on_device) {
     double tm = pa_wtime();
     const int cut = !o->d_vmap;
@@ -743,6 +822,10 @@ int preAlps_OperatorUpdateValues(const double* val) {
     t0 += pa_wtime() - tm;
     d_pv = (double*)pa_rt_malloc((size_t)(o->lnnz ? o->lnnz : 1) * sizeof(double));
     if (!d_pv) { free(d); return PA_FAIL("no device memory for the new panel values: %s", pa_rt_error()); }
+    if (o->plan.packed) {
+      d_miss = (unsigned*)pa_rt_malloc(sizeof(unsigned));
+      if (!d_miss) { free(d); pa_rt_free(d_pv); return PA_FAIL("no device memory for the update of the packed plan: %s", pa_rt_error()); }
+    }
   }
   /* the panel, as the build forms it (pa_op_panel_value) */
   const CPLM_Mat_CSR_t* A = &in->A;
@@ -759,8 +842,25 @@ int preAlps_OperatorUpdateValues(const double* val) {
   g_update_copy_s = pa_wtime() - t0;
   void* e0 = pa_rt_event_create();
   void* e1 = pa_rt_event_create();
-  rc = rc || !e0 || !e1 || pa_rt_event_record(e0) ||
-       pa_k_plan_set_values(o->d_vmap, d_pv, (double*)o->plan.val, o->plan_val_n) || pa_rt_event_record(e1) || pa_rt_sync();
+  if (o->plan.packed) {
+    /* the packed values have places only for what was not +0.0: count first what has none, write nothing */
+    unsigned misses = 0;
+    rc = rc || !e0 || !e1 || pa_rt_event_record(e0) || pa_rt_memset(d_miss, 0, sizeof(unsigned)) ||
+         pa_k_pack_set_values(o->d_vmap, d_pv, o->plan.pk_meta, (double*)o->plan.val, o->plan_val_n, 0, d_miss) ||
+         pa_rt_d2h(&misses, d_miss, sizeof(unsigned));
+    if (!rc && misses) {
+      /* a dropped place receives a value: pack anew, from the plan a fresh build would cut; the address moves */
+      pa_rt_event_destroy(e0); pa_rt_event_destroy(e1);
+      pa_rt_free(d_pv); pa_rt_free(d_miss);
+      return repack_plan(o);
+    }
+    rc = rc || pa_k_pack_set_values(o->d_vmap, d_pv, o->plan.pk_meta, (double*)o->plan.val, o->plan_val_n, 1, d_miss) ||
+         pa_rt_event_record(e1) || pa_rt_sync();
+    pa_rt_free(d_miss);
+  } else {
+    rc = rc || !e0 || !e1 || pa_rt_event_record(e0) ||
+         pa_k_plan_set_values(o->d_vmap, d_pv, (double*)o->plan.val, o->plan_val_n) || pa_rt_event_record(e1) || pa_rt_sync();
+  }
   if (!rc) g_update_kernel_s = pa_rt_event_elapsed_s(e0, e1);
   pa_rt_event_destroy(e0); pa_rt_event_destroy(e1);
   pa_rt_free(d_pv);             /* (the launch has finished) */
@@ -879,6 +979,10 @@ int preAlps_hip_get_stat(const char* key, double* value) {
   else if (!strcmp(key, "spmm_slices")) *value = o->plan.nslices;
   else if (!strcmp(key, "spmm_stored_entries")) *value = o->sell_entries;
   else if (!strcmp(key, "spmm_stream_bytes")) *value = o->stream_bytes;
+  else if (!strcmp(key, "spmm_packed")) *value = o->plan.packed;      /* the values are on the device without their zeros */
+  else if (!strcmp(key, "spmm_packed_values")) *value = (double)o->pk_nval;
+  else if (!strcmp(key, "spmm_packed_stream_bytes")) *value = o->pk_stream_bytes;
+  else if (!strcmp(key, "spmm_repacks")) *value = o->repacks;
   else if (!strcmp(key, "spmm_val_address")) *value = (double)(uintptr_t)o->plan.val;      /* (for the run-to-run spread study) */
   else if (!strcmp(key, "spmm_slot_address")) *value = (double)(uintptr_t)o->plan.col16;
   else if (!strcmp(key, "spmm_staged")) *value = o->plan.staged;

@@ -100,6 +100,11 @@ typedef struct {
   const int* blk_nlow;
   int runs_cols;            /* columns a workgroup of the run plan stages and computes (= the panel stride, or 8
                              * when a 16-column panel is split between two workgroups) */
+  /* packed run plan (spmm_pack.h): `val` holds only the values that are not +0.0 and pk_meta four 64-bit words
+   * per step -- three presence masks and the index of the step's part of `val`, a 0.0 and then its kept values;
+   * sl_off / sl_len still count runs */
+  int packed;
+  const unsigned long long* pk_meta;
 } pa_spmm_plan_t;
 /* phase 0: interior blocks, 1: halo-reading blocks, 2: all */
 int pa_k_spmm(const pa_spmm_plan_t* pl, int ts, const double* X, const double* Xhalo,
@@ -133,6 +138,11 @@ int pa_k_bj_gram_take(const double* in, const double* out);
  * slots the upload copied (n even; entries past n are not touched).  map: spmm_plan.h, pa_spmm_plan_value_map;
  * pv: the panel's values in panel order.  All three on the device. */
 int pa_k_plan_set_values(const unsigned* map, const double* pv, double* val, size_t n);
+/* The same for a packed run plan (spmm_pack.h), over the n slots of the unpacked array: write = 0 counts into
+ * *misses (device, zeroed by the caller) the slots whose new value is not +0.0 while the pack has no place for
+ * it and writes nothing; write = 1 stores the new value of every slot that has a place in `packed`. */
+int pa_k_pack_set_values(const unsigned* map, const double* pv, const unsigned long long* meta, double* packed,
+                         size_t n, int write, unsigned* misses);
 /* sendbuf[i*ts + c] = X[idx[i]*ts + c] */
 int pa_k_pack_rows(int n, int ts, const int* idx, const double* X, double* sendbuf);
 

@@ -224,7 +224,52 @@ __device__ __forceinline__ void spmm_runs_fma(const double* sx, const int (&sl)[
   }
 }
 
-template <int TS, int XS, bool GRAM, int RL>
+// PACK: the value array of the run plan without its +0.0 entries (spmm_pack.h).  Per step of a slice four 64-bit
+// words -- the presence masks of the three positions and the index of the step's part of the packed array, which
+// is one 0.0 and then the kept values -- all wavefront-uniform: they are read with uniform indices (scalar
+// loads, one group ahead of the values they address) and live in SGPRs.  A lane's value of position p lies at
+// 1 + (kept values of the positions before p) + (set bits of mask p below the lane); a lane without a value reads
+// the step's 0.0 instead.  The load is unconditional, the choice is made on the offset, with the mask itself as
+// the condition register; what was skipped was +0.0, so every FMA sees the bits it saw and the sums are the same.
+typedef unsigned long long pk_u64;
+struct spmm_pk { pk_u64 m[9]; pk_u64 base[3]; };
+__device__ __forceinline__ void spmm_pack_meta(const pk_u64* __restrict__ mp, int g, int len, spmm_pk& M) {
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int k = g * 3 + j, kc = min(k, len - 1);
+    // (the constant address space: nothing writes the words while a product runs, and a uniform load from it is
+    // a scalar load whatever stores the kernel has)
+    typedef const __attribute__((address_space(4))) pk_u64* kdp;
+    const kdp q = (kdp)(mp + (size_t)kc * 4);
+    const pk_u64 w0 = q[0], w1 = q[1], w2 = q[2], w3 = q[3];      // (unconditional, as the vector loads are)
+    const bool in = k < len;      // (a step beyond the slice: no lane has a value)
+    M.m[3 * j] = in ? w0 : 0ull; M.m[3 * j + 1] = in ? w1 : 0ull; M.m[3 * j + 2] = in ? w2 : 0ull;
+    M.base[j] = w3;
+  }
+}
+__device__ __forceinline__ void spmm_runs_load_pack(const unsigned short* __restrict__ cp, const double* __restrict__ vpk,
+                                                    const spmm_pk& M, unsigned lane, int g, int len, int (&sl)[3],
+                                                    double (&vv)[9]) {
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int kc = min(g * 3 + j, len - 1);
+    sl[j] = cp[(size_t)kc * 64 + lane];
+    typedef const __attribute__((address_space(1))) char* gcp;
+    typedef const __attribute__((address_space(1))) double* gdp;
+    const gcp vk = (gcp)(vpk + M.base[j]);      // a scalar base; the lane adds a 32-bit byte offset (< 193 * 8)
+    unsigned first = 1u;          // the place of the position's first kept value
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const pk_u64 mk = M.m[3 * j + i];
+      const unsigned at = __builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, first));
+      const unsigned byte = (__builtin_amdgcn_inverse_ballot_w64(mk) ? at : 0u) << 3;
+      vv[3 * j + i] = *(gdp)(vk + byte);
+      first += (unsigned)__builtin_popcountll(mk);
+    }
+  }
+}
+
+template <int TS, int XS, bool GRAM, int RL, bool PACK = false>
 __device__ __forceinline__ void spmm_runs_block(
     int m, const long long* __restrict__ sl_off, const int* __restrict__ sl_len,
     const int* __restrict__ sl_row0, const int* __restrict__ sl_nrows,
@@ -233,9 +278,10 @@ __device__ __forceinline__ void spmm_runs_block(
     const int* __restrict__ blk_nlow, const int* __restrict__ ext_rows,
     const int* __restrict__ order, const double* __restrict__ X,
     const double* __restrict__ Xh, double* __restrict__ Y,
-    const double* __restrict__ Rg, double* __restrict__ gpart, int gbase, int logical, int coff);
+    const double* __restrict__ Rg, double* __restrict__ gpart, int gbase, int logical, int coff,
+    const pk_u64* __restrict__ meta);
 
-template <int TS, int XS, bool GRAM, int RL = 3>
+template <int TS, int XS, bool GRAM, int RL = 3, bool PACK = false>
 __device__ __forceinline__ void spmm_runs_body(
     int m, const long long* __restrict__ sl_off, const int* __restrict__ sl_len,
     const int* __restrict__ sl_row0, const int* __restrict__ sl_nrows,
@@ -244,18 +290,22 @@ __device__ __forceinline__ void spmm_runs_body(
     const int* __restrict__ blk_nlow, const int* __restrict__ ext_rows,
     const int* __restrict__ order, int nlist, const double* __restrict__ X,
     const double* __restrict__ Xh, double* __restrict__ Y,
-    const double* __restrict__ Rg, double* __restrict__ gpart, int gbase) {
+    const double* __restrict__ Rg, double* __restrict__ gpart, int gbase,
+    const pk_u64* __restrict__ meta = nullptr) {
   constexpr int NS = XS / TS;
   const int cpx = (nlist + 7) >> 3;
   const int idx = blockIdx.x >> 3;
   const int logical = (blockIdx.x & 7) * cpx + idx / NS;
   if (logical >= nlist) return;
-  spmm_runs_block<TS, XS, GRAM, RL>(m, sl_off, sl_len, sl_row0, sl_nrows, slot16, val, blk_slice, blk_ext_off, blk_nlow,
-                                         ext_rows, order, X, Xh, Y, Rg, gpart, gbase, logical, (idx % NS) * TS);
+  spmm_runs_block<TS, XS, GRAM, RL, PACK>(m, sl_off, sl_len, sl_row0, sl_nrows, slot16, val, blk_slice, blk_ext_off,
+                                          blk_nlow, ext_rows, order, X, Xh, Y, Rg, gpart, gbase, logical,
+                                          (idx % NS) * TS, meta);
 }
 
 // One block of slices: `logical` = its place in the launch's list, `coff` = first of the TS columns.
-template <int TS, int XS, bool GRAM, int RL>
+// PACK: `val` is the packed value array and `meta` its masks and offsets; everything but the value fetch is
+// the same code.
+template <int TS, int XS, bool GRAM, int RL, bool PACK>
 __device__ __forceinline__ void spmm_runs_block(
     int m, const long long* __restrict__ sl_off, const int* __restrict__ sl_len,
     const int* __restrict__ sl_row0, const int* __restrict__ sl_nrows,
@@ -264,8 +314,10 @@ __device__ __forceinline__ void spmm_runs_block(
     const int* __restrict__ blk_nlow, const int* __restrict__ ext_rows,
     const int* __restrict__ order, const double* __restrict__ X,
     const double* __restrict__ Xh, double* __restrict__ Y,
-    const double* __restrict__ Rg, double* __restrict__ gpart, int gbase, int logical, int coff) {
+    const double* __restrict__ Rg, double* __restrict__ gpart, int gbase, int logical, int coff,
+    const pk_u64* __restrict__ meta) {
   static_assert(!GRAM || (TS == 4 && XS == 4), "the fused Gram block is built for 4-column panels");
+  static_assert(!PACK || (RL == 3 && TS == XS && TS <= 4), "the packed values are read by the narrow run kernels");
   extern __shared__ double sx[];
   const int b = order[logical];
   const int s0 = blk_slice[b], s1 = blk_slice[b + 1];
@@ -287,12 +339,24 @@ __device__ __forceinline__ void spmm_runs_block(
   int len = 0;
   const unsigned short* __restrict__ cp = slot16;
   const double* __restrict__ vp = val;
+  // PACK: the masks and offsets of the group whose values are requested next
+  const pk_u64* __restrict__ mp = meta;
+  spmm_pk pN;
   if (s < s1) {
     const long long off = sl_off[s];
     len = sl_len[s];
     cp = slot16 + off;
-    vp = val + RL * off;
-    if (len > 0) spmm_runs_load<RL>(cp, vp, lane, 0, len, slA, vA);
+    if constexpr (PACK) {
+      mp = meta + (size_t)(off >> 6) * 4;
+      if (len > 0) {
+        spmm_pack_meta(mp, 0, len, pN);
+        spmm_runs_load_pack(cp, val, pN, lane, 0, len, slA, vA);
+        spmm_pack_meta(mp, min(1, (len + RU - 1) / RU - 1), len, pN);
+      }
+    } else {
+      vp = val + RL * off;
+      if (len > 0) spmm_runs_load<RL>(cp, vp, lane, 0, len, slA, vA);
+    }
   }
 
   // Staging: LDS row L of [external rows below | own rows | external rows above] comes from global row
@@ -341,17 +405,34 @@ __device__ __forceinline__ void spmm_runs_block(
       const int ngt = (len + RU - 1) / RU;
       // (one exit at the bottom and the odd group behind the loop: with an exit in the middle the register
       // allocator copies the set that is in flight at the end of every round, behind a full wait)
-      for (int i = 0; i < (ngt >> 1); ++i) {
-        spmm_runs_load<RL>(cp, vp, lane, 2 * i + 1, len, slB, vB);
-        __builtin_amdgcn_sched_barrier(0);      // (keeps the requests in front of the sums of the group before)
-        spmm_runs_fma<TS, RL>(sx, slA, vA, acc);
-        __builtin_amdgcn_sched_barrier(0);
-        spmm_runs_load<RL>(cp, vp, lane, min(2 * i + 2, ngt - 1), len, slA, vA);
-        __builtin_amdgcn_sched_barrier(0);
-        spmm_runs_fma<TS, RL>(sx, slB, vB, acc);
-        __builtin_amdgcn_sched_barrier(0);
+      if constexpr (PACK) {
+        // the same rounds; the masks and offsets of a group were requested when the group before it was
+        for (int i = 0; i < (ngt >> 1); ++i) {
+          spmm_runs_load_pack(cp, val, pN, lane, 2 * i + 1, len, slB, vB);
+          spmm_pack_meta(mp, min(2 * i + 2, ngt - 1), len, pN);
+          __builtin_amdgcn_sched_barrier(0);
+          spmm_runs_fma<TS, RL>(sx, slA, vA, acc);
+          __builtin_amdgcn_sched_barrier(0);
+          spmm_runs_load_pack(cp, val, pN, lane, min(2 * i + 2, ngt - 1), len, slA, vA);
+          spmm_pack_meta(mp, min(2 * i + 3, ngt - 1), len, pN);
+          __builtin_amdgcn_sched_barrier(0);
+          spmm_runs_fma<TS, RL>(sx, slB, vB, acc);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        if (ngt & 1) spmm_runs_fma<TS, RL>(sx, slA, vA, acc);
+      } else {
+        for (int i = 0; i < (ngt >> 1); ++i) {
+          spmm_runs_load<RL>(cp, vp, lane, 2 * i + 1, len, slB, vB);
+          __builtin_amdgcn_sched_barrier(0);      // (keeps the requests in front of the sums of the group before)
+          spmm_runs_fma<TS, RL>(sx, slA, vA, acc);
+          __builtin_amdgcn_sched_barrier(0);
+          spmm_runs_load<RL>(cp, vp, lane, min(2 * i + 2, ngt - 1), len, slA, vA);
+          __builtin_amdgcn_sched_barrier(0);
+          spmm_runs_fma<TS, RL>(sx, slB, vB, acc);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        if (ngt & 1) spmm_runs_fma<TS, RL>(sx, slA, vA, acc);
       }
-      if (ngt & 1) spmm_runs_fma<TS, RL>(sx, slA, vA, acc);
     }
     const int nr = sl_nrows[s], row_s = sl_row0[s];
     if (lane < nr) {
@@ -368,8 +449,17 @@ __device__ __forceinline__ void spmm_runs_block(
       const long long off = sl_off[sn];
       len = sl_len[sn];
       cp = slot16 + off;
-      vp = val + RL * off;
-      if (len > 0) spmm_runs_load<RL>(cp, vp, lane, 0, len, slA, vA);
+      if constexpr (PACK) {
+        mp = meta + (size_t)(off >> 6) * 4;
+        if (len > 0) {
+          spmm_pack_meta(mp, 0, len, pN);
+          spmm_runs_load_pack(cp, val, pN, lane, 0, len, slA, vA);
+          spmm_pack_meta(mp, min(1, (len + RU - 1) / RU - 1), len, pN);
+        }
+      } else {
+        vp = val + RL * off;
+        if (len > 0) spmm_runs_load<RL>(cp, vp, lane, 0, len, slA, vA);
+      }
     }
   }
   if constexpr (GRAM) spmm_gram_tail(gw, gg, sx, wave, lane, tid, gpart + (size_t)(gbase + logical) * 32);
@@ -405,6 +495,33 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(5))) void k_
                              ext_rows, order, nlist, X, Xh, Y, Rg, gpart, gbase);
 }
 
+// The run kernels on the packed value array (2 and 4 columns): the same grid, staging and occupancy.
+template <int TS>
+__global__ __launch_bounds__(WG, 5) void k_spmm_runs_pack(
+    int m, const long long* __restrict__ sl_off, const int* __restrict__ sl_len,
+    const int* __restrict__ sl_row0, const int* __restrict__ sl_nrows,
+    const unsigned short* __restrict__ slot16, const double* __restrict__ val, const pk_u64* __restrict__ meta,
+    const int* __restrict__ blk_slice, const int* __restrict__ blk_ext_off,
+    const int* __restrict__ blk_nlow, const int* __restrict__ ext_rows,
+    const int* __restrict__ order, int nlist, const double* __restrict__ X,
+    const double* __restrict__ Xh, double* __restrict__ Y) {
+  spmm_runs_body<TS, TS, false, 3, true>(m, sl_off, sl_len, sl_row0, sl_nrows, slot16, val, blk_slice, blk_ext_off,
+                                         blk_nlow, ext_rows, order, nlist, X, Xh, Y, nullptr, nullptr, 0, meta);
+}
+
+__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(5))) void k_spmm_runs_gram_pack(
+    int m, const long long* __restrict__ sl_off, const int* __restrict__ sl_len,
+    const int* __restrict__ sl_row0, const int* __restrict__ sl_nrows,
+    const unsigned short* __restrict__ slot16, const double* __restrict__ val, const pk_u64* __restrict__ meta,
+    const int* __restrict__ blk_slice, const int* __restrict__ blk_ext_off,
+    const int* __restrict__ blk_nlow, const int* __restrict__ ext_rows,
+    const int* __restrict__ order, int nlist, const double* __restrict__ X,
+    const double* __restrict__ Xh, double* __restrict__ Y,
+    const double* __restrict__ Rg, double* __restrict__ gpart, int gbase) {
+  spmm_runs_body<4, 4, true, 3, true>(m, sl_off, sl_len, sl_row0, sl_nrows, slot16, val, blk_slice, blk_ext_off, blk_nlow,
+                                      ext_rows, order, nlist, X, Xh, Y, Rg, gpart, gbase, meta);
+}
+
 template <int TS>
 __global__ __launch_bounds__(WG) void k_pack_rows(int n, const int* __restrict__ idx,
                                                   const double* __restrict__ X,
@@ -435,7 +552,12 @@ static int launch_spmm(const pa_spmm_plan_t* pl, const int* order, int nlist, co
       const int cpx = (nlist + 7) / 8;
       // (spmm_gram_tail passes the wavefronts' shares through the first 1024 bytes, whatever a tiny plan stages)
       const size_t lds_gram = lds > 1024 ? lds : 1024;
-      if (pl->runs)
+      if (pl->runs && pl->packed)
+        PA_LAUNCH(k_spmm_runs_gram_pack, dim3(cpx * 8), dim3(WG), lds_gram, cur_stream(), pl->m, pl->sl_off,
+                  pl->sl_len, pl->sl_row0, pl->sl_nrows, pl->col16, pl->val, pl->pk_meta, pl->blk_slice,
+                  pl->blk_ext_off, pl->blk_nlow, pl->ext_rows, order, nlist, X, Xh, Y, g_sg.R, g_sg.partials,
+                  g_sg.count);
+      else if (pl->runs)
         PA_LAUNCH(k_spmm_runs_gram<3>, dim3(cpx * 8), dim3(WG), lds_gram, cur_stream(), pl->m, pl->sl_off,
                   pl->sl_len, pl->sl_row0, pl->sl_nrows, pl->col16, pl->val, pl->blk_slice, pl->blk_ext_off,
                   pl->blk_nlow, pl->ext_rows, order, nlist, X, Xh, Y, g_sg.R, g_sg.partials, g_sg.count);
@@ -463,6 +585,19 @@ static int launch_spmm(const pa_spmm_plan_t* pl, const int* order, int nlist, co
       }
     }
     if (g_sg.armed && X == g_sg.X && Y == g_sg.Y) g_sg.count = -1;    // this product leaves no Gram block
+  }
+  if (pl->runs && pl->packed) {       // the value array without its zeros: the narrow run kernel reads it
+    if constexpr (TS <= 4) {
+      const size_t lds = (size_t)pl->stage_cap * TS * 8;
+      const int cpx = (nlist + 7) / 8;
+      PA_LAUNCH((k_spmm_runs_pack<TS>), dim3(cpx * 8), dim3(WG), lds, cur_stream(), pl->m, pl->sl_off, pl->sl_len,
+                pl->sl_row0, pl->sl_nrows, pl->col16, pl->val, pl->pk_meta, pl->blk_slice, pl->blk_ext_off,
+                pl->blk_nlow, pl->ext_rows, order, nlist, X, Xh, Y);
+      return kfail("k_spmm_runs_pack");
+    } else {
+      pa_rt_set_error("a packed run plan at panel stride %d: no kernel reads it", TS);
+      return 1;
+    }
   }
   if (pl->runs) {
     // a plan cut for half the panel stride (16 columns): two workgroups per block, 8 of the 16 columns each.

@@ -26,7 +26,47 @@ __global__ __launch_bounds__(WG) void k_plan_set_values(const u2v* __restrict__ 
   }
 }
 
+// The packed run plan (spmm_pack.h): slot s of the unpacked array is lane s % 64 of position (s / 64) % 3 of step
+// s / 192; its place in the packed array follows from the step's four words.  WRITE = false only counts the slots
+// that would need a place the pack does not have (the caller then packs anew), so that nothing is written before
+// the update is known to fit.
+template <bool WRITE>
+__global__ __launch_bounds__(WG) void k_pack_set_values(const unsigned* __restrict__ map, const double* __restrict__ pv,
+                                                       const unsigned long long* __restrict__ meta,
+                                                       double* __restrict__ packed, size_t n, unsigned* __restrict__ misses) {
+  const size_t stride = (size_t)gridDim.x * WG;
+  unsigned miss = 0;
+  for (size_t s = (size_t)blockIdx.x * WG + threadIdx.x; s < n; s += stride) {
+    const unsigned e = map[s];
+    const double v = e ? pv[e - 1u] : 0.0;
+    const size_t g = s / 192;
+    const int p = (int)((s >> 6) % 3), lane = (int)(s & 63);
+    const unsigned long long* __restrict__ q = meta + 4 * g;
+    const unsigned long long mk = q[p];
+    if ((mk >> lane) & 1ull) {
+      if constexpr (WRITE) {
+        size_t at = (size_t)q[3] + 1 + __popcll(mk & ((1ull << lane) - 1ull));
+        if (p > 0) at += __popcll(q[0]);
+        if (p > 1) at += __popcll(q[1]);
+        packed[at] = v;
+      }
+    } else if (__double_as_longlong(v) != 0) ++miss;
+  }
+  if constexpr (!WRITE) { if (miss) atomicAdd(misses, miss); }
+}
+
 }  // namespace
+
+extern "C" int pa_k_pack_set_values(const unsigned* map, const double* pv, const unsigned long long* meta, double* packed,
+                                    size_t n, int write, unsigned* misses) {
+  if (n == 0) return 0;
+  const int cus = pa_rt_num_cus() > 0 ? pa_rt_num_cus() : 256;
+  size_t blocks = (n + WG - 1) / WG;
+  if (blocks > (size_t)8 * cus) blocks = (size_t)8 * cus;
+  if (write) PA_LAUNCH(k_pack_set_values<true>, dim3((unsigned)blocks), dim3(WG), 0, cur_stream(), map, pv, meta, packed, n, misses);
+  else PA_LAUNCH(k_pack_set_values<false>, dim3((unsigned)blocks), dim3(WG), 0, cur_stream(), map, pv, meta, packed, n, misses);
+  return kfail("k_pack_set_values");
+}
 
 extern "C" int pa_k_plan_set_values(const unsigned* map, const double* pv, double* val, size_t n) {
   if (n == 0) return 0;
