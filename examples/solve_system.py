@@ -1,9 +1,13 @@
 """Solve the caller's own system on the graded Poisson problem of tests/test_gpu_system_solve.py, both ways, and print
 both residuals:
-  python examples/solve_system.py [n [t [decades]]]      (defaults 10, 4, 2: S A0 S with S = diag(10^linspace(-2, 2, N)))
+  python examples/solve_system.py [--operator-precision single|double] [--refine] [n [t [decades]]]
+                                                         (defaults 10, 4, 2: S A0 S with S = diag(10^linspace(-2, 2, N)))
 The right-hand side, the guess and the solution are in the order and units of the matrix as it is assembled here; the
 permutation by parts and the row scaling of the solver stay inside the library (EcgProblem.solve_system).
-stop="scaled" is the library's own test, on the scaled system; stop="original" stops on ||b - A x|| <= tol ||b||."""
+stop="scaled" is the library's own test, on the scaled system; stop="original" stops on ||b - A x|| <= tol ||b||.
+--operator-precision single stores the matrix values of the SpMM in fp32 where the plan allows it (the packed run plan at
+up to 4 columns; "spmm_precision" in the output says what the plan in use reads); --refine solves in passes
+(solve_system(..., refine=True)), each started from the x before it with a residual formed on the fp64 matrix."""
 import json
 import os
 import sys
@@ -14,9 +18,16 @@ import scipy.sparse as sp
 import prealps_amd as pa
 from prealps_amd import gen
 
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 10
-t = int(sys.argv[2]) if len(sys.argv) > 2 else 4
-dec = float(sys.argv[3]) if len(sys.argv) > 3 else 2.0
+args = sys.argv[1:]
+refine = "--refine" in args
+precision = None
+if "--operator-precision" in args:
+    precision = args[args.index("--operator-precision") + 1]
+    del args[args.index("--operator-precision"):args.index("--operator-precision") + 2]
+args = [a for a in args if a != "--refine"]
+n = int(args[0]) if len(args) > 0 else 10
+t = int(args[1]) if len(args) > 1 else 4
+dec = float(args[2]) if len(args) > 2 else 2.0
 TOL = 1e-5
 rp, ci, v0 = gen.poisson3d_csr(n)
 v = gen.graded_values(rp, ci, v0, -dec, dec)
@@ -25,11 +36,16 @@ A = sp.csr_matrix((v, ci, rp), shape=(N, N))
 b = np.random.default_rng(20260407).standard_normal(N)
 prob = pa.EcgProblem(rp, ci, v, 8, None, scale=True, device=0)
 prob.create_block_jacobi()
+if precision is not None:
+    prob.set_operator_precision(precision)
+kw = dict(refine=True) if refine else {}
 out = dict(n=n, N=N, t=t, decades=2 * dec, tol=TOL, scaling_range=[float(prob.scaling.min()), float(prob.scaling.max())])
 for stop in ("scaled", "original"):
-    r = prob.solve_system(b, t, stop=stop, tol=TOL)
+    r = prob.solve_system(b, t, stop=stop, tol=TOL, **kw)
     fresh, normb = prob.system_residuals(b, r.x)
     out[stop] = dict(iters=r.iters,
+                     **(dict(passes=r.passes, pass_iters=[int(i) for i in r.pass_iters], refine_status=r.refine_status,
+                             pass_relative_residuals=(r.pass_res[:, 0] / r.sys_normb[0]).tolist()) if refine else {}),
                      # what the stopping test saw, in its own metric, and the recurrence residual in the caller's units
                      stopped_at=float(r.sys_res[0] / r.sys_normb[0]),
                      recurrence_relative_residual=float(r.sys_res_original[0] / normb[0]),
@@ -38,8 +54,9 @@ for stop in ("scaled", "original"):
                      host_relative_residual=float(np.linalg.norm(b - A @ r.x) / np.linalg.norm(b)))
 # a time step: go on from the last solution with a perturbed right-hand side
 b2 = b + 1e-3 * np.random.default_rng(1).standard_normal(N)
-warm = prob.solve_system(b2, t, x0=r.x, stop="original", tol=TOL)
-cold = prob.solve_system(b2, t, stop="original", tol=TOL)
+warm = prob.solve_system(b2, t, x0=r.x, stop="original", tol=TOL, **kw)
+cold = prob.solve_system(b2, t, stop="original", tol=TOL, **kw)
 out["next_step"] = dict(iters_from_the_last_solution=warm.iters, iters_from_zero=cold.iters)
+out["spmm_precision"] = int(prob.stat("spmm_precision"))
 prob.close()
 print(json.dumps(out))

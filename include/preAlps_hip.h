@@ -383,6 +383,39 @@ int preAlps_ECGSolveSystem(preAlps_ECG_t* ecg, int nrhs, const double* b, int ld
                            double* sys_res, int max_hist, int* n_hist);
 int preAlps_OperatorSystemResiduals(int nrhs, const double* b, int ldb, const double* x, int ldx,
                                     int flags, double* res, double* normb);
+/* preAlps_ECGSolveSystem in passes, each measured against the matrix as the caller gave it.  Pass 0 is
+ * preAlps_ECGSolveSystem with these arguments as it is.  Every later pass is the same solve started from the x of the
+ * pass before it; the product A x of that start always runs on the fp64 values of the matrix, whatever storage the
+ * iteration reads (preAlps_hip_set_operator_precision), so the start residual of pass p is a fresh b - A x of the
+ * given system.  A start under which every system meets its threshold comes back after no iteration, as a converged
+ * guess does from preAlps_ECGSolveSystem, and ends the chain.  With fp32 storage this is iterative refinement with
+ * an inner solver on the rounded matrix; with fp64 storage it is a restart with the residual replaced.
+ *   max_passes: 1 .. 16 passes may iterate.  ecg->maxIter bounds the iterations of all passes together: a pass gets
+ * what is left; ecg->iter holds their sum at the end.  pass_iters: max_passes ints, the iterations of every pass.
+ * pass_res: (max_passes + 1) x nrhs doubles, row p (pass_res[p * nrhs + j]) = the start residuals of pass p in the
+ * metric of the stopping test -- row 0 those of x0 (||b_j|| without a guess), row p >= 1 the fresh residuals of what
+ * pass p - 1 left.  *n_passes: the passes that iterated; row *n_passes holds the residuals that ended the chain.
+ * res_hist, bs_hist and sys_hist hold the histories of the passes one behind the other, *n_hist entries in all;
+ * sys_normb is that of pass 0.  sys_res: ||b_j - A x_j|| of the x handed back, in the caller's units -- where the
+ * chain ended at a start, fresh from the fp64 product, also when x is the iterate before the last pass (below).
+ * ecg->res and ecg->normb are the scaled Frobenius norms of the last start or iteration that ran, not those of x.
+ *   *status, the first that applies before a pass p >= 1 iterates, with q = max_j res_j / (tol ||b_j||):
+ * PREALPS_REFINE_CONVERGED (q <= 1), PREALPS_REFINE_OUT_OF_ITERATIONS (the passes so far have used ecg->maxIter),
+ * PREALPS_REFINE_STAGNATED (p >= 2 and pass p - 1 did not halve q), PREALPS_REFINE_OUT_OF_PASSES (p = max_passes).
+ * All four return 0.  With the three that are not CONVERGED x is the better of the iterates before and behind the
+ * last pass -- a pass that the budget cut short may not have recovered from its restart yet -- so its residuals are
+ * row *n_passes or row *n_passes - 1 of pass_res, whichever has the smaller ratio.  (ecg_refine.h states the rule.)
+ *   Refused: what preAlps_ECGSolveSystem refuses, max_passes outside 1 .. 16, nrhs > 16, a NULL among n_passes,
+ * pass_iters, pass_res and status.  One process, like the entry it wraps. */
+#define PREALPS_REFINE_CONVERGED         0
+#define PREALPS_REFINE_OUT_OF_PASSES     1
+#define PREALPS_REFINE_OUT_OF_ITERATIONS 2
+#define PREALPS_REFINE_STAGNATED         3
+int preAlps_ECGSolveSystemRefined(preAlps_ECG_t* ecg, int nrhs, const double* b, int ldb,
+                                  const double* x0, int ldx0, double* x, int ldx, int flags,
+                                  double* res_hist, int* bs_hist, double* sys_hist, double* sys_normb,
+                                  double* sys_res, int max_hist, int* n_hist, int max_passes, int* n_passes,
+                                  int* pass_iters, double* pass_res, int* status);
 /* 1 / 0: the two driver loops above and below replay each half of an iteration from a HIP graph
  * captured on its first passes (default: off, or PREALPS_ECG_GRAPH; plain launches measured faster). */
 void preAlps_hip_graphs(int on);
@@ -402,6 +435,26 @@ int preAlps_hip_set_nd_precision(int bits);
  * that the kernels for 9 to 16 columns and for wide bands read are not touched: those applies keep the fp64 bits.
  * Other values are refused; needs no GPU. */
 int preAlps_hip_set_band_precision(int bits);
+/* Storage of the matrix values that preAlps_BlockOperator streams: 64 = fp64; 32 = fp32 (every value rounded once,
+ * widened again exactly in the kernel, every operation in fp64 in the order of the fp64 kernel: a product has the
+ * bits of the fp64 product with the rounded matrix, which stays symmetric and keeps its zeros); 0 (default) = follow
+ * PREALPS_SPMM_PRECISION (`double`, the default, or `single`; any other value makes the next plan cut fail and is
+ * named there).  Other values are refused; needs no GPU and works in plan-only mode.
+ *   It takes effect at once: the library stream is drained and a plan that is on the device gets or drops its fp32
+ * copy inside the call.  fp32 reaches the packed run plan at a panel stride of at most 4 columns (k_spmm_runs_pack,
+ * k_spmm_runs_gram_pack; with 32 in force a run plan at such a stride is packed whatever that saves, unless
+ * PREALPS_SPMM_PACK=0, which wins).  Every other plan -- the window plan, the staged plan, the unpacked run plan, 8 and
+ * 16 columns -- keeps its fp64 values and its bits; the stat "spmm_precision" (64 / 32) tells which the plan in use
+ * reads.  The fp64 array stays on the device beside the copy and does not move ("spmm_val_address"); the copy is
+ * formed again after every plan cut, after preAlps_OperatorUpdateValues (in place when the update writes through;
+ * in a new allocation when it packs anew) -- stats "spmm_val32_bytes", "spmm_val32_address",
+ * "spmm_precision_stream_bytes" (what one product streams), "spmm_round_kernel_s".
+ *   A value that is finite in fp64 and not in fp32 is refused: the copy is freed, the call (or the product that cut
+ * the plan, or the update) fails and names the value; a scaled operator has |a'| <= 1 and cannot meet this.
+ *   The rounded matrix is another matrix: a solve converges to ITS solution, off by up to cond(A) 2^-24 relative.
+ * The product that forms the start residual of a guess (preAlps_ECGInitializeGuess, preAlps_ECGSolveSystem with x0,
+ * preAlps_OperatorSystemResiduals) therefore always reads the fp64 values; preAlps_ECGSolveSystemRefined builds on it. */
+int preAlps_hip_set_operator_precision(int bits);
 /* 1: the two driver loops run an Orthodir iteration of a solver described by the arguments with the block solve
  * before the update of X and R (one finish and one row pass per iteration; bitwise the same results), 0: in the
  * order of preAlps_ECGIterate.  PREALPS_ECG_SOLVE_FIRST=0 (read here as a solver reads it when it is reset) keeps
@@ -446,7 +499,8 @@ int preAlps_hip_panel_permute_solve(const CPLM_Mat_Dense_t* Z, CPLM_Mat_Dense_t*
  * precision; "bj_factor_bytes" does not count them), "bj_g4_last_ring" / "bj_g4_last_bits" /
  * "bj_g4_last_pipelined" (the last launch that read them: LDS ring depth, storage bits of the records, 1 = the
  * pipelined few-blocks chain), "ecg_graph_captures" / "ecg_graph_replays" (iteration segments captured and graphs
- * launched by the driver loops so far, preAlps_hip_graphs), ...  Returns non-zero for unknown keys. */
+ * launched by the driver loops so far, preAlps_hip_graphs), "spmm_precision" (64 / 32: storage of the values the
+ * plan in use streams, 0: no plan yet), ...  Returns non-zero for unknown keys. */
 int preAlps_hip_get_stat(const char* key, double* value);
 /* A stopwatch made of two hipEvents on the library stream: start records the
  * first, stop records the second, waits for it and returns the device time

@@ -2,9 +2,11 @@
  * ecg_loops.c -- the library's own driver loops around the RCI iteration of ecg.c: the graph segments, the
  * iteration with the block solve first, and preAlps_ECGSolve / SolveMulti / SolveGuess / SolveSystem / Advance.
  */
+#include <stdlib.h>
 #include <string.h>
 
 #include "ecg_priv.h"
+#include "ecg_refine.h"
 
 /* Z = M^-1 R for Orthomin, Z = M^-1 AP otherwise */
 static int apply_preconditioner(preAlps_ECG_t* ecg) {
@@ -21,11 +23,13 @@ static long long g_graph_captures, g_graph_replays;     /* segments captured / g
 long long pa_ecg_graph_count(int which) { return which ? g_graph_replays : g_graph_captures; }
 static int seg_begin(ecg_priv_t* pv, int seg) {
   if (!pv->use_graphs || pa_timing_enabled()) return 0;    /* (phase timers put events between the launches) */
-  if (pv->bj_epoch != pa_bj_apply_epoch()) {
-    /* the preconditioner was created again, or its coarse space set or cleared, since the capture: the graphs hold
-     * the old launches and pointers (the entry that changed them has drained the stream), so capture anew */
+  if (pv->bj_epoch != pa_bj_apply_epoch() || pv->op_epoch != pa_operator_plan_epoch()) {
+    /* the preconditioner was created again, or its coarse space set or cleared, since the capture -- or the SpMM plan
+     * was cut again, or gained or lost its fp32 copy (preAlps_hip_set_operator_precision): the graphs hold the old
+     * launches and pointers (the entry that changed them has drained the stream), so capture anew */
     for (int a = 0; a < 2; ++a) for (int b = 0; b < 6; ++b) { pa_rt_graph_free(pv->graph[a][b]); pv->graph[a][b] = NULL; pv->seen[a][b] = 0; }
     pv->bj_epoch = pa_bj_apply_epoch();
+    pv->op_epoch = pa_operator_plan_epoch();
   }
   if (pv->graph[seg][pv->phase]) { pa_rt_skip(1); return 2; }
   if (pv->seen[seg][pv->phase]++ == 0) return 0;
@@ -147,7 +151,7 @@ static void record_hist(preAlps_ECG_t* ecg, const multi_args_t* mu, double* res_
   if (mu->nrhs > 0 && mu->sys_hist) {
     ecg_priv_t* pv = priv_of(ecg);
     for (int j = 0; j < mu->nrhs; ++j)
-      mu->sys_hist[nh + (size_t)j * max_hist] = (pv && (pv->nrhs > 1 || pv->metric)) ? pv->sys_res[j] : ecg->res;
+      mu->sys_hist[nh + (size_t)j * (mu->sys_hist_ld ? mu->sys_hist_ld : max_hist)] = (pv && (pv->nrhs > 1 || pv->metric)) ? pv->sys_res[j] : ecg->res;
   }
 }
 /* The start's norms go where the caller asked for them; *live becomes 1 when a system is above its threshold. */
@@ -159,6 +163,8 @@ static int start_norms(preAlps_ECG_t* ecg, const multi_args_t* mu, int* live) {
     if (mu->sys_res0) mu->sys_res0[j] = g0[j];
     if (g0[j] > nb[j] * ecg->tol) *live = 1;
   }
+  /* (a refined solve decides here whether this pass runs at all) */
+  if (*live && mu->gate && mu->gate(mu->gate_ctx, mu->nrhs, g0, nb)) *live = 0;
   return 0;
 }
 /* The driver loop of examples/test_ecg_prealps_op.c:203-223 (fused:
@@ -297,21 +303,125 @@ int preAlps_ECGSolveGuess(preAlps_ECG_t* ecg, int nrhs, const double* rhs, int l
   return solve_in_own_loop(ecg, (double*)rhs, sol, res_hist, bs_hist, max_hist, n_hist, &mu);
 }
 /* preAlps_ECGSolveGuess around the gather and the scatter: A x = b as the caller stated it (one process: N = m). */
+/* the refusals of a system solve that its arguments alone decide; who: the entry they name */
+static int system_args_refused(const char* who, const preAlps_ECG_t* ecg, int nrhs, const double* b, int ldb,
+                               const double* x0, int ldx0, const double* x, int ldx, int flags) {
+  const pa_operator_info_t* op = pa_operator_info();
+  if (!op) return pa_fail_at(who, "the operator must be built before the solver");
+  if (!ecg || !b || !x) return pa_fail_at(who, " wrong test 'ecg != NULL && b != NULL && x != NULL'");
+  if (nrhs < 1) return pa_fail_at(who, "nrhs = %d: at least one right-hand side is needed", nrhs);
+  if (flags & ~(PREALPS_SYS_DEVICE | PREALPS_SYS_STOP_ORIGINAL)) return pa_fail_at(who, "flags = %d holds unknown bits", flags);
+  if (ldb < op->N) return pa_fail_at(who, "ldb = %d is smaller than the %d rows of the matrix", ldb, op->N);
+  if (x0 && ldx0 < op->N) return pa_fail_at(who, "ldx0 = %d is smaller than the %d rows of the matrix", ldx0, op->N);
+  if (ldx < op->N) return pa_fail_at(who, "ldx = %d is smaller than the %d rows of the matrix", ldx, op->N);
+  return 0;
+}
 int preAlps_ECGSolveSystem(preAlps_ECG_t* ecg, int nrhs, const double* b, int ldb, const double* x0, int ldx0, double* x,
                            int ldx, int flags, double* res_hist, int* bs_hist, double* sys_hist, double* sys_normb,
                            double* sys_res, int max_hist, int* n_hist) {
-  const pa_operator_info_t* op = pa_operator_info();
-  if (!op) return PA_FAIL("the operator must be built before the solver");
-  if (!ecg || !b || !x) return PA_FAIL(" wrong test 'ecg != NULL && b != NULL && x != NULL'");
-  if (nrhs < 1) return PA_FAIL("nrhs = %d: at least one right-hand side is needed", nrhs);
-  if (flags & ~(PREALPS_SYS_DEVICE | PREALPS_SYS_STOP_ORIGINAL)) return PA_FAIL("flags = %d holds unknown bits", flags);
-  if (ldb < op->N) return PA_FAIL("ldb = %d is smaller than the %d rows of the matrix", ldb, op->N);
-  if (x0 && ldx0 < op->N) return PA_FAIL("ldx0 = %d is smaller than the %d rows of the matrix", ldx0, op->N);
-  if (ldx < op->N) return PA_FAIL("ldx = %d is smaller than the %d rows of the matrix", ldx, op->N);
+  if (system_args_refused(__func__, ecg, nrhs, b, ldb, x0, ldx0, x, ldx, flags)) return 1;
   const sys_in_t in = {b, ldb, x0, ldx0, (flags & PREALPS_SYS_DEVICE) != 0, (flags & PREALPS_SYS_STOP_ORIGINAL) != 0, 0};
   const multi_args_t mu = {.nrhs = nrhs, .sys_hist = sys_hist, .sys_normb = sys_normb, .sys = &in, .sys_x = x, .sys_ldx = ldx,
                            .sys_res = sys_res};
   return solve_in_own_loop(ecg, NULL, NULL, res_hist, bs_hist, max_hist, n_hist, &mu);
+}
+
+/* ---- the refined system solve -----------------------------------------------------------------------------------
+ * Pass 0 is preAlps_ECGSolveSystem as it is.  Every later pass p is the same solve started from the x that pass p - 1
+ * left: its start forms R0 = b - A x with the fp64 values of the matrix (pa_operator_apply_exact), whatever storage
+ * the iteration reads, so what a pass converged to under a rounded operator is measured, and repaired, against the
+ * matrix the caller gave.  The start's norms are the verdict's input (ecg_refine.h): a start that meets every
+ * threshold comes back after no iteration, as any converged guess does, and ends the chain; the gate ends it for the
+ * other reasons.  The start of pass p reads a copy of x (two scratch arrays in turn, so that the iterate before the
+ * last pass is still there when that pass turns out to have made things worse). */
+typedef struct {
+  int pass, max_passes, iters_used, max_iter, verdict, keep_prev;
+  double tol, q_prev;      /* q_prev: the ratio the pass before this one started from */
+} refine_gate_t;
+static int refine_gate(void* ctx, int nrhs, const double* g0, const double* nb) {
+  refine_gate_t* g = (refine_gate_t*)ctx;
+  double thr[16];
+  for (int j = 0; j < nrhs; ++j) thr[j] = nb[j] * g->tol;
+  const double q = pa_refine_ratio(nrhs, g0, thr);
+  g->verdict = pa_refine_verdict(q, g->q_prev, g->pass, g->max_passes, g->iters_used, g->max_iter, &g->keep_prev);
+  /* (q <= 1 here, with a system a rounding above its threshold in the solver's own comparison, counts as converged) */
+  if (g->verdict == PA_REFINE_CONTINUE) g->q_prev = q;
+  return g->verdict != PA_REFINE_CONTINUE;
+}
+/* dst(:, j) = src(:, j) for the k columns of n rows, both on the device or both on the host */
+static int copy_columns(int device, int n, int k, double* dst, int ldd, const double* src, int lds) {
+  for (int j = 0; j < k; ++j) {
+    if (!device) memcpy(dst + (size_t)j * ldd, src + (size_t)j * lds, (size_t)n * sizeof(double));
+    else if (pa_rt_d2d(dst + (size_t)j * ldd, src + (size_t)j * lds, (size_t)n * sizeof(double))) return 1;
+  }
+  return device ? pa_rt_sync() : 0;
+}
+int preAlps_ECGSolveSystemRefined(preAlps_ECG_t* ecg, int nrhs, const double* b, int ldb, const double* x0, int ldx0,
+                                  double* x, int ldx, int flags, double* res_hist, int* bs_hist, double* sys_hist,
+                                  double* sys_normb, double* sys_res, int max_hist, int* n_hist, int max_passes,
+                                  int* n_passes, int* pass_iters, double* pass_res, int* status) {
+  if (system_args_refused(__func__, ecg, nrhs, b, ldb, x0, ldx0, x, ldx, flags)) return 1;
+  if (!pa_refine_passes_ok(max_passes))
+    return PA_FAIL("max_passes = %d: between 1 and %d passes", max_passes, PA_REFINE_MAX_PASSES);
+  if (nrhs > 16) return PA_FAIL("nrhs = %d: at most 16 systems at a time (what the per-system arrays of a solver hold)", nrhs);
+  if (!n_passes || !pass_iters || !pass_res || !status)
+    return PA_FAIL(" wrong test 'n_passes != NULL && pass_iters != NULL && pass_res != NULL && status != NULL'");
+  const pa_operator_info_t* op = pa_operator_info();
+  const int device = (flags & PREALPS_SYS_DEVICE) != 0, N = op->N, k = nrhs;
+  const int max_iter = ecg->maxIter;
+  const size_t cols = (size_t)(N > 0 ? N : 1) * k;
+  double* xs[2] = {NULL, NULL};      /* the start of pass p: xs[p & 1] */
+  refine_gate_t g = {.max_passes = max_passes, .max_iter = max_iter, .tol = ecg->tol};
+  int nh_tot = 0, used = 0, rc = 0, p;
+  double nb[16], res_end[16];
+  for (int i = 0; i < (max_passes + 1) * k; ++i) pass_res[i] = 0.0;
+  for (int i = 0; i < max_passes; ++i) pass_iters[i] = 0;
+  *status = PA_REFINE_CONVERGED;
+  for (p = 0; !rc; ++p) {      /* (left at p <= max_passes: the gate lets no pass beyond the last one run) */
+    const double* start = x0;
+    multi_args_t mu = {.nrhs = k, .sys_hist = sys_hist ? sys_hist + nh_tot : NULL, .sys_normb = nb, .sys_x = x, .sys_ldx = ldx,
+                       .sys_res = res_end, .sys_res0 = pass_res + (size_t)p * k, .sys_hist_ld = max_hist};
+    if (p > 0) {
+      double** slot = &xs[p & 1];
+      if (!*slot) *slot = (double*)(device ? pa_rt_malloc(cols * sizeof(double)) : malloc(cols * sizeof(double)));
+      if (!*slot) { rc = PA_FAIL("no memory for the start of pass %d (%zu values)", p, cols); break; }
+      if (copy_columns(device, N, k, *slot, N, x, ldx)) { rc = PA_FAIL("%s", pa_rt_error()); break; }
+      start = *slot;
+      g.pass = p; g.iters_used = used; g.verdict = PA_REFINE_CONVERGED;      /* (what stands when the gate is not asked) */
+      mu.gate = refine_gate; mu.gate_ctx = &g;
+    }
+    const sys_in_t in = {b, ldb, start, p > 0 ? N : ldx0, device, (flags & PREALPS_SYS_STOP_ORIGINAL) != 0, 0};
+    mu.sys = &in;
+    int nh = 0;
+    ecg->maxIter = max_iter - used;      /* a pass gets what is left (> 0 wherever a pass runs) */
+    rc = solve_in_own_loop(ecg, NULL, NULL, res_hist ? res_hist + nh_tot : NULL, bs_hist ? bs_hist + nh_tot : NULL,
+                           max_hist > nh_tot ? max_hist - nh_tot : 0, &nh, &mu);
+    if (rc) break;
+    if (p == 0 && sys_normb) for (int j = 0; j < k; ++j) sys_normb[j] = nb[j];
+    if (sys_res) for (int j = 0; j < k; ++j) sys_res[j] = res_end[j];
+    if (p > 0 && g.verdict != PA_REFINE_CONTINUE) {      /* the start ended the chain: x holds its own start again */
+      *status = g.verdict;
+      if (g.keep_prev) {      /* the better of the two iterates: the start of pass p - 1, and ITS residuals in sys_res */
+        if (copy_columns(device, N, k, x, ldx, xs[(p - 1) & 1], N)) rc = PA_FAIL("%s", pa_rt_error());
+        else if (sys_res && (flags & PREALPS_SYS_STOP_ORIGINAL))      /* (row p - 1: already in the caller's units) */
+          for (int j = 0; j < k; ++j) sys_res[j] = pass_res[(size_t)(p - 1) * k + j];
+        else if (sys_res) rc = preAlps_OperatorSystemResiduals(k, b, ldb, x, ldx, flags & PREALPS_SYS_DEVICE, sys_res, NULL);
+      }
+      break;
+    }
+    pass_iters[p] = ecg->iter;
+    used += ecg->iter;
+    nh_tot += nh;
+  }
+  ecg->maxIter = max_iter;
+  if (!rc) {
+    *n_passes = p;
+    ecg->iter = used;
+    if (n_hist) *n_hist = nh_tot;
+  }
+  if (device) { pa_rt_free(xs[0]); pa_rt_free(xs[1]); }
+  else { free(xs[0]); free(xs[1]); }
+  return rc;
 }
 
 /* The tail of a restart in preAlps_ECGAdvance: count it, keep what the finished solve reached, start again from the

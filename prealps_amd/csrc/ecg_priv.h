@@ -83,6 +83,7 @@ typedef struct {
   void* graph[2][6];
   unsigned char seen[2][6];
   int bj_epoch;       /* pa_bj_apply_epoch() the graphs were captured under */
+  int op_epoch;       /* pa_operator_plan_epoch() likewise */
   /* Several right-hand sides (preAlps_ECGInitializeMulti): nrhs systems of sgrp = enlFac / nrhs columns each, system
    * j in the columns j*sgrp .. j*sgrp + sgrp - 1.  nrhs <= 1: one system, nothing below is used.  Every launch that
    * leaves the column sums of R^2 in d_rtr_part is followed by pa_k_group_norms (pa_ecg_queue_group_norms), which leaves
@@ -136,6 +137,12 @@ typedef struct {      /* what preAlps_ECGSolveMulti adds to the arguments of pre
   /* ... and preAlps_ECGSolveSystem: the caller's arrays (sys->b, sys->x0: the rows in the caller's order and units), the
    * solution and the final norms in the caller's units; sys = NULL: one of the others */
   const sys_in_t* sys; double* sys_x; int sys_ldx; double* sys_res;
+  /* ... and preAlps_ECGSolveSystemRefined: gate (NULL: none) is asked once the start's norms are known and a system is
+   * above its threshold -- g0[j], nb[j]: the start residual and ||b_j|| of system j in the metric of the test --
+   * and a nonzero answer ends the solve there as a converged guess ends it: x0 comes back as x, after no iteration.
+   * sys_hist_ld: the leading dimension of sys_hist where it is not max_hist (0: it is). */
+  int (*gate)(void* ctx, int nrhs, const double* g0, const double* nb); void* gate_ctx;
+  int sys_hist_ld;
 } multi_args_t;
 
 /* ---- ecg.c ---- */

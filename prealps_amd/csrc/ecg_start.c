@@ -153,8 +153,10 @@ static int start_from_guess(const start_t* c, staging_t* st, int rc) {
     if (!rc) FAIL_AS(c->who, "another process of the group could not stage its rows (its own message says why)");
     return START_QUIT;
   }
-  /* a plain product: nothing is armed for X -> Z, and pa_ecg_reset_done has not asked the SpMM for a block yet */
-  if (!rc) rc = preAlps_BlockOperator(c->ecg->X, c->ecg->Z);
+  /* a plain product: nothing is armed for X -> Z, and pa_ecg_reset_done has not asked the SpMM for a block yet; on
+   * the fp64 values whatever the iteration reads (preAlps_hip_set_operator_precision): R0 belongs to the matrix the
+   * caller gave, which is what lets a second solve from x repair the first one's rounded operator */
+  if (!rc) rc = pa_operator_apply_exact(c->ecg->X, c->ecg->Z);
   if (!rc) {
     const size_t panel = c->mm * pv->ts;
     rc = pa_k_guess_start(m, pv->ts, k, s, st->d_B, m, st->d_pcol, pv->buf_z, pv->d_R, pv->d_partials, pv->d_rtr_part, &nblk) ||

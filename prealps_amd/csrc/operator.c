@@ -70,6 +70,11 @@ typedef struct {
   size_t pk_nval;
   double pk_stream_bytes;   /* bytes of matrix data one product streams from the packed plan */
   int repacks;              /* updates of the values that had to pack anew */
+  /* the fp32 copy of the packed array (preAlps_hip_set_operator_precision(32)): pk_nalloc floats -- every element of
+   * plan.val, the steps' zeros and the slack included -- at plan.val32; plan.val stays where it is */
+  size_t pk_nalloc;         /* elements of the packed array as allocated */
+  int plan_pack_sw;         /* PREALPS_SPMM_PACK as the current plan was cut under */
+  int val32_owed;           /* the copy was refused after new values while 32 stays in force: the next product forms it or fails */
   unsigned* d_vmap;    /* device: stored value -> panel entry + 1, 0 = padding (plan_val_n entries; NULL: not cut yet) */
   int values_epoch;    /* 0 after a build, + 1 per update */
   int vmap_builds;     /* value maps cut for this operator */
@@ -81,6 +86,9 @@ typedef struct {
 } pa_operator_t;
 
 static pa_operator_t g_op;
+/* + 1 per change of what a product launches or reads (pa_operator_plan_epoch); never reset, so that a solver kept across
+ * a free and a rebuild of the operator cannot meet the count it last saw */
+static int g_plan_epoch;
 static int g_op_builds;   /* operators built so far (pa_operator_build_count) */
 static double g_setup_build_s, g_setup_plan_s;   /* host seconds: scale/permute/halo lists, SpMM plan */
 
@@ -99,7 +107,10 @@ static void free_plan(pa_operator_t* o) {
   for (int i = 0; i < PA_PL_COUNT; ++i) { pa_rt_free(o->d_plan[i]); o->d_plan[i] = NULL; }
   o->plan_ts = 0;
   pa_rt_free((void*)o->plan.pk_meta);
+  pa_rt_free((void*)o->plan.val32);
   memset(&o->plan, 0, sizeof(o->plan));
+  o->pk_nalloc = 0; o->val32_owed = 0;
+  ++g_plan_epoch;
   pa_rt_free(o->d_vmap); o->d_vmap = NULL;   /* the value map belongs to the plan */
   o->plan_val_n = 0;
   o->pk_nval = 0; o->pk_stream_bytes = 0.0;
@@ -150,7 +161,7 @@ static int upload_plan(pa_operator_t* o, const pa_spmm_host_plan_t* hp, const pa
     void* d_meta = NULL;
     if (upload_pack(pk, &o->d_plan[PA_PL_VAL], &d_meta)) return 1;
     pl->packed = 1; pl->pk_meta = (const unsigned long long*)d_meta;
-    o->pk_nval = pk->nval;
+    o->pk_nval = pk->nval; o->pk_nalloc = pk->nval_alloc;
     o->pk_stream_bytes = hp->stream_bytes - pk->unpacked_bytes + pk->packed_bytes;
   }
   pl->m = hp->m; pl->nslices = hp->nslices; pl->nblk = hp->nblk; pl->n_interior = hp->n_interior;
@@ -182,8 +193,62 @@ static pa_spmm_plan_in_t plan_input(const pa_operator_t* o, int ts) {
   return pin;
 }
 
+/* ---- storage of the matrix values (preAlps_hip_set_operator_precision) ----
+ * 64 / 32 bits; 0 = follow PREALPS_SPMM_PRECISION (double, the default, or single).  fp32 reaches the packed run plan
+ * at a panel stride of at most 4 columns and nothing else: every other plan keeps its fp64 values and its bits. */
+static int g_op_bits = 0;
+static double g_round_kernel_s;      /* device seconds of the last k_plan_round_values */
+/* the storage in force: 64 or 32; -1 (reported): the variable holds something else */
+static int operator_bits(void) {
+  if (g_op_bits) return g_op_bits;
+  const char* pe = getenv("PREALPS_SPMM_PRECISION");
+  if (!pe || !*pe || !strcmp(pe, "double")) return 64;
+  if (!strcmp(pe, "single")) return 32;
+  PA_FAIL("PREALPS_SPMM_PRECISION=%s: expected double or single (storage of the matrix values of the SpMM)", pe);
+  return -1;
+}
+static void drop_val32(pa_operator_t* o) {
+  if (!o->plan.val32) return;
+  pa_rt_free((void*)o->plan.val32);
+  o->plan.val32 = NULL;
+  ++g_plan_epoch;
+}
+/* The fp32 copy of the packed array as it stands (k_plan_round_values), into the allocation that is there or a new
+ * one of pk_nalloc floats.  A value that fp32 cannot hold frees the copy and is reported. */
+static int form_val32(pa_operator_t* o) {
+  float* d32 = (float*)o->plan.val32;
+  const int fresh = d32 == NULL;
+  unsigned long long bad[2] = {0, 0};
+  unsigned long long* d_bad = (unsigned long long*)pa_rt_malloc(sizeof(bad));
+  if (fresh) d32 = (float*)pa_rt_malloc((o->pk_nalloc ? o->pk_nalloc : 1) * sizeof(float));
+  void* e0 = pa_rt_event_create();
+  void* e1 = pa_rt_event_create();
+  int rc = !d_bad || !d32 || !e0 || !e1 || pa_rt_memset(d_bad, 0, sizeof(bad)) || pa_rt_event_record(e0) ||
+           pa_k_plan_round_values(o->plan.val, d32, o->pk_nalloc, d_bad) || pa_rt_event_record(e1) ||
+           pa_rt_d2h(bad, d_bad, sizeof(bad)) || pa_rt_sync();
+  if (!rc) g_round_kernel_s = pa_rt_event_elapsed_s(e0, e1);
+  pa_rt_event_destroy(e0); pa_rt_event_destroy(e1);
+  pa_rt_free(d_bad);
+  if (rc || bad[0]) {
+    pa_rt_free(d32);
+    o->plan.val32 = NULL;
+    o->val32_owed = 1;
+    ++g_plan_epoch;
+    if (rc) return PA_FAIL("the single-precision copy of the matrix values: %s", pa_rt_error());
+    double v;
+    memcpy(&v, &bad[1], sizeof(v));
+    return PA_FAIL("single precision cannot hold %llu of the matrix values (one of them: %.17g); the operator keeps "
+                   "double (scale the operator, or preAlps_hip_set_operator_precision(64))", bad[0], v);
+  }
+  if (fresh) { o->plan.val32 = d32; ++g_plan_epoch; }
+  o->val32_owed = 0;
+  return 0;
+}
+
 /* The switches are read at every build: tests and probes change them between builds in one process. */
 static int build_plan(pa_operator_t* o, int ts) {
+  const int bits = operator_bits();
+  if (bits < 0) return 1;
   free_plan(o);
   o->plan_cus = pa_rt_num_cus();
   o->plan_staged_sw = env_int("PREALPS_SPMM_STAGED", -1);
@@ -199,11 +264,13 @@ static int build_plan(pa_operator_t* o, int ts) {
   pa_spmm_pack_t pk;
   int packed = 0;
   const int pack_sw = env_int("PREALPS_SPMM_PACK", -1);
+  o->plan_pack_sw = pack_sw;
+  /* (fp32 storage lives behind the masks of the pack: with 32 in force such a plan is packed whatever it saves) */
   if (hp.runs && hp.runs_cols == ts && ts <= 4 && pack_sw != 0) {
     int prc = pa_spmm_pack_build((const double*)hp.a[PA_PL_VAL].p, (const long long*)hp.a[PA_PL_SL_OFF].p,
                                  (const int*)hp.a[PA_PL_SL_LEN].p, hp.nslices, 0, &pk);
     if (prc == -1) { pa_spmm_plan_free(&hp); return PA_FAIL("out of host memory for the packed values of the SpMM plan"); }
-    packed = prc == 0 && (pack_sw > 0 || hp.stream_bytes - pk.unpacked_bytes + pk.packed_bytes < 0.9 * hp.stream_bytes);
+    packed = prc == 0 && (pack_sw > 0 || bits == 32 || hp.stream_bytes - pk.unpacked_bytes + pk.packed_bytes < 0.9 * hp.stream_bytes);
     if (prc == 0 && !packed) pa_spmm_pack_free(&pk);
   }
   int rc = upload_plan(o, &hp, packed ? &pk : NULL);
@@ -211,6 +278,7 @@ static int build_plan(pa_operator_t* o, int ts) {
   pa_spmm_plan_free(&hp);
   if (rc) return PA_FAIL("uploading the SpMM plan failed: %s", pa_rt_error());
   o->plan_ts = ts;
+  if (packed && bits == 32 && form_val32(o)) { free_plan(o); return 1; }
   return 0;
 }
 
@@ -717,11 +785,40 @@ int pa_operator_pack_hint(int ts, const double* X, const int** pk_off, const int
 int preAlps_hip_prepare_operator(int enlFac) {
   pa_operator_t* o = &g_op;
   if (!o->info.built) return PA_FAIL("operator not built");
+  if (operator_bits() < 0) return 1;      /* (what the cut itself would refuse, without a GPU as well) */
   if (g_plan_only) return 0;
   int ts = pa_panel_stride(enlFac);
   double t0 = pa_wtime();
   if (o->plan_ts != ts && build_plan(o, ts)) return 1;
   g_setup_plan_s = pa_wtime() - t0;
+  return 0;
+}
+
+int pa_operator_plan_epoch(void) { return g_plan_epoch; }
+
+/* Storage of the matrix values the products read: 64, 32, or 0 = follow PREALPS_SPMM_PRECISION.  Needs no GPU.  A plan
+ * that is on the device follows at once, behind the work already queued: a packed run plan at up to 4 columns gets
+ * its fp32 copy or drops it (its fp64 array stays where it is); an unpacked run plan at such a stride is cut again,
+ * packed, when 32 comes into force; every other plan is left alone.  A refusal leaves the setting as it was, and the
+ * plan too -- but for an unpacked run plan whose new cut failed: that plan is gone, and the next product cuts it again
+ * under the old setting. */
+int preAlps_hip_set_operator_precision(int bits) {
+  pa_operator_t* o = &g_op;
+  if (bits != 0 && bits != 32 && bits != 64)
+    return PA_FAIL("precision %d refused: 64 (double), 32 (single) or 0 (follow PREALPS_SPMM_PRECISION)", bits);
+  const int before = g_op_bits;
+  g_op_bits = bits;
+  if (!o->info.built || g_plan_only || o->plan_ts == 0) return 0;
+  const char* pe = getenv("PREALPS_SPMM_PRECISION");
+  if (!bits && pe && *pe && strcmp(pe, "double") && strcmp(pe, "single")) return 0;   /* (the next plan cut names it) */
+  const int want = operator_bits();
+  const pa_spmm_plan_t* pl = &o->plan;
+  if (want != 32) o->val32_owed = 0;      /* (a copy that an update could not form is no longer wanted) */
+  if ((want == 32) == (pl->val32 != NULL)) return 0;
+  if (pa_rt_sync()) { g_op_bits = before; return PA_FAIL("%s", pa_rt_error()); }   /* products in flight read the plan */
+  if (want == 64) { drop_val32(o); return 0; }
+  if (!pl->runs || pl->runs_cols != o->plan_ts || o->plan_ts > 4 || o->plan_pack_sw == 0) return 0;
+  if (pl->packed ? form_val32(o) : build_plan(o, o->plan_ts)) { g_op_bits = before; o->val32_owed = 0; return 1; }
   return 0;
 }
 
@@ -783,6 +880,12 @@ static int repack_plan(pa_operator_t* o) {
     o->pk_stream_bytes = hp.stream_bytes - pk.unpacked_bytes + pk.packed_bytes;
     g_dbg_val_bytes = pk.nval_alloc * sizeof(double);
     ++o->repacks;
+    ++g_plan_epoch;
+    /* the fp32 copy follows the new array: another length, so another allocation */
+    const int had32 = o->plan.val32 != NULL;
+    drop_val32(o);
+    o->pk_nalloc = pk.nval_alloc;
+    if (had32) rc = form_val32(o);
   }
   pa_spmm_pack_free(&pk);
   pa_spmm_plan_free(&hp);
@@ -857,6 +960,12 @@ int preAlps_OperatorUpdateValues(const double* val) {
     rc = rc || pa_k_pack_set_values(o->d_vmap, d_pv, o->plan.pk_meta, (double*)o->plan.val, o->plan_val_n, 1, d_miss) ||
          pa_rt_event_record(e1) || pa_rt_sync();
     pa_rt_free(d_miss);
+    /* the fp32 copy is rounded again from the array just written, in place */
+    if (!rc && o->plan.val32 && form_val32(o)) {
+      pa_rt_event_destroy(e0); pa_rt_event_destroy(e1);
+      pa_rt_free(d_pv);
+      return 1;
+    }
   } else {
     rc = rc || !e0 || !e1 || pa_rt_event_record(e0) ||
          pa_k_plan_set_values(o->d_vmap, d_pv, (double*)o->plan.val, o->plan_val_n) || pa_rt_event_record(e1) || pa_rt_sync();
@@ -902,8 +1011,9 @@ int pa_operator_gram_blocks(int ts) {
   return o->plan.nblk;
 }
 
-/* AX = A X for the X->info.n current columns (operator.c:334-351). */
-int preAlps_BlockOperator(CPLM_Mat_Dense_t* X, CPLM_Mat_Dense_t* AX) {
+/* AX = A X for the X->info.n current columns (operator.c:334-351).  exact: on the fp64 values whatever the storage in
+ * force, and outside every Gram request (pa_operator_apply_exact). */
+static int block_operator(CPLM_Mat_Dense_t* X, CPLM_Mat_Dense_t* AX, int exact) {
   pa_operator_t* o = &g_op;
   if (!o->info.built) return PA_FAIL("operator not built");
   if (g_plan_only) return PA_FAIL("the operator was built in plan-only mode (no GPU)");
@@ -913,6 +1023,10 @@ int preAlps_BlockOperator(CPLM_Mat_Dense_t* X, CPLM_Mat_Dense_t* AX) {
     return PA_FAIL("panel shapes do not match the operator (m %d vs %d, stride %d vs %d)", X->info.m,
                    o->info.m, ts, pa_desc_stride(AX));
   if (o->plan_ts != ts && build_plan(o, ts)) return 1;
+  if (o->val32_owed && !exact) {      /* an update could not round its values: with 32 still in force, again or fail */
+    if (operator_bits() != 32) o->val32_owed = 0;
+    else if (form_val32(o)) return 1;
+  }
   pa_time_begin(PA_T_OPERATOR);
   if (pa_world_size() > 1 && o->npeers > 0) {
     int rc = ensure_halo_buffers(o, ts);
@@ -934,7 +1048,7 @@ int preAlps_BlockOperator(CPLM_Mat_Dense_t* X, CPLM_Mat_Dense_t* AX) {
       if (!packed) PA_CHECK(pa_k_pack_rows(o->nsend, ts, o->d_send_idx, X->val, o->d_sendbuf));
       rc = pa_exchange(o->d_sendbuf, o->send_cnt, o->d_halo, o->recv_cnt, o->peers, o->npeers);
       if (rc) return rc;
-      PA_CHECK(pa_k_spmm(&o->plan, ts, X->val, o->d_halo, AX->val, 2));
+      PA_CHECK(pa_k_spmm(&o->plan, ts, X->val, o->d_halo, AX->val, 2, exact));
       pa_time_end(PA_T_OPERATOR);
       return 0;
     }
@@ -953,15 +1067,19 @@ int preAlps_BlockOperator(CPLM_Mat_Dense_t* X, CPLM_Mat_Dense_t* AX) {
     pa_rt_set_stream(main_stream);
     if (rc) return rc;
     if (rc2) return PA_FAIL("%s", pa_rt_error());
-    PA_CHECK(pa_k_spmm(&o->plan, ts, X->val, o->d_halo, AX->val, 0));
+    PA_CHECK(pa_k_spmm(&o->plan, ts, X->val, o->d_halo, AX->val, 0, exact));
     PA_CHECK(pa_rt_stream_wait_event(main_stream, o->ev_halo));
-    PA_CHECK(pa_k_spmm(&o->plan, ts, X->val, o->d_halo, AX->val, 1));
+    PA_CHECK(pa_k_spmm(&o->plan, ts, X->val, o->d_halo, AX->val, 1, exact));
   } else {
-    PA_CHECK(pa_k_spmm(&o->plan, ts, X->val, NULL, AX->val, 2));
+    PA_CHECK(pa_k_spmm(&o->plan, ts, X->val, NULL, AX->val, 2, exact));
   }
   pa_time_end(PA_T_OPERATOR);
   return 0;
 }
+
+int preAlps_BlockOperator(CPLM_Mat_Dense_t* X, CPLM_Mat_Dense_t* AX) { return block_operator(X, AX, 0); }
+/* The product of a start from a guess (ecg_start.c): R0 = b - A x0 is formed with the matrix as the caller gave it. */
+int pa_operator_apply_exact(CPLM_Mat_Dense_t* X, CPLM_Mat_Dense_t* AX) { return block_operator(X, AX, 1); }
 
 int preAlps_hip_get_stat(const char* key, double* value) {
   const pa_operator_t* o = &g_op;
@@ -983,6 +1101,13 @@ int preAlps_hip_get_stat(const char* key, double* value) {
   else if (!strcmp(key, "spmm_packed_values")) *value = (double)o->pk_nval;
   else if (!strcmp(key, "spmm_packed_stream_bytes")) *value = o->pk_stream_bytes;
   else if (!strcmp(key, "spmm_repacks")) *value = o->repacks;
+  else if (!strcmp(key, "spmm_precision")) *value = o->plan_ts ? (o->plan.val32 ? 32 : 64) : 0;      /* storage the products of the plan in use read */
+  else if (!strcmp(key, "spmm_val32_bytes")) *value = o->plan.val32 ? 4.0 * (double)o->pk_nalloc : 0.0;
+  else if (!strcmp(key, "spmm_val32_address")) *value = (double)(uintptr_t)o->plan.val32;
+  else if (!strcmp(key, "spmm_precision_stream_bytes"))      /* what one product streams: 4 bytes less per packed value and step zero */
+    *value = !o->plan_ts ? 0.0 : o->plan.val32 ? o->pk_stream_bytes - 4.0 * (double)(o->pk_nalloc - PA_SPMM_PACK_SLACK)
+                                               : o->plan.packed ? o->pk_stream_bytes : o->stream_bytes;
+  else if (!strcmp(key, "spmm_round_kernel_s")) *value = g_round_kernel_s;
   else if (!strcmp(key, "spmm_val_address")) *value = (double)(uintptr_t)o->plan.val;      /* (for the run-to-run spread study) */
   else if (!strcmp(key, "spmm_slot_address")) *value = (double)(uintptr_t)o->plan.col16;
   else if (!strcmp(key, "spmm_staged")) *value = o->plan.staged;

@@ -105,10 +105,14 @@ typedef struct {
    * sl_off / sl_len still count runs */
   int packed;
   const unsigned long long* pk_meta;
+  /* non-NULL (packed run plan at up to 4 columns, preAlps_hip_set_operator_precision(32)): `val` rounded to fp32,
+   * element for element (pa_k_plan_round_values), read through the same pk_meta in place of `val`; `val` stays */
+  const float* val32;
 } pa_spmm_plan_t;
-/* phase 0: interior blocks, 1: halo-reading blocks, 2: all */
+/* phase 0: interior blocks, 1: halo-reading blocks, 2: all.  exact != 0: read `val` even where val32 is set, and
+ * leave every Gram request (pa_k_spmm_gram_arm) as it is. */
 int pa_k_spmm(const pa_spmm_plan_t* pl, int ts, const double* X, const double* Xhalo,
-              double* Y, int phase);
+              double* Y, int phase, int exact);
 /* Ask the next product X -> Y of pa_k_spmm (4-column panels, run plan) to leave the partial
  * blocks of [Y | R]^T X (8 x 4 each, the layout of pa_k_gram with two panels) in `partials`
  * (room for cap blocks); pa_k_spmm_gram_take returns how many there are (0: the product ran
@@ -143,6 +147,10 @@ int pa_k_plan_set_values(const unsigned* map, const double* pv, double* val, siz
  * it and writes nothing; write = 1 stores the new value of every slot that has a place in `packed`. */
 int pa_k_pack_set_values(const unsigned* map, const double* pv, const unsigned long long* meta, double* packed,
                          size_t n, int write, unsigned* misses);
+/* val32[i] = (float)val[i], i < n (spmm_values.hip: k_plan_round_values).  bad (device, two 8-byte words, zeroed by
+ * the caller): bad[0] counts, as an integer, the values that are finite in fp64 and not in fp32; bad[1] receives the
+ * bits of one of them. */
+int pa_k_plan_round_values(const double* val, float* val32, size_t n, unsigned long long* bad);
 /* sendbuf[i*ts + c] = X[idx[i]*ts + c] */
 int pa_k_pack_rows(int n, int ts, const int* idx, const double* X, double* sendbuf);
 

@@ -88,6 +88,10 @@ int pa_operator_pack_hint(int ts, const double* X, const int** pk_off, const int
 /* The row map of the system solve on the device (one process: N = m rows): src[i] = perm[row_off + i], dl[i] =
  * scaling[src[i]] (1.0 when unscaled); cut lazily, again after preAlps_OperatorUpdateValues; library-owned. */
 int pa_operator_system_map(const int** src, const double** dl);
+/* The product of preAlps_BlockOperator on the fp64 values of the matrix whatever storage is in force
+ * (preAlps_hip_set_operator_precision): what forms R0 = b - A x0.  It neither serves nor ends a Gram request. */
+int pa_operator_apply_exact(CPLM_Mat_Dense_t* X, CPLM_Mat_Dense_t* AX);
+int pa_operator_plan_epoch(void);     /* + 1 per change of what a product launches or reads (plan cut, repack, fp32 copy) */
 int pa_operator_values_epoch(void);   /* 0 after a build, + 1 per preAlps_OperatorUpdateValues */
 int pa_bj_values_epoch(void);         /* that count at the last preAlps_BlockJacobiCreate / preAlps_BlockJacobiUpdateValues */
 int pa_operator_plan_only(void);     /* 1: preAlps_hip_plan_only is on (host side only, no GPU) */

@@ -212,15 +212,17 @@ __device__ __forceinline__ void spmm_runs_load(const unsigned short* __restrict_
 // area would cost the fifth workgroup per CU, and there the kernel is bound by HBM.
 template <int TS> struct spmm_row { static constexpr int stride = TS == 8 ? TS + 2 : TS; };
 
-template <int TS, int RL>
+// VT: the type the values are held in (float: the fp32 copy of the packed array, widened here -- exactly -- right in
+// front of the FMAs)
+template <int TS, int RL, typename VT = double>
 __device__ __forceinline__ void spmm_runs_fma(const double* sx, const int (&sl)[spmm_ru<RL>::n],
-                                              const double (&vv)[RL * spmm_ru<RL>::n], double (&acc)[TS]) {
+                                              const VT (&vv)[RL * spmm_ru<RL>::n], double (&acc)[TS]) {
   constexpr int TSP = spmm_row<TS>::stride;
 #pragma unroll
   for (int j = 0; j < spmm_ru<RL>::n; ++j) {
     const double* __restrict__ xr = sx + (size_t)sl[j] * TSP;
 #pragma unroll
-    for (int i = 0; i < RL; ++i) spmm_fma_row<TS>(acc, vv[RL * j + i], xr + i * TSP);
+    for (int i = 0; i < RL; ++i) spmm_fma_row<TS>(acc, (double)vv[RL * j + i], xr + i * TSP);
   }
 }
 
@@ -247,33 +249,37 @@ __device__ __forceinline__ void spmm_pack_meta(const pk_u64* __restrict__ mp, in
     M.base[j] = w3;
   }
 }
-__device__ __forceinline__ void spmm_runs_load_pack(const unsigned short* __restrict__ cp, const double* __restrict__ vpk,
+// VT = float: the fp32 copy of the packed array (k_plan_round_values) behind the same masks and offsets -- element
+// indices, so the lane's byte offset is << 2 and the fetch a 4-byte load.
+template <typename VT>
+__device__ __forceinline__ void spmm_runs_load_pack(const unsigned short* __restrict__ cp, const VT* __restrict__ vpk,
                                                     const spmm_pk& M, unsigned lane, int g, int len, int (&sl)[3],
-                                                    double (&vv)[9]) {
+                                                    VT (&vv)[9]) {
+  constexpr int SH = sizeof(VT) == 8 ? 3 : 2;
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
     const int kc = min(g * 3 + j, len - 1);
     sl[j] = cp[(size_t)kc * 64 + lane];
     typedef const __attribute__((address_space(1))) char* gcp;
-    typedef const __attribute__((address_space(1))) double* gdp;
+    typedef const __attribute__((address_space(1))) VT* gdp;
     const gcp vk = (gcp)(vpk + M.base[j]);      // a scalar base; the lane adds a 32-bit byte offset (< 193 * 8)
     unsigned first = 1u;          // the place of the position's first kept value
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
       const pk_u64 mk = M.m[3 * j + i];
       const unsigned at = __builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, first));
-      const unsigned byte = (__builtin_amdgcn_inverse_ballot_w64(mk) ? at : 0u) << 3;
+      const unsigned byte = (__builtin_amdgcn_inverse_ballot_w64(mk) ? at : 0u) << SH;
       vv[3 * j + i] = *(gdp)(vk + byte);
       first += (unsigned)__builtin_popcountll(mk);
     }
   }
 }
 
-template <int TS, int XS, bool GRAM, int RL, bool PACK = false>
+template <int TS, int XS, bool GRAM, int RL, bool PACK = false, typename VT = double>
 __device__ __forceinline__ void spmm_runs_block(
     int m, const long long* __restrict__ sl_off, const int* __restrict__ sl_len,
     const int* __restrict__ sl_row0, const int* __restrict__ sl_nrows,
-    const unsigned short* __restrict__ slot16, const double* __restrict__ val,
+    const unsigned short* __restrict__ slot16, const VT* __restrict__ val,
     const int* __restrict__ blk_slice, const int* __restrict__ blk_ext_off,
     const int* __restrict__ blk_nlow, const int* __restrict__ ext_rows,
     const int* __restrict__ order, const double* __restrict__ X,
@@ -281,11 +287,11 @@ __device__ __forceinline__ void spmm_runs_block(
     const double* __restrict__ Rg, double* __restrict__ gpart, int gbase, int logical, int coff,
     const pk_u64* __restrict__ meta);
 
-template <int TS, int XS, bool GRAM, int RL = 3, bool PACK = false>
+template <int TS, int XS, bool GRAM, int RL = 3, bool PACK = false, typename VT = double>
 __device__ __forceinline__ void spmm_runs_body(
     int m, const long long* __restrict__ sl_off, const int* __restrict__ sl_len,
     const int* __restrict__ sl_row0, const int* __restrict__ sl_nrows,
-    const unsigned short* __restrict__ slot16, const double* __restrict__ val,
+    const unsigned short* __restrict__ slot16, const VT* __restrict__ val,
     const int* __restrict__ blk_slice, const int* __restrict__ blk_ext_off,
     const int* __restrict__ blk_nlow, const int* __restrict__ ext_rows,
     const int* __restrict__ order, int nlist, const double* __restrict__ X,
@@ -297,19 +303,20 @@ __device__ __forceinline__ void spmm_runs_body(
   const int idx = blockIdx.x >> 3;
   const int logical = (blockIdx.x & 7) * cpx + idx / NS;
   if (logical >= nlist) return;
-  spmm_runs_block<TS, XS, GRAM, RL, PACK>(m, sl_off, sl_len, sl_row0, sl_nrows, slot16, val, blk_slice, blk_ext_off,
+  spmm_runs_block<TS, XS, GRAM, RL, PACK, VT>(m, sl_off, sl_len, sl_row0, sl_nrows, slot16, val, blk_slice, blk_ext_off,
                                           blk_nlow, ext_rows, order, X, Xh, Y, Rg, gpart, gbase, logical,
                                           (idx % NS) * TS, meta);
 }
 
 // One block of slices: `logical` = its place in the launch's list, `coff` = first of the TS columns.
 // PACK: `val` is the packed value array and `meta` its masks and offsets; everything but the value fetch is
-// the same code.
-template <int TS, int XS, bool GRAM, int RL, bool PACK>
+// the same code.  VT = float (PACK only): `val` is the fp32 copy of the packed array; the two register sets hold
+// floats, and the FMAs, their order and the staging are those of VT = double.
+template <int TS, int XS, bool GRAM, int RL, bool PACK, typename VT>
 __device__ __forceinline__ void spmm_runs_block(
     int m, const long long* __restrict__ sl_off, const int* __restrict__ sl_len,
     const int* __restrict__ sl_row0, const int* __restrict__ sl_nrows,
-    const unsigned short* __restrict__ slot16, const double* __restrict__ val,
+    const unsigned short* __restrict__ slot16, const VT* __restrict__ val,
     const int* __restrict__ blk_slice, const int* __restrict__ blk_ext_off,
     const int* __restrict__ blk_nlow, const int* __restrict__ ext_rows,
     const int* __restrict__ order, const double* __restrict__ X,
@@ -318,6 +325,7 @@ __device__ __forceinline__ void spmm_runs_block(
     const pk_u64* __restrict__ meta) {
   static_assert(!GRAM || (TS == 4 && XS == 4), "the fused Gram block is built for 4-column panels");
   static_assert(!PACK || (RL == 3 && TS == XS && TS <= 4), "the packed values are read by the narrow run kernels");
+  static_assert(PACK || sizeof(VT) == 8, "fp32 values: the packed run plan only");
   extern __shared__ double sx[];
   const int b = order[logical];
   const int s0 = blk_slice[b], s1 = blk_slice[b + 1];
@@ -334,11 +342,11 @@ __device__ __forceinline__ void spmm_runs_block(
   // the barrier.
   constexpr int RU = spmm_ru<RL>::n;
   int slA[RU], slB[RU];
-  double vA[RL * RU], vB[RL * RU];
+  VT vA[RL * RU], vB[RL * RU];
   int s = s0 + wave;
   int len = 0;
   const unsigned short* __restrict__ cp = slot16;
-  const double* __restrict__ vp = val;
+  const VT* __restrict__ vp = val;
   // PACK: the masks and offsets of the group whose values are requested next
   const pk_u64* __restrict__ mp = meta;
   spmm_pk pN;
@@ -411,27 +419,27 @@ __device__ __forceinline__ void spmm_runs_block(
           spmm_runs_load_pack(cp, val, pN, lane, 2 * i + 1, len, slB, vB);
           spmm_pack_meta(mp, min(2 * i + 2, ngt - 1), len, pN);
           __builtin_amdgcn_sched_barrier(0);
-          spmm_runs_fma<TS, RL>(sx, slA, vA, acc);
+          spmm_runs_fma<TS, RL, VT>(sx, slA, vA, acc);
           __builtin_amdgcn_sched_barrier(0);
           spmm_runs_load_pack(cp, val, pN, lane, min(2 * i + 2, ngt - 1), len, slA, vA);
           spmm_pack_meta(mp, min(2 * i + 3, ngt - 1), len, pN);
           __builtin_amdgcn_sched_barrier(0);
-          spmm_runs_fma<TS, RL>(sx, slB, vB, acc);
+          spmm_runs_fma<TS, RL, VT>(sx, slB, vB, acc);
           __builtin_amdgcn_sched_barrier(0);
         }
-        if (ngt & 1) spmm_runs_fma<TS, RL>(sx, slA, vA, acc);
+        if (ngt & 1) spmm_runs_fma<TS, RL, VT>(sx, slA, vA, acc);
       } else {
         for (int i = 0; i < (ngt >> 1); ++i) {
           spmm_runs_load<RL>(cp, vp, lane, 2 * i + 1, len, slB, vB);
           __builtin_amdgcn_sched_barrier(0);      // (keeps the requests in front of the sums of the group before)
-          spmm_runs_fma<TS, RL>(sx, slA, vA, acc);
+          spmm_runs_fma<TS, RL, VT>(sx, slA, vA, acc);
           __builtin_amdgcn_sched_barrier(0);
           spmm_runs_load<RL>(cp, vp, lane, min(2 * i + 2, ngt - 1), len, slA, vA);
           __builtin_amdgcn_sched_barrier(0);
-          spmm_runs_fma<TS, RL>(sx, slB, vB, acc);
+          spmm_runs_fma<TS, RL, VT>(sx, slB, vB, acc);
           __builtin_amdgcn_sched_barrier(0);
         }
-        if (ngt & 1) spmm_runs_fma<TS, RL>(sx, slA, vA, acc);
+        if (ngt & 1) spmm_runs_fma<TS, RL, VT>(sx, slA, vA, acc);
       }
     }
     const int nr = sl_nrows[s], row_s = sl_row0[s];
@@ -496,29 +504,31 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(5))) void k_
 }
 
 // The run kernels on the packed value array (2 and 4 columns): the same grid, staging and occupancy.
-template <int TS>
+// VT = float: the same kernels on the fp32 copy of the packed array (preAlps_hip_set_operator_precision(32)).
+template <int TS, typename VT = double>
 __global__ __launch_bounds__(WG, 5) void k_spmm_runs_pack(
     int m, const long long* __restrict__ sl_off, const int* __restrict__ sl_len,
     const int* __restrict__ sl_row0, const int* __restrict__ sl_nrows,
-    const unsigned short* __restrict__ slot16, const double* __restrict__ val, const pk_u64* __restrict__ meta,
+    const unsigned short* __restrict__ slot16, const VT* __restrict__ val, const pk_u64* __restrict__ meta,
     const int* __restrict__ blk_slice, const int* __restrict__ blk_ext_off,
     const int* __restrict__ blk_nlow, const int* __restrict__ ext_rows,
     const int* __restrict__ order, int nlist, const double* __restrict__ X,
     const double* __restrict__ Xh, double* __restrict__ Y) {
-  spmm_runs_body<TS, TS, false, 3, true>(m, sl_off, sl_len, sl_row0, sl_nrows, slot16, val, blk_slice, blk_ext_off,
+  spmm_runs_body<TS, TS, false, 3, true, VT>(m, sl_off, sl_len, sl_row0, sl_nrows, slot16, val, blk_slice, blk_ext_off,
                                          blk_nlow, ext_rows, order, nlist, X, Xh, Y, nullptr, nullptr, 0, meta);
 }
 
+template <typename VT = double>
 __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(5))) void k_spmm_runs_gram_pack(
     int m, const long long* __restrict__ sl_off, const int* __restrict__ sl_len,
     const int* __restrict__ sl_row0, const int* __restrict__ sl_nrows,
-    const unsigned short* __restrict__ slot16, const double* __restrict__ val, const pk_u64* __restrict__ meta,
+    const unsigned short* __restrict__ slot16, const VT* __restrict__ val, const pk_u64* __restrict__ meta,
     const int* __restrict__ blk_slice, const int* __restrict__ blk_ext_off,
     const int* __restrict__ blk_nlow, const int* __restrict__ ext_rows,
     const int* __restrict__ order, int nlist, const double* __restrict__ X,
     const double* __restrict__ Xh, double* __restrict__ Y,
     const double* __restrict__ Rg, double* __restrict__ gpart, int gbase) {
-  spmm_runs_body<4, 4, true, 3, true>(m, sl_off, sl_len, sl_row0, sl_nrows, slot16, val, blk_slice, blk_ext_off, blk_nlow,
+  spmm_runs_body<4, 4, true, 3, true, VT>(m, sl_off, sl_len, sl_row0, sl_nrows, slot16, val, blk_slice, blk_ext_off, blk_nlow,
                                       ext_rows, order, nlist, X, Xh, Y, Rg, gpart, gbase, meta);
 }
 
@@ -541,19 +551,33 @@ static struct {
 
 static long long g_sg_launches = 0;
 
+// exact: the product on the fp64 values whatever copy the plan holds, and outside every Gram request (the start
+// residual of a guess, operator.c: pa_operator_apply_exact).  Otherwise a plan with a fp32 copy (pl->val32: a packed
+// run plan at up to 4 columns) is read through the float instantiations of the packed kernels.
 template <int TS>
 static int launch_spmm(const pa_spmm_plan_t* pl, const int* order, int nlist, const double* X,
-                       const double* Xh, double* Y) {
+                       const double* Xh, double* Y, bool exact) {
   if (nlist <= 0) return 0;
+  const bool f32 = pl->val32 && !exact;
+  if (f32 && !(pl->runs && pl->packed && TS <= 4)) {
+    pa_rt_set_error("a fp32 copy of the values beside a plan that is no packed run plan at up to 4 columns (stride %d)", TS);
+    return 1;
+  }
   if constexpr (TS == 4) {
     const size_t lds = (size_t)pl->stage_cap * TS * 8;
-    if (g_sg.armed && (pl->runs || pl->staged) && lds <= 64 * 1024 && X == g_sg.X && Y == g_sg.Y && g_sg.count >= 0 &&
-        g_sg.count + nlist <= g_sg.cap) {
+    // (an exact product neither serves nor ends a request)
+    if (!exact && g_sg.armed && (pl->runs || pl->staged) && lds <= 64 * 1024 && X == g_sg.X && Y == g_sg.Y &&
+        g_sg.count >= 0 && g_sg.count + nlist <= g_sg.cap) {
       const int cpx = (nlist + 7) / 8;
       // (spmm_gram_tail passes the wavefronts' shares through the first 1024 bytes, whatever a tiny plan stages)
       const size_t lds_gram = lds > 1024 ? lds : 1024;
-      if (pl->runs && pl->packed)
-        PA_LAUNCH(k_spmm_runs_gram_pack, dim3(cpx * 8), dim3(WG), lds_gram, cur_stream(), pl->m, pl->sl_off,
+      if (pl->runs && pl->packed && f32)
+        PA_LAUNCH(k_spmm_runs_gram_pack<float>, dim3(cpx * 8), dim3(WG), lds_gram, cur_stream(), pl->m, pl->sl_off,
+                  pl->sl_len, pl->sl_row0, pl->sl_nrows, pl->col16, pl->val32, pl->pk_meta, pl->blk_slice,
+                  pl->blk_ext_off, pl->blk_nlow, pl->ext_rows, order, nlist, X, Xh, Y, g_sg.R, g_sg.partials,
+                  g_sg.count);
+      else if (pl->runs && pl->packed)
+        PA_LAUNCH(k_spmm_runs_gram_pack<double>, dim3(cpx * 8), dim3(WG), lds_gram, cur_stream(), pl->m, pl->sl_off,
                   pl->sl_len, pl->sl_row0, pl->sl_nrows, pl->col16, pl->val, pl->pk_meta, pl->blk_slice,
                   pl->blk_ext_off, pl->blk_nlow, pl->ext_rows, order, nlist, X, Xh, Y, g_sg.R, g_sg.partials,
                   g_sg.count);
@@ -569,7 +593,7 @@ static int launch_spmm(const pa_spmm_plan_t* pl, const int* order, int nlist, co
       ++g_sg_launches;
       return kfail("k_spmm_runs");
     }
-    if (g_sg.armed && !pl->runs && !pl->staged && X == g_sg.X && Y == g_sg.Y && g_sg.count >= 0 &&
+    if (!exact && g_sg.armed && !pl->runs && !pl->staged && X == g_sg.X && Y == g_sg.Y && g_sg.count >= 0 &&
         g_sg.count + nlist <= g_sg.cap) {                             // the window kernel (e.g. 7-point Poisson)
       int win_cap = pl->win_cap;
       if ((size_t)win_cap * TS * 8 > 32 * 1024) win_cap = (32 * 1024) / (TS * 8);
@@ -584,15 +608,20 @@ static int launch_spmm(const pa_spmm_plan_t* pl, const int* order, int nlist, co
         return kfail("k_spmm_gram");
       }
     }
-    if (g_sg.armed && X == g_sg.X && Y == g_sg.Y) g_sg.count = -1;    // this product leaves no Gram block
+    if (!exact && g_sg.armed && X == g_sg.X && Y == g_sg.Y) g_sg.count = -1;    // this product leaves no Gram block
   }
   if (pl->runs && pl->packed) {       // the value array without its zeros: the narrow run kernel reads it
     if constexpr (TS <= 4) {
       const size_t lds = (size_t)pl->stage_cap * TS * 8;
       const int cpx = (nlist + 7) / 8;
-      PA_LAUNCH((k_spmm_runs_pack<TS>), dim3(cpx * 8), dim3(WG), lds, cur_stream(), pl->m, pl->sl_off, pl->sl_len,
-                pl->sl_row0, pl->sl_nrows, pl->col16, pl->val, pl->pk_meta, pl->blk_slice, pl->blk_ext_off,
-                pl->blk_nlow, pl->ext_rows, order, nlist, X, Xh, Y);
+      if (f32)
+        PA_LAUNCH((k_spmm_runs_pack<TS, float>), dim3(cpx * 8), dim3(WG), lds, cur_stream(), pl->m, pl->sl_off,
+                  pl->sl_len, pl->sl_row0, pl->sl_nrows, pl->col16, pl->val32, pl->pk_meta, pl->blk_slice,
+                  pl->blk_ext_off, pl->blk_nlow, pl->ext_rows, order, nlist, X, Xh, Y);
+      else
+        PA_LAUNCH((k_spmm_runs_pack<TS, double>), dim3(cpx * 8), dim3(WG), lds, cur_stream(), pl->m, pl->sl_off,
+                  pl->sl_len, pl->sl_row0, pl->sl_nrows, pl->col16, pl->val, pl->pk_meta, pl->blk_slice,
+                  pl->blk_ext_off, pl->blk_nlow, pl->ext_rows, order, nlist, X, Xh, Y);
       return kfail("k_spmm_runs_pack");
     } else {
       pa_rt_set_error("a packed run plan at panel stride %d: no kernel reads it", TS);
@@ -670,14 +699,14 @@ int pa_k_spmm_gram_take(const double* X, const double* Y) {
 }
 
 int pa_k_spmm(const pa_spmm_plan_t* pl, int ts, const double* X, const double* Xhalo, double* Y,
-              int phase) {
+              int phase, int exact) {
   const int* order = pl->order;
   int n = pl->nblk;
-  if (phase != 1 && g_sg.armed && X == g_sg.X && Y == g_sg.Y) g_sg.count = 0;   /* a new product starts */
+  if (!exact && phase != 1 && g_sg.armed && X == g_sg.X && Y == g_sg.Y) g_sg.count = 0;   /* a new product starts */
   if (phase == 0) n = pl->n_interior;
   else if (phase == 1) { order += pl->n_interior; n = pl->nblk - pl->n_interior; }
   const double* Xh = Xhalo ? Xhalo : X;
-  TS_DISPATCH(ts, return launch_spmm<TS_>(pl, order, n, X, Xh, Y));
+  TS_DISPATCH(ts, return launch_spmm<TS_>(pl, order, n, X, Xh, Y, exact != 0));
   return 0;
 }
 

@@ -55,7 +55,33 @@ __global__ __launch_bounds__(WG) void k_pack_set_values(const unsigned* __restri
   if constexpr (!WRITE) { if (miss) atomicAdd(misses, miss); }
 }
 
+// The fp32 copy of a packed value array (preAlps_hip_set_operator_precision(32)): val32[i] = (float)val[i] for the n
+// elements, the steps' zeros and the slack included (they stay 0.0f), so the masks and offsets of the pack address
+// both arrays.  A streaming kernel, the grid strides over the elements.  A value that is finite in fp64 and rounds to
+// +-Inf is counted (bad[0]) and one such value is left in bad[1]: the caller refuses the copy.
+__global__ __launch_bounds__(WG) void k_plan_round_values(const double* __restrict__ val, float* __restrict__ val32,
+                                                         size_t n, unsigned long long* __restrict__ bad) {
+  const size_t stride = (size_t)gridDim.x * WG;
+  unsigned lost = 0;
+  for (size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < n; i += stride) {
+    const double v = __builtin_nontemporal_load(val + i);
+    const float f = (float)v;
+    __builtin_nontemporal_store(f, val32 + i);
+    if (v - v == 0.0 && !(f - f == 0.0f)) { ++lost; bad[1] = (unsigned long long)__double_as_longlong(v); }
+  }
+  if (lost) atomicAdd(bad, (unsigned long long)lost);
+}
+
 }  // namespace
+
+extern "C" int pa_k_plan_round_values(const double* val, float* val32, size_t n, unsigned long long* bad) {
+  if (n == 0) return 0;
+  const int cus = pa_rt_num_cus() > 0 ? pa_rt_num_cus() : 256;
+  size_t blocks = (n + WG - 1) / WG;
+  if (blocks > (size_t)8 * cus) blocks = (size_t)8 * cus;
+  PA_LAUNCH(k_plan_round_values, dim3((unsigned)blocks), dim3(WG), 0, cur_stream(), val, val32, n, bad);
+  return kfail("k_plan_round_values");
+}
 
 extern "C" int pa_k_pack_set_values(const unsigned* map, const double* pv, const unsigned long long* meta, double* packed,
                                     size_t n, int write, unsigned* misses) {

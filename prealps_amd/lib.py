@@ -10,6 +10,8 @@ ORTHOMIN, ORTHODIR, ORTHODIR_FUSED = 0, 1, 2
 ADAPT_BS, NO_BS_RED = 0, 1
 ROW_MAJOR, COL_MAJOR = 0, 1
 SYS_DEVICE, SYS_STOP_ORIGINAL = 1, 2      # flags of preAlps_ECGSolveSystem
+# *status of preAlps_ECGSolveSystemRefined
+REFINE_STATUS = {0: "converged", 1: "out of passes", 2: "out of iterations", 3: "stagnated"}
 
 
 class PreAlpsError(RuntimeError):
@@ -87,6 +89,7 @@ EXPORTS = [
     "preAlps_OperatorGetScalingPtr", "preAlps_ECGSolveSystem", "preAlps_OperatorSystemResiduals",
     "preAlps_BlockJacobiSetCoarseSpace", "preAlps_BlockJacobiClearCoarseSpace",
     "preAlps_BlockJacobiGetCoarseAggregates",
+    "preAlps_hip_set_operator_precision", "preAlps_ECGSolveSystemRefined",
 ]
 
 _lib = None
@@ -131,6 +134,8 @@ def load():
     # b, x0, x: host or device addresses (PREALPS_SYS_DEVICE), so plain pointers
     L.preAlps_ECGSolveSystem.argtypes = [pe, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                          C.c_int, pd, pi, pd, pd, pd, C.c_int, pi]
+    L.preAlps_ECGSolveSystemRefined.argtypes = [pe, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                C.c_int, pd, pi, pd, pd, pd, C.c_int, pi, C.c_int, pi, pi, pd, pi]
     L.preAlps_OperatorSystemResiduals.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, pd, pd]
     L.preAlps_OperatorGetScalingPtr.argtypes = [C.POINTER(pd), pi]
     L._preAlps_ECGReset.argtypes = [pe, pd, pi]
@@ -177,6 +182,7 @@ def load():
     L.preAlps_hip_graphs.restype = None
     L.preAlps_hip_set_nd_precision.argtypes = [C.c_int]
     L.preAlps_hip_set_band_precision.argtypes = [C.c_int]
+    L.preAlps_hip_set_operator_precision.argtypes = [C.c_int]
     L.preAlps_hip_timing_reset.restype = None
     L.preAlps_hip_shutdown.restype = None
     L.preAlps_hip_set_abort_mode.restype = None

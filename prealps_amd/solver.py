@@ -42,6 +42,13 @@ class EcgResult:
     # and the recurrence residual norms ||b_j - A x_j|| in the caller's units at the end, whichever metric stopped it
     metric: str = None
     sys_res_original: np.ndarray = None
+    # solve_system(refine=True) only: the passes that iterated, the iterations of each, the start residuals of every
+    # pass in the metric of the stopping test (row p; row `passes` = what ended the chain), and why it ended:
+    # "converged", "out of passes", "out of iterations" or "stagnated"
+    passes: int = None
+    pass_iters: np.ndarray = None
+    pass_res: np.ndarray = None
+    refine_status: str = None
 
 
 class DistributedHooks:
@@ -275,6 +282,7 @@ class EcgProblem:
         self.has_precond = False
         self._precond_args = (None, None)
         self._coarse = None
+        self._set_precision = False
 
     def part_vector(self):
         """part[i] of every original row i, recovered from the permutation and rowPos."""
@@ -370,6 +378,19 @@ class EcgProblem:
                 self._coarse = None
         check(rc, "preAlps_BlockJacobiUpdateValues")
 
+    def set_operator_precision(self, precision):
+        """preAlps_hip_set_operator_precision: storage of the matrix values the products stream, "double" or "single"
+        (every value rounded once to fp32, all arithmetic in fp64).  It takes effect at once and for every plan cut
+        later; it reaches the packed run plan at up to 4 columns, every other plan keeps fp64 -- stat("spmm_precision")
+        tells.  The setting is the library's: close() of a problem that called this puts it back to the default
+        (PREALPS_SPMM_PRECISION); a problem that never did leaves the library's setting alone.  A solve
+        on the rounded matrix converges to that matrix's solution; solve_system(..., refine=True) repairs it."""
+        bits = {"double": 64, "single": 32}.get(precision)
+        if bits is None:
+            raise ValueError("precision must be 'double' or 'single', not %r" % (precision,))
+        check(self.L.preAlps_hip_set_operator_precision(bits), "preAlps_hip_set_operator_precision")
+        self._set_precision = True
+
     def update_values(self, val, precond="keep"):
         """preAlps_OperatorUpdateValues: new values for the same pattern, partition and scaling flag, in the order of
         the val this problem was built from (the whole matrix); the operator becomes the one a fresh problem built from
@@ -464,7 +485,7 @@ class EcgProblem:
             torch.cuda.current_stream().synchronize()
 
     def solve_system(self, b, t, x0=None, stop="original", ortho_alg=ORTHODIR, bs_red=NO_BS_RED, tol=1e-5,
-                     max_iter=1000):
+                     max_iter=1000, refine=False, max_passes=4):
         """preAlps_ECGSolveSystem: A x = b as the caller stated it -- the rows in the order of the matrix this problem
         was built from, the values in its units -- for one system (b of shape (N,)) or k systems (b of shape (N, k), t a
         multiple of k), with or without a starting value x0 of the same shape.  One process.
@@ -477,7 +498,12 @@ class EcgProblem:
         Returns an EcgResult: x in the caller's order and units, metric = stop, sys_res / sys_normb / sys_hist in that
         metric, sys_res_original = the recurrence residual norms in the caller's units at the end; res / bs / normb /
         final_res stay the scaled Frobenius norms.  Mixed host and device arguments, a tensor that is not float64, wrong
-        shapes and a bad stop raise ValueError before any library call."""
+        shapes and a bad stop raise ValueError before any library call.
+        refine=True: preAlps_ECGSolveSystemRefined -- the same solve, then up to max_passes - 1 more, each started from
+        the x before it with a start residual formed on the fp64 matrix, until that residual meets tol (what makes
+        set_operator_precision("single") safe); max_iter bounds all passes together, iters is their sum, the histories
+        are concatenated, and passes / pass_iters / pass_res / refine_status say what happened.  refine=False is
+        preAlps_ECGSolveSystem, and max_passes is not looked at."""
         if stop not in ("original", "scaled"):
             raise ValueError("stop must be 'original' or 'scaled', not %r" % (stop,))
         kind, k, vector = self._system_args("solve_system", b, x0, "x0")
@@ -512,10 +538,24 @@ class EcgProblem:
         sys_hist = np.zeros((cap, k), order="F")
         sys_normb, sys_end = np.zeros(k), np.zeros(k)
         nh = C.c_int()
+        extra = {}
         t0 = time.perf_counter()
-        check(L.preAlps_ECGSolveSystem(C.byref(e), k, pb, ldb, px0, ldx0, px, ldx, flags, _pd(res), _pi(bs),
-                                       _pd(sys_hist), _pd(sys_normb), _pd(sys_end), cap, C.byref(nh)),
-              "preAlps_ECGSolveSystem")
+        if refine:
+            mp = int(max_passes)
+            room = max(mp, 0)
+            npass, status = C.c_int(), C.c_int()
+            pass_iters = np.zeros(room + 1, dtype=np.int32)
+            pass_res = np.zeros((room + 1, k))
+            check(L.preAlps_ECGSolveSystemRefined(C.byref(e), k, pb, ldb, px0, ldx0, px, ldx, flags, _pd(res), _pi(bs),
+                                                  _pd(sys_hist), _pd(sys_normb), _pd(sys_end), cap, C.byref(nh), mp,
+                                                  C.byref(npass), _pi(pass_iters), _pd(pass_res), C.byref(status)),
+                  "preAlps_ECGSolveSystemRefined")
+            extra = dict(passes=npass.value, pass_iters=pass_iters[:npass.value].copy(),
+                         pass_res=pass_res[:npass.value + 1].copy(), refine_status=_l.REFINE_STATUS[status.value])
+        else:
+            check(L.preAlps_ECGSolveSystem(C.byref(e), k, pb, ldb, px0, ldx0, px, ldx, flags, _pd(res), _pi(bs),
+                                           _pd(sys_hist), _pd(sys_normb), _pd(sys_end), cap, C.byref(nh)),
+                  "preAlps_ECGSolveSystem")
         dt = time.perf_counter() - t0
         n = nh.value
         if vector:
@@ -525,7 +565,7 @@ class EcgProblem:
                          normb=e.normb, seconds=dt, timers=timers,
                          sys_res=sys_hist[n - 1].copy() if n else (sys_end.copy() if stop == "original" else None),
                          sys_normb=sys_normb, sys_hist=np.ascontiguousarray(sys_hist[:n]), metric=stop,
-                         sys_res_original=sys_end)
+                         sys_res_original=sys_end, **extra)
 
     def system_residuals(self, B, X):
         """preAlps_OperatorSystemResiduals: (res, normb) with res[j] = ||b_j - A x_j|| and normb[j] = ||b_j|| in the
@@ -735,6 +775,9 @@ class EcgProblem:
     def close(self):
         self.L.preAlps_BlockJacobiFree()
         self.L.preAlps_OperatorFree()
+        if getattr(self, "_set_precision", False):      # (the library's setting: back to the default if this problem moved it)
+            self.L.preAlps_hip_set_operator_precision(0)
+            self._set_precision = False
         self.has_precond = False
         if getattr(self, "_plan_only", False):
             self.L.preAlps_hip_plan_only(0)
