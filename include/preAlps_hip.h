@@ -499,8 +499,10 @@ int preAlps_hip_panel_permute_solve(const CPLM_Mat_Dense_t* Z, CPLM_Mat_Dense_t*
  * precision; "bj_factor_bytes" does not count them), "bj_g4_last_ring" / "bj_g4_last_bits" /
  * "bj_g4_last_pipelined" (the last launch that read them: LDS ring depth, storage bits of the records, 1 = the
  * pipelined few-blocks chain), "ecg_graph_captures" / "ecg_graph_replays" (iteration segments captured and graphs
- * launched by the driver loops so far, preAlps_hip_graphs), "spmm_precision" (64 / 32: storage of the values the
- * plan in use streams, 0: no plan yet), ...  Returns non-zero for unknown keys. */
+ * launched by the driver loops so far, preAlps_hip_graphs), "ecg_x_skips" / "ecg_x_flushes" (row passes of the
+ * library's loops that left X alone so far, and owed updates of X that a stop paid with a launch of its own,
+ * PREALPS_ECG_X_DEFER), "spmm_precision" (64 / 32: storage of the values the plan in use streams, 0: no plan
+ * yet), ...  Returns non-zero for unknown keys. */
 int preAlps_hip_get_stat(const char* key, double* value);
 /* A stopwatch made of two hipEvents on the library stream: start records the
  * first, stop records the second, waits for it and returns the device time

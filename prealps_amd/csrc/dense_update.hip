@@ -3,7 +3,8 @@
 //    kernels and in one pass (k_trsm_update; on the matrix cores at 8 / 16 columns);
 //  - Z -= [V0 | V1] beta: lane per row up to 4 columns, on the matrix cores at 8 / 16, with the lazy normalisation,
 //    the packing of the send rows (g_zpack) and Z^T Z as by-products;
-//  - k_update_xrz, which is both in one pass and so keeps the two halves in one unit.
+//  - k_update_xrz, which is both in one pass and so keeps the two halves in one unit; it moves X in every pass or in
+//    every second one (its X modes), and k_flush_x pays an update of X that a stop left owed.
 // See dense_gram.hip for the layout of panels and blocks.
 #include "dense_device.h"
 
@@ -504,24 +505,51 @@ __global__ __launch_bounds__(WG) void k_update_z(int m, int a_lo, int a_hi, int 
 // through one launch.  Per element the arithmetic of the two kernels (the same device functions); the grid, the
 // row -> workgroup map and the column sums of R^2 are k_trsm_update's (update_grid), so k_trace_finish forms the
 // same norm.  ucur of k_update_z is U itself: the factor k_trsm_update keeps in ukeep for it.
+//
+// XM, what the pass does with X (ecg_loops.c: solve_first_step decides, pa_ecg_x_mode).  Nobody reads X between two row
+// passes of one call of the library's loops, so its 2 x 33 MB need not move in every pass:
+//   XM_EVERY  x += p alpha, as k_trsm_update;
+//   XM_SKIP   X is neither read nor written: the update is owed.  U is in ukeep and P stays raw, as ever; workgroup 0
+//             keeps alpha in akeep, because the finish of the next iteration overwrites it;
+//   XM_BOTH   the owed update first -- the raw P_prev row normalised with U_prev (sfac's second half, already here for
+//             Z) by trsm_update_row's own loop, x += p_prev alpha_prev with alpha_prev from akeep -- then this
+//             iteration's: the two additions to x[c] of two XM_EVERY passes, in their order, so the same bits.
+// k_flush_x pays a debt no pass will pay (a stop).  xnt holds wherever X moves.
+enum { XM_EVERY = 0, XM_SKIP = 1, XM_BOTH = 2 };
+// The owed update of one row: p (raw, of the factor su; sd = 1 / its diagonal) <- p U^-1, x += p alpha.  This IS
+// trsm_update_row -- on an AP, an R and column sums that nobody reads, which the compiler drops.
 template <int TS>
+__device__ __forceinline__ void owed_x_row(double (&p)[TS], double (&x)[TS], const double* su, const double* sd,
+                                           const double* sa, int t) {
+  double ap[TS], r[TS], rr[TS];
+#pragma unroll
+  for (int c = 0; c < TS; ++c) ap[c] = r[c] = rr[c] = 0.0;
+  trsm_update_row<TS>(p, ap, x, r, rr, su, sd, sa, t, t);
+}
+template <int TS, int XM>
 __global__ __launch_bounds__(WG) void k_update_xrz(int m, int t, double* U, double* alpha, const double* __restrict__ P,
                                                    const double* __restrict__ AP, const double* __restrict__ Pprev,
                                                    double* __restrict__ X, double* __restrict__ R,
                                                    double* __restrict__ Z, double* __restrict__ rtr,
                                                    double* __restrict__ ukeep, const double* __restrict__ beta,
-                                                   int ldb, const double* __restrict__ uprev, int xnt) {
+                                                   int ldb, const double* __restrict__ uprev, int xnt,
+                                                   double* __restrict__ akeep) {
   __shared__ double su[TS * TS];
   __shared__ double sd[TS];
   __shared__ double sa[TS * TS];
   __shared__ double sb[2 * TS * TS];
   __shared__ double sfac[2 * TS * TS];
   __shared__ double sc[7 * TS * TS];
+  __shared__ double sdp[TS];          // XM_BOTH: 1 / diag(U_prev) and alpha_prev
+  __shared__ double sap[TS * TS];
   const int na = 2 * t, tt = t * t;
   for (int e = threadIdx.x; e < na * t; e += WG) sb[e] = beta[(e % na) + ldb * (e / na)];
   for (int e = threadIdx.x; e < 2 * tt; e += WG) sfac[e] = e < tt ? U[e] : uprev[e - tt];
-  trsm_update_prologue<TS>(t, t, U, alpha, nullptr, nullptr, ukeep, su, sd, sa);    // (its barriers cover sb / sfac)
-  lazy_coeffs_wg<TS>(sb, sfac, t, t, sc);
+  if (XM == XM_BOTH) for (int e = threadIdx.x; e < tt; e += WG) sap[e] = akeep[e];
+  trsm_update_prologue<TS>(t, t, U, alpha, nullptr, nullptr, ukeep, su, sd, sa);    // (its barriers cover sb / sfac / sap)
+  if (XM == XM_SKIP && blockIdx.x == 0) for (int e = threadIdx.x; e < tt; e += WG) akeep[e] = sa[e];
+  if (XM == XM_BOTH && threadIdx.x < t) sdp[threadIdx.x] = 1.0 / sfac[tt + threadIdx.x + t * threadIdx.x];   // (sd's own expression)
+  lazy_coeffs_wg<TS>(sb, sfac, t, t, sc);      // (ends with a barrier: sdp is there)
   const double* C0 = sc + 4 * TS * TS; const double* C1 = sc + 5 * TS * TS; const double* C2 = sc + 6 * TS * TS;
   double rr[TS];
 #pragma unroll
@@ -531,19 +559,49 @@ __global__ __launch_bounds__(WG) void k_update_xrz(int m, int t, double* U, doub
     double p[TS], ap[TS], x[TS], r[TS], z[TS], v0[TS], v1[TS], o[TS];
     load_row<TS>(P, row, v0);
     load_row<TS>(AP, row, ap);
-    if (xnt) load_row_nt<TS>(X, row, x); else load_row<TS>(X, row, x);
+    if (XM == XM_SKIP) {
+#pragma unroll
+      for (int c = 0; c < TS; ++c) x[c] = 0.0;      // (never stored: the X half of the row code falls away)
+    } else if (xnt) load_row_nt<TS>(X, row, x); else load_row<TS>(X, row, x);
     load_row<TS>(R, row, r);
     load_row<TS>(Z, row, z);
     load_row<TS>(Pprev, row, v1);
+    if (XM == XM_BOTH) {
+#pragma unroll
+      for (int c = 0; c < TS; ++c) p[c] = v1[c];
+      owed_x_row<TS>(p, x, sfac + tt, sdp, sap, t);
+    }
 #pragma unroll
     for (int c = 0; c < TS; ++c) p[c] = v0[c];      // (normalised in registers below; Z's update takes the raw row)
     trsm_update_row<TS>(p, ap, x, r, rr, su, sd, sa, t, t);
     update_z_lazy_row<TS>(z, v0, v1, o, C0, C1, C2, t, t, t);
-    if (xnt) store_row_nt<TS>(X, row, x); else store_row<TS>(X, row, x);
+    if (XM != XM_SKIP) { if (xnt) store_row_nt<TS>(X, row, x); else store_row<TS>(X, row, x); }
     store_row<TS>(R, row, r);
     store_row<TS>(Z, row, o);
   }
   block_sum_cols<TS>(rr, rtr + (size_t)blockIdx.x * TS);
+}
+
+// X += (P_prev U_prev^-1) alpha_prev: the update a k_update_xrz<XM_SKIP> pass owes, where no XM_BOTH pass follows it.
+template <int TS>
+__global__ __launch_bounds__(WG) void k_flush_x(int m, int t, const double* __restrict__ uprev,
+                                                const double* __restrict__ akeep, const double* __restrict__ Pprev,
+                                                double* __restrict__ X, int xnt) {
+  __shared__ double su[TS * TS];
+  __shared__ double sd[TS];
+  __shared__ double sa[TS * TS];
+  for (int e = threadIdx.x; e < t * t; e += WG) { su[e] = uprev[e]; sa[e] = akeep[e]; }
+  __syncthreads();
+  if (threadIdx.x < t) sd[threadIdx.x] = 1.0 / su[threadIdx.x + t * threadIdx.x];
+  __syncthreads();
+  const size_t stride = (size_t)gridDim.x * WG;
+  for (size_t row = (size_t)blockIdx.x * WG + threadIdx.x; row < (size_t)m; row += stride) {
+    double p[TS], x[TS];
+    load_row<TS>(Pprev, row, p);
+    if (xnt) load_row_nt<TS>(X, row, x); else load_row<TS>(X, row, x);
+    owed_x_row<TS>(p, x, su, sd, sa, t);
+    if (xnt) store_row_nt<TS>(X, row, x); else store_row<TS>(X, row, x);
+  }
 }
 
 // 16-column panels on the f64 matrix cores: a tile of 16 rows of Z is the C/D operand (lane l
@@ -902,18 +960,46 @@ int pa_k_trsm_update(int m, int ts, int t, int nc, double* U, double* alpha, dou
   return pa_k_trace_finish(rtr_partials, blocks, ts, trace_nc, res2, info, host);
 }
 
-int pa_k_update_xrz(int m, int ts, int t, double* U, double* alpha, const double* P, const double* AP,
-                    const double* P_prev, double* X, double* R, double* Z, double* rtr_partials, int* nblk,
-                    double* ukeep, const double* beta, int ldb, const double* uprev) {
+int pa_k_update_xrz_mode(int m, int ts, int t, double* U, double* alpha, const double* P, const double* AP,
+                         const double* P_prev, double* X, double* R, double* Z, double* rtr_partials, int* nblk,
+                         double* ukeep, const double* beta, int ldb, const double* uprev, int xmode, double* akeep) {
   if (ts != 4 || t < 1 || t > 4 || ldb < 2 * t || !U || !alpha || !P_prev || !ukeep || !beta || !uprev) {
     pa_rt_set_error("pa_k_update_xrz: 4-column panels with lazy normalisation only");
     return 1;
   }
+  if (xmode < XM_EVERY || xmode > XM_BOTH || (xmode != XM_EVERY && !akeep)) {
+    pa_rt_set_error("pa_k_update_xrz: X mode %d, or no place for the kept alpha", xmode);
+    return 1;
+  }
   const int blocks = update_grid(m);
   *nblk = blocks;
-  PA_LAUNCH((k_update_xrz<4>), dim3(blocks), dim3(WG), 0, cur_stream(), m, t, U, alpha, P, AP, P_prev, X, R, Z,
-            rtr_partials, ukeep, beta, ldb, uprev, x_nontemporal(m, ts));
+  const int xnt = x_nontemporal(m, ts);
+  if (xmode == XM_SKIP)
+    PA_LAUNCH((k_update_xrz<4, XM_SKIP>), dim3(blocks), dim3(WG), 0, cur_stream(), m, t, U, alpha, P, AP, P_prev, X, R, Z,
+              rtr_partials, ukeep, beta, ldb, uprev, xnt, akeep);
+  else if (xmode == XM_BOTH)
+    PA_LAUNCH((k_update_xrz<4, XM_BOTH>), dim3(blocks), dim3(WG), 0, cur_stream(), m, t, U, alpha, P, AP, P_prev, X, R, Z,
+              rtr_partials, ukeep, beta, ldb, uprev, xnt, akeep);
+  else
+    PA_LAUNCH((k_update_xrz<4, XM_EVERY>), dim3(blocks), dim3(WG), 0, cur_stream(), m, t, U, alpha, P, AP, P_prev, X, R, Z,
+              rtr_partials, ukeep, beta, ldb, uprev, xnt, akeep);
   return kfail("k_update_xrz");
+}
+int pa_k_update_xrz(int m, int ts, int t, double* U, double* alpha, const double* P, const double* AP,
+                    const double* P_prev, double* X, double* R, double* Z, double* rtr_partials, int* nblk,
+                    double* ukeep, const double* beta, int ldb, const double* uprev) {
+  return pa_k_update_xrz_mode(m, ts, t, U, alpha, P, AP, P_prev, X, R, Z, rtr_partials, nblk, ukeep, beta, ldb, uprev,
+                              XM_EVERY, nullptr);
+}
+
+int pa_k_flush_x(int m, int ts, int t, const double* uprev, const double* akeep, const double* P_prev, double* X) {
+  if (ts != 4 || t < 1 || t > 4 || !uprev || !akeep || !P_prev || !X) {
+    pa_rt_set_error("pa_k_flush_x: 4-column panels with a kept factor and a kept alpha only");
+    return 1;
+  }
+  PA_LAUNCH((k_flush_x<4>), dim3(update_grid(m)), dim3(WG), 0, cur_stream(), m, t, uprev, akeep, P_prev, X,
+            x_nontemporal(m, ts));
+  return kfail("k_flush_x");
 }
 
 /* One-shot: the next pa_k_update_z on a panel of up to 4 columns also packs the send rows of the Z it writes

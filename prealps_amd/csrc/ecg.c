@@ -134,6 +134,8 @@ int _preAlps_ECGMalloc(preAlps_ECG_t* ecg) {
   pv->d_info = (int*)pa_rt_malloc((8 + T) * sizeof(int));
   if (!pv->d_info) return PA_FAIL("device allocation failed: %s", pa_rt_error());
   pv->d_piv = pv->d_info + 8;
+  pv->d_akeep = (double*)pa_rt_malloc(2 * (size_t)T * T * sizeof(double));    /* (not in the pool: see ecg_priv.h) */
+  if (!pv->d_akeep) return PA_FAIL("device allocation failed: %s", pa_rt_error());
   pv->h_pin = (double*)pa_rt_host_alloc_coherent((16 + 4 * (size_t)T * T) * sizeof(double));
   pv->h_pin_i = (int*)pa_rt_host_alloc((8 + T) * sizeof(int));
   pv->h_grp = (double*)pa_rt_host_alloc_coherent(48 * sizeof(double));
@@ -183,6 +185,8 @@ int pa_ecg_reset_state(preAlps_ECG_t* ecg, ecg_priv_t* pv, int nrhs, int guess, 
   pv->rotate = sw.rotate; pv->fuse = sw.fuse; pv->lazy_norm = sw.lazy_norm; pv->lazy_stop = sw.lazy_stop;
   pv->use_graphs = sw.use_graphs; pv->poll = sw.poll; pv->ride = sw.ride;
   pv->solve_first = solve_first_switch();
+  pv->x_defer = pa_env_flag("PREALPS_ECG_X_DEFER", 1) != 0;
+  pv->x_pending = 0;
   pv->uu_cur = 0;
   pv->z_ready = 0;
   pv->sf_ready = 0;
@@ -543,6 +547,21 @@ static int update_iterate(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
   TAC(PA_T_UPDATE, gemm_t);
   pv->rtr_valid = RTR_SUMMED;
   pv->lazy_ptr = NULL;
+  return 0;
+}
+
+/* X every second row pass (ecg_priv.h: x_pending).  The debt is described by where the panels and the factors lie
+ * AFTER the step that left it: pa_ecg_shift_directions has made its P the previous panel, and uu_cur has moved on. */
+static long long g_x_skips, g_x_flushes;
+long long pa_ecg_x_count(int which) { return which ? g_x_flushes : g_x_skips; }
+void pa_ecg_x_owed(ecg_priv_t* pv) { pv->x_pending = 1; ++g_x_skips; }
+int pa_ecg_flush_x(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
+  if (!pv->x_pending) return 0;
+  const int T = ecg->enlFac;
+  const size_t prev = (size_t)(1 - pv->uu_cur) * T * T;
+  PA_CHECK(pa_k_flush_x(pv->m, pv->ts, T, pv->d_uu + prev, pv->d_akeep + prev, pv->buf_v[1], pv->d_X));
+  pv->x_pending = 0;
+  ++g_x_flushes;
   return 0;
 }
 
@@ -912,6 +931,7 @@ int preAlps_ECGIterate(preAlps_ECG_t* ecg, int* rci_request) {
 int _preAlps_ECGWrapUp(preAlps_ECG_t* ecg, double* solution) {
   ecg_priv_t* pv = priv_of(ecg);
   if (!pv) return PA_FAIL("solver not initialised");
+  if (pa_ecg_flush_x(ecg, pv)) return 1;
   /* x = X * ones (ecg.c:674); the partial sums go through the free Z buffer */
   double* d_sol = pv->d_partials;
   size_t room = pv->lay.rtr_part - pv->lay.partials;
@@ -932,6 +952,7 @@ void _preAlps_ECGFree(preAlps_ECG_t* ecg) {
     if (pv->d_bj_parts) pa_k_bj_gram_disarm(pv->d_bj_parts);
     pa_rt_sync();
     pa_rt_free(pv->d_info);
+    pa_rt_free(pv->d_akeep);
     pa_rt_host_free(pv->h_pin);
     pa_rt_host_free(pv->h_pin_i);
     pa_rt_host_free(pv->h_grp);

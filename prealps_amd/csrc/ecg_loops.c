@@ -120,11 +120,18 @@ static int solve_first_step(preAlps_ECG_t* ecg, ecg_priv_t* pv, int ahead, int* 
   double tg = pa_wtime(), t0;
   if (!pv->sf_ready && sf_queue_solve(ecg, pv)) return 1;
   pv->sf_ready = 0;
+  /* X moves every second pass: a pass that another one of this call follows leaves its update owed, and that one
+   * applies both, in order (pa_ecg_x_mode).  What the debt needs stays put until then: P becomes the raw P_prev, U
+   * is in d_uu and alpha in d_akeep (same slot), and nothing queued in between writes any of the three. */
+  const int xm = pa_ecg_x_mode(pv->x_defer, pv->x_pending, ahead);
+  const size_t cur = (size_t)pv->uu_cur * T * T, prev = (size_t)(1 - pv->uu_cur) * T * T;
   TIC(PA_T_UPDATE);
-  PA_CHECK(pa_k_update_xrz(pv->m, pv->ts, t, pv->d_mu, pv->d_alpha, ecg->P->val, ecg->AP->val, pv->buf_v[1], pv->d_X,
-                           pv->d_R, pv->buf_z, pv->d_rtr_part, &nb, pv->d_uu + (size_t)pv->uu_cur * T * T, pv->d_beta,
-                           ecg->beta->info.lda, pv->d_uu + (size_t)(1 - pv->uu_cur) * T * T));
+  PA_CHECK(pa_k_update_xrz_mode(pv->m, pv->ts, t, pv->d_mu, pv->d_alpha, ecg->P->val, ecg->AP->val, pv->buf_v[1], pv->d_X,
+                                pv->d_R, pv->buf_z, pv->d_rtr_part, &nb, pv->d_uu + cur, pv->d_beta, ecg->beta->info.lda,
+                                pv->d_uu + prev, xm, pv->d_akeep + (xm == PA_ECG_X_BOTH ? prev : cur)));
   TAC(PA_T_UPDATE, trsm_t);
+  if (xm == PA_ECG_X_SKIP) pa_ecg_x_owed(pv);
+  else pv->x_pending = 0;
   pv->rtr_nblk = nb;
   if (pa_ecg_queue_group_norms(ecg, pv, NULL)) return 1;      /* (never pv->ride: solve_first_applies) */
   pv->uu_cur ^= 1;
@@ -140,7 +147,9 @@ static int solve_first_step(preAlps_ECG_t* ecg, ecg_priv_t* pv, int ahead, int* 
   if (preAlps_BlockOperator(ecg->P, ecg->AP)) return 1;
   if (ahead && sf_queue_solve(ecg, pv)) return 1;
   ecg->tot_t += pa_wtime() - tg;
-  return pa_ecg_stopping_end(ecg, pv, stop);
+  if (pa_ecg_stopping_end(ecg, pv, stop)) return 1;
+  /* a stop (tolerance, maxIter, NaN): no pass follows that would pay what this one may owe to X */
+  return *stop == 1 ? pa_ecg_flush_x(ecg, pv) : 0;
 }
 
 /* one entry of the histories after a stopping test */
@@ -270,6 +279,8 @@ static int solve_in_own_loop(preAlps_ECG_t* ecg, double* rhs, double* sol, doubl
                              int max_hist, int* n_hist, const multi_args_t* mu) {
   pa_ecg_enter_own_loop();
   int rc = ecg_solve_loop(ecg, rhs, sol, res_hist, bs_hist, max_hist, n_hist, mu);
+  ecg_priv_t* pv = priv_of(ecg);      /* (NULL where the loop has released the solver) */
+  if (!rc && pv) rc = pa_ecg_flush_x(ecg, pv);
   pa_ecg_leave_own_loop();
   return rc;
 }
@@ -431,6 +442,8 @@ static int restart(preAlps_ECG_t* ecg, double* rhs, int* rci_request, int* resta
   if (restarts) ++*restarts;
   if (last_iters) *last_iters = ecg->iter;
   if (last_res) *last_res = ecg->res;
+  ecg_priv_t* pv = priv_of(ecg);
+  if (pv && pa_ecg_flush_x(ecg, pv)) return 1;      /* (the stop has paid already: the reset must find nothing owed) */
   if (_preAlps_ECGReset(ecg, rhs, rci_request)) return 1;
   if (preAlps_BlockJacobiApply(ecg->R, ecg->P)) return 1;
   if (!fused && preAlps_BlockOperator(ecg->P, ecg->AP)) return 1;
@@ -516,6 +529,7 @@ int preAlps_ECGAdvance(preAlps_ECG_t* ecg, double* rhs, int* rci_request, int ns
                    "(use preAlps_ECGSolveMulti or the caller's own loop)", pvm->nrhs);
   pa_ecg_enter_own_loop();
   int rc = ecg_advance_loop(ecg, rhs, rci_request, nsteps, restarts, last_iters, last_res);
+  if (!rc && pvm) rc = pa_ecg_flush_x(ecg, pvm);
   pa_ecg_leave_own_loop();
   return rc;
 }

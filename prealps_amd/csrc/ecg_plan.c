@@ -90,3 +90,8 @@ int pa_ecg_solve_first_rule(int on, int nprocs, int ortho_alg, int bs_red, int e
   return on && nprocs == 1 && ortho_alg == PA_ECG_ORTHODIR && bs_red == PA_ECG_NO_BS_RED && enlFac == 4 && fuse &&
          lazy_norm && lazy_stop && bj_gram && spmm_gram && !graphs;
 }
+
+int pa_ecg_x_mode(int on, int pending, int another_step_follows) {
+  if (pending) return PA_ECG_X_BOTH;      /* (whatever the switch says now: a debt is paid) */
+  return on && another_step_follows ? PA_ECG_X_SKIP : PA_ECG_X_EVERY;
+}

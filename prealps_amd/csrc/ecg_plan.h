@@ -57,4 +57,15 @@ void pa_ecg_switches(const pa_ecg_switch_in_t* in, pa_ecg_switch_t* out);
 int pa_ecg_solve_first_rule(int on, int nprocs, int ortho_alg, int bs_red, int enlFac, int fuse, int lazy_norm,
                             int lazy_stop, int bj_gram, int spmm_gram, int graphs);
 
+/* What a row pass of solve_first_step does with X (the values are the kernel's: pa_k_update_xrz_mode).  on: the
+ * switch PREALPS_ECG_X_DEFER; pending: the pass before this one left its update of X owed; another_step_follows: this
+ * call of the library's loop queues another row pass behind this one unless the iteration stops.
+ *   pending                    -> BOTH: the owed update and this one (the caller clears pending);
+ *   on, another step follows   -> SKIP: X stays where it is (the caller sets pending);
+ *   otherwise                  -> EVERY.
+ * So no two passes in a row skip, a pass that may be the call's last owes nothing, and a debt is left only by a stop
+ * (which pa_k_flush_x pays before anything else can look at X). */
+enum { PA_ECG_X_EVERY = 0, PA_ECG_X_SKIP = 1, PA_ECG_X_BOTH = 2 };
+int pa_ecg_x_mode(int on, int pending, int another_step_follows);
+
 #endif

@@ -79,6 +79,14 @@ typedef struct {
    * solve_first_step; PREALPS_ECG_SOLVE_FIRST, read at reset).  sf_ready: the block solve and the finish of the
    * next iteration are queued behind its product (only inside one call of those loops, see solve_first_step). */
   int solve_first, sf_ready;
+  /* X every second row pass (solve_first_step only; PREALPS_ECG_X_DEFER, read at reset; the rule: pa_ecg_x_mode).
+   * x_pending: the last row pass left X as it was and owes it x += (p U^-1) alpha -- that P is the raw panel in
+   * buf_v[1] now, its factor is d_uu's previous slot, and its alpha is in the same slot of d_akeep (an allocation of
+   * its own, two t x t blocks indexed like d_uu: the next finish overwrites d_alpha).  INVARIANT: nothing is owed
+   * whenever anything but the next row pass may touch X -- pa_ecg_flush_x pays on a stop, and is called again, for
+   * nothing, before every reader of X and on every way out of the library's loops. */
+  int x_defer, x_pending;
+  double* d_akeep;
   int phase;          /* iterations since the last reset, mod 6 */
   void* graph[2][6];
   unsigned char seen[2][6];
@@ -157,6 +165,8 @@ int pa_ecg_stopping_queue(preAlps_ECG_t* ecg, ecg_priv_t* pv);
 int pa_ecg_stopping_begin(preAlps_ECG_t* ecg, ecg_priv_t* pv);
 int pa_ecg_stopping_end(preAlps_ECG_t* ecg, ecg_priv_t* pv, int* stop);
 int pa_ecg_shift_directions(preAlps_ECG_t* ecg, ecg_priv_t* pv, int ncopy);
+void pa_ecg_x_owed(ecg_priv_t* pv);                        /* a row pass skipped X: sets x_pending, counts */
+int pa_ecg_flush_x(preAlps_ECG_t* ecg, ecg_priv_t* pv);    /* pays what is owed to X, if anything (pa_k_flush_x) */
 /* ---- ecg_start.c ---- */
 int pa_ecg_start_systems(const char* who, preAlps_ECG_t* ecg, int nrhs, const double* rhs, int ldrhs,
                          const double* x0, int ldx0, int* rci_request, const sys_in_t* sys);

@@ -348,6 +348,7 @@ int preAlps_ECGInitializeGuess(preAlps_ECG_t* ecg, int nrhs, const double* rhs, 
 int preAlps_ECGSystemResiduals(preAlps_ECG_t* ecg, double* sys_res, double* sys_normb) {
   ecg_priv_t* pv = priv_of(ecg);
   if (!pv) return PA_FAIL("solver not initialised");
+  if (pa_ecg_flush_x(ecg, pv)) return 1;
   if (pv->nrhs > 1 || pv->metric) {
     for (int j = 0; j < (pv->nrhs > 1 ? pv->nrhs : 1); ++j) {
       if (sys_res) sys_res[j] = pv->sys_res[j];
@@ -366,6 +367,7 @@ int preAlps_ECGFinalizeMulti(preAlps_ECG_t* ecg, double* sol, int ldsol) {
   if (!sol) return PA_FAIL(" wrong test 'sol != NULL'");
   if (ldsol < pv->m) return PA_FAIL("ldsol = %d is smaller than the %d local rows", ldsol, pv->m);
   if (pv->nrhs <= 1) return preAlps_ECGFinalize(ecg, sol);
+  if (pa_ecg_flush_x(ecg, pv)) return 1;
   /* one pass over X, k sums per row, one copy to the host */
   const int m = pv->m, k = pv->nrhs;
   const size_t need = (size_t)m * k, room = pv->lay.rtr_part - pv->lay.partials;
@@ -394,6 +396,7 @@ int preAlps_ECGFinalizeMulti(preAlps_ECG_t* ecg, double* sol, int ldsol) {
 int pa_ecg_finish_system(preAlps_ECG_t* ecg, const multi_args_t* mu, int as_x0) {
   ecg_priv_t* pv = priv_of(ecg);
   if (!pv) return PA_FAIL("solver not initialised");
+  if (pa_ecg_flush_x(ecg, pv)) return 1;
   const pa_operator_info_t* op = pa_operator_info();
   const sys_in_t* in = mu->sys;
   const int m = pv->m, k = pv->nrhs > 1 ? pv->nrhs : 1, s = pv->sgrp;

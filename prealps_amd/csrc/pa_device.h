@@ -215,6 +215,15 @@ int pa_k_trsm_update(int m, int ts, int t, int nc, double* U, double* alpha, dou
 int pa_k_update_xrz(int m, int ts, int t, double* U, double* alpha, const double* P, const double* AP,
                     const double* P_prev, double* X, double* R, double* Z, double* rtr_partials, int* nblk,
                     double* ukeep, const double* beta, int ldb, const double* uprev);
+/* The same pass with a choice of what happens to X (nobody reads X between two row passes of one call of the library's
+ * loops).  xmode 0: pa_k_update_xrz.  1: X is neither read nor written -- the update is owed -- and alpha is kept in
+ * akeep (t x t), as U is in ukeep.  2: the update owed by the pass before (P_prev, uprev and the alpha in akeep) and
+ * then this one's, two additions to every x in that order: the bits of two passes of mode 0.  pa_k_flush_x: the owed
+ * update alone, X += (P_prev uprev^-1) akeep, for a debt that no pass of mode 2 will pay. */
+int pa_k_update_xrz_mode(int m, int ts, int t, double* U, double* alpha, const double* P, const double* AP,
+                         const double* P_prev, double* X, double* R, double* Z, double* rtr_partials, int* nblk,
+                         double* ukeep, const double* beta, int ldb, const double* uprev, int xmode, double* akeep);
+int pa_k_flush_x(int m, int ts, int t, const double* uprev, const double* akeep, const double* P_prev, double* X);
 /* Standalone sums of R(:,c)^2 (same layout as above). */
 int pa_k_colnorm2(int m, int ts, const double* R, double* rtr_partials, int* nblk);
 /* res2[0] = sum over blocks and columns c < nc; res2[1] = *info (0 if info is NULL). */
