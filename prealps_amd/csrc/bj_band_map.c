@@ -59,7 +59,7 @@ int pa_bj_band_map_build(const pa_bj_band_map_in_t* in, pa_bj_band_map_t* map) {
   for (int q = 0; q < np && !rc; ++q) {
     map->boff[q] = btot;
     if (in->is_nd[q]) continue;
-    const long long len = (long long)in->nrows[q] * ((long long)in->bw[q] + 1);
+    const long long len = pa_bj_band_len(in->nrows[q], in->bw[q], 0);
     if (len >= (1LL << 32)) { map->bad_block = q; rc = -2; break; }
     btot += len;
     if (in->nrows[q] > bmax) bmax = in->nrows[q];

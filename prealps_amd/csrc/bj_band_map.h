@@ -45,6 +45,10 @@ typedef struct {
   int bad_block;           /* after -2 / -3: the block that was refused */
 } pa_bj_band_map_t;
 
+/* The one statement of a band's length: nrows * (bw + 1) doubles, none for a sparse-factored block (bj_build.c
+ * lays out the bands of the create by it, bj_band_map.c those of the refresh). */
+static inline long long pa_bj_band_len(int nrows, int bw, int is_nd) { return is_nd ? 0 : (long long)nrows * ((long long)bw + 1); }
+
 /* Returns 0, -1 when out of memory, -2 when a block's band has 2^32 entries or more, -3 when an entry of a
  * block lies outside its band (bw is not the bandwidth of order); bad_block names the block.  The map is empty
  * after a failure. */
