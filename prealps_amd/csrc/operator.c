@@ -28,6 +28,7 @@
 #include "op_build.h"
 #include "pa_alloc.h"
 #include "spmm_plan.h"
+#include "spmm_code.h"
 #include "spmm_pack.h"
 
 typedef struct {
@@ -75,6 +76,12 @@ typedef struct {
   size_t pk_nalloc;         /* elements of the packed array as allocated */
   int plan_pack_sw;         /* PREALPS_SPMM_PACK as the current plan was cut under */
   int val32_owed;           /* the copy was refused after new values while 32 stays in force: the next product forms it or fails */
+  /* the 2-byte codes of the packed array and their per-block tables (spmm_code.h), beside plan.val, which stays */
+  int plan_code_sw;         /* PREALPS_SPMM_CODE as the current plan was cut under (-1: the rule decides) */
+  int code_blocks;          /* coded blocks */
+  size_t code_entries;      /* table entries of all blocks */
+  double code_stream_bytes; /* bytes of matrix data one product streams from the coded plan */
+  int recodes;              /* updates of the values that formed the codes anew */
   unsigned* d_vmap;    /* device: stored value -> panel entry + 1, 0 = padding (plan_val_n entries; NULL: not cut yet) */
   int values_epoch;    /* 0 after a build, + 1 per update */
   int vmap_builds;     /* value maps cut for this operator */
@@ -103,11 +110,19 @@ static int env_int(const char* name, int dflt) {
 }
 
 /* --------------------------------------------------------------- free ---- */
+static void free_codes(pa_operator_t* o) {
+  pa_rt_free((void*)o->plan.code); pa_rt_free((void*)o->plan.code_tab); pa_rt_free((void*)o->plan.blk_tab_off);
+  o->plan.code = NULL; o->plan.code_tab = NULL; o->plan.blk_tab_off = NULL;
+  o->plan.coded = 0; o->plan.code_lds = 0;
+  o->code_blocks = 0; o->code_entries = 0; o->code_stream_bytes = 0.0;
+}
+
 static void free_plan(pa_operator_t* o) {
   for (int i = 0; i < PA_PL_COUNT; ++i) { pa_rt_free(o->d_plan[i]); o->d_plan[i] = NULL; }
   o->plan_ts = 0;
   pa_rt_free((void*)o->plan.pk_meta);
   pa_rt_free((void*)o->plan.val32);
+  free_codes(o);
   memset(&o->plan, 0, sizeof(o->plan));
   o->pk_nalloc = 0; o->val32_owed = 0;
   ++g_plan_epoch;
@@ -180,6 +195,48 @@ static int upload_plan(pa_operator_t* o, const pa_spmm_host_plan_t* hp, const pa
     g_dbg_val_bytes = pk ? pk->nval_alloc * sizeof(double) : hp->a[PA_PL_VAL].n_alloc * hp->a[PA_PL_VAL].elem;
     g_dbg_slot_bytes = hp->a[PA_PL_COL16].n_alloc * hp->a[PA_PL_COL16].elem;
   }
+  return 0;
+}
+
+/* ---- the packed values as 2-byte codes (spmm_code.h) ----
+ * A packed run plan at 2 or 4 columns with fp64 storage is coded when that takes a tenth off what the packed plan
+ * streams: matrices assembled from one element matrix (Q1 elasticity: a few dozen distinct values per block).
+ * PREALPS_SPMM_CODE=0 never codes, =1 codes every block that fits whatever it saves.  The codes go into device arrays
+ * of their own; the old ones go only when the new ones are up.  A plan the rule leaves alone holds no codes. */
+static int code_plan(pa_operator_t* o, const pa_spmm_host_plan_t* hp, const pa_spmm_pack_t* pk, int ts, int bits) {
+  const int sw = o->plan_code_sw;
+  if (sw == 0 || bits != 64 || (ts != 2 && ts != 4) || !hp->runs || hp->runs_cols != ts) {
+    if (o->plan.coded) { free_codes(o); ++g_plan_epoch; }
+    return 0;
+  }
+  pa_spmm_code_t cd;
+  int crc = pa_spmm_code_build(pk, (const int*)hp->a[PA_PL_BLK_SLICE].p, hp->nblk, (const long long*)hp->a[PA_PL_SL_OFF].p,
+                               (const int*)hp->a[PA_PL_SL_ROW0].p, (const int*)hp->a[PA_PL_SL_NROWS].p,
+                               (const int*)hp->a[PA_PL_BLK_EXT_OFF].p, hp->runs, ts, 32768, &cd);
+  if (crc == -1) return PA_FAIL("out of host memory for the codes of the SpMM plan");
+  const double packed_stream = hp->stream_bytes - pk->unpacked_bytes + pk->packed_bytes;
+  const double coded_stream = hp->stream_bytes - pk->unpacked_bytes + cd.coded_bytes;
+  const int code = crc == 0 && cd.ncoded > 0 && (sw > 0 || coded_stream < 0.9 * packed_stream);
+  if (!code) {
+    pa_spmm_code_free(&cd);
+    if (o->plan.coded) { free_codes(o); ++g_plan_epoch; }
+    return 0;
+  }
+  void* d_code = pa_rt_malloc(cd.ncode * sizeof(uint16_t));
+  void* d_tab = pa_rt_malloc((cd.ntab ? cd.ntab : 1) * sizeof(double));
+  void* d_off = pa_rt_malloc(((size_t)cd.nblk + 1) * sizeof(int));
+  if (!d_code || !d_tab || !d_off || pa_rt_h2d(d_code, cd.code, cd.ncode * sizeof(uint16_t)) ||
+      pa_rt_h2d(d_tab, cd.tab, cd.ntab * sizeof(double)) || pa_rt_h2d(d_off, cd.blk_tab_off, ((size_t)cd.nblk + 1) * sizeof(int))) {
+    pa_rt_free(d_code); pa_rt_free(d_tab); pa_rt_free(d_off);
+    pa_spmm_code_free(&cd);
+    return PA_FAIL("uploading the codes of the SpMM plan failed: %s", pa_rt_error());
+  }
+  free_codes(o);
+  o->plan.code = (const unsigned short*)d_code; o->plan.code_tab = (const double*)d_tab; o->plan.blk_tab_off = (const int*)d_off;
+  o->plan.code_lds = cd.lds_bytes; o->plan.coded = 1;
+  o->code_blocks = cd.ncoded; o->code_entries = cd.ntab; o->code_stream_bytes = coded_stream;
+  ++g_plan_epoch;
+  pa_spmm_code_free(&cd);
   return 0;
 }
 
@@ -273,10 +330,13 @@ static int build_plan(pa_operator_t* o, int ts) {
     packed = prc == 0 && (pack_sw > 0 || bits == 32 || hp.stream_bytes - pk.unpacked_bytes + pk.packed_bytes < 0.9 * hp.stream_bytes);
     if (prc == 0 && !packed) pa_spmm_pack_free(&pk);
   }
+  o->plan_code_sw = env_int("PREALPS_SPMM_CODE", -1);
   int rc = upload_plan(o, &hp, packed ? &pk : NULL);
+  if (rc) PA_FAIL("uploading the SpMM plan failed: %s", pa_rt_error());
+  else if (packed) rc = code_plan(o, &hp, &pk, ts, bits);
   if (packed) pa_spmm_pack_free(&pk);
   pa_spmm_plan_free(&hp);
-  if (rc) return PA_FAIL("uploading the SpMM plan failed: %s", pa_rt_error());
+  if (rc) { free_plan(o); return 1; }
   o->plan_ts = ts;
   if (packed && bits == 32 && form_val32(o)) { free_plan(o); return 1; }
   return 0;
@@ -802,6 +862,7 @@ int pa_operator_plan_epoch(void) { return g_plan_epoch; }
  * packed, when 32 comes into force; every other plan is left alone.  A refusal leaves the setting as it was, and the
  * plan too -- but for an unpacked run plan whose new cut failed: that plan is gone, and the next product cuts it again
  * under the old setting. */
+static int recode_plan(pa_operator_t* o);
 int preAlps_hip_set_operator_precision(int bits) {
   pa_operator_t* o = &g_op;
   if (bits != 0 && bits != 32 && bits != 64)
@@ -816,9 +877,15 @@ int preAlps_hip_set_operator_precision(int bits) {
   if (want != 32) o->val32_owed = 0;      /* (a copy that an update could not form is no longer wanted) */
   if ((want == 32) == (pl->val32 != NULL)) return 0;
   if (pa_rt_sync()) { g_op_bits = before; return PA_FAIL("%s", pa_rt_error()); }   /* products in flight read the plan */
-  if (want == 64) { drop_val32(o); return 0; }
+  if (want == 64) {
+    drop_val32(o);
+    /* (fp64 again: the codes, which went when the float copy came, are formed anew where the rule holds) */
+    if (pl->packed && !pl->coded && o->plan_code_sw != 0 && (o->plan_ts == 2 || o->plan_ts == 4)) return recode_plan(o);
+    return 0;
+  }
   if (!pl->runs || pl->runs_cols != o->plan_ts || o->plan_ts > 4 || o->plan_pack_sw == 0) return 0;
   if (pl->packed ? form_val32(o) : build_plan(o, o->plan_ts)) { g_op_bits = before; o->val32_owed = 0; return 1; }
+  if (o->plan.coded) { free_codes(o); ++g_plan_epoch; }      /* (no codes beside the float copy) */
   return 0;
 }
 
@@ -886,7 +953,41 @@ static int repack_plan(pa_operator_t* o) {
     drop_val32(o);
     o->pk_nalloc = pk.nval_alloc;
     if (had32) rc = form_val32(o);
+    /* the codes of the old array do not fit the new one: formed anew where the rule still holds, else dropped */
+    const int was_coded = o->plan.coded;
+    if (was_coded) { free_codes(o); ++g_plan_epoch; }
+    if (!rc && !o->plan.val32) {
+      rc = code_plan(o, &hp, &pk, o->plan_ts, operator_bits());
+      if (!rc && (was_coded || o->plan.coded)) ++o->recodes;
+    }
   }
+  pa_spmm_pack_free(&pk);
+  pa_spmm_plan_free(&hp);
+  return rc;
+}
+
+/* The codes of the packed array as it stands on the device, anew: the plan a build would cut for the host panel,
+ * packed and coded on the host (the path of repack_plan), the codes uploaded; the packed array is not touched.  The
+ * caller has made sure that no new value lacks a place (k_pack_set_values), so the fresh pack has the layout of the
+ * array on the device exactly when it keeps as many values; when a kept place now holds +0.0 it keeps fewer, and the
+ * codes are dropped: the products read fp64 until the next build or repack.  (Writing the codes through on the device
+ * would spare the host pass: not done here.) */
+static int recode_plan(pa_operator_t* o) {
+  pa_spmm_plan_in_t pin = plan_input(o, o->plan_ts);
+  pa_spmm_host_plan_t hp;
+  if (pa_spmm_plan_build(&pin, &hp)) { free_codes(o); ++g_plan_epoch; return PA_FAIL("out of host memory for the SpMM plan"); }
+  pa_spmm_pack_t pk;
+  int rc = 0;
+  if (!hp.runs || hp.nslices != o->plan.nslices || hp.a[PA_PL_VAL].n != o->plan_val_n ||
+      pa_spmm_pack_build((const double*)hp.a[PA_PL_VAL].p, (const long long*)hp.a[PA_PL_SL_OFF].p,
+                         (const int*)hp.a[PA_PL_SL_LEN].p, hp.nslices, 0, &pk)) {
+    pa_spmm_plan_free(&hp);
+    free_codes(o); ++g_plan_epoch;
+    return PA_FAIL("the SpMM plan cut for the new values does not fit the plan on the device");
+  }
+  if (pk.nval != o->pk_nval || pk.nval_alloc != o->pk_nalloc) { free_codes(o); ++g_plan_epoch; }
+  else if ((rc = code_plan(o, &hp, &pk, o->plan_ts, operator_bits())) != 0) { free_codes(o); ++g_plan_epoch; }   /* (never stale codes) */
+  if (!rc) ++o->recodes;
   pa_spmm_pack_free(&pk);
   pa_spmm_plan_free(&hp);
   return rc;
@@ -896,7 +997,8 @@ static int repack_plan(pa_operator_t* o) {
  * give, bit for bit, without the build: the host panel is rewritten through o->src, the plan on the device through
  * its value map (k_plan_set_values); every address stays.  Every refusal and every allocation comes before the first
  * write.  A packed run plan (spmm_pack.h) is written through its masks (k_pack_set_values); only when a value that
- * the pack dropped as +0.0 becomes something else are the values packed anew, into new arrays (repack_plan). */
+ * the pack dropped as +0.0 becomes something else are the values packed anew, into new arrays (repack_plan).  A plan
+ * that holds codes (spmm_code.h) gets them anew from the host panel after the write, or loses them (recode_plan). */
 int preAlps_OperatorUpdateValues(const double* val) {
   pa_operator_t* o = &g_op;
   pa_operator_info_t* in = &o->info;
@@ -962,6 +1064,13 @@ int preAlps_OperatorUpdateValues(const double* val) {
     pa_rt_free(d_miss);
     /* the fp32 copy is rounded again from the array just written, in place */
     if (!rc && o->plan.val32 && form_val32(o)) {
+      pa_rt_event_destroy(e0); pa_rt_event_destroy(e1);
+      pa_rt_free(d_pv);
+      return 1;
+    }
+    /* the codes name the old values: anew from the host panel, or gone */
+    if (rc && o->plan.coded) { free_codes(o); ++g_plan_epoch; }
+    if (!rc && o->plan.coded && recode_plan(o)) {
       pa_rt_event_destroy(e0); pa_rt_event_destroy(e1);
       pa_rt_free(d_pv);
       return 1;
@@ -1109,6 +1218,14 @@ int preAlps_hip_get_stat(const char* key, double* value) {
   else if (!strcmp(key, "spmm_precision_stream_bytes"))      /* what one product streams: 4 bytes less per packed value and step zero */
     *value = !o->plan_ts ? 0.0 : o->plan.val32 ? o->pk_stream_bytes - 4.0 * (double)(o->pk_nalloc - PA_SPMM_PACK_SLACK)
                                                : o->plan.packed ? o->pk_stream_bytes : o->stream_bytes;
+  /* (spmm_precision_stream_bytes prices the storage precision alone, as its tests hold it; what a coded product
+   * streams is spmm_coded_stream_bytes) */
+  else if (!strcmp(key, "spmm_coded")) *value = o->plan.coded;      /* the products read 2-byte codes and per-block tables */
+  else if (!strcmp(key, "spmm_coded_blocks")) *value = o->code_blocks;
+  else if (!strcmp(key, "spmm_code_table_entries")) *value = (double)o->code_entries;
+  else if (!strcmp(key, "spmm_coded_stream_bytes")) *value = o->code_stream_bytes;
+  else if (!strcmp(key, "spmm_recodes")) *value = o->recodes;
+  else if (!strcmp(key, "spmm_code_lds_bytes")) *value = o->plan.code_lds;
   else if (!strcmp(key, "spmm_round_kernel_s")) *value = g_round_kernel_s;
   else if (!strcmp(key, "spmm_val_address")) *value = (double)(uintptr_t)o->plan.val;      /* (for the run-to-run spread study) */
   else if (!strcmp(key, "spmm_slot_address")) *value = (double)(uintptr_t)o->plan.col16;

@@ -108,6 +108,15 @@ typedef struct {
   /* non-NULL (packed run plan at up to 4 columns, preAlps_hip_set_operator_precision(32)): `val` rounded to fp32,
    * element for element (pa_k_plan_round_values), read through the same pk_meta in place of `val`; `val` stays */
   const float* val32;
+  /* coded != 0 (packed run plan at 2 or 4 columns, spmm_code.h): `code` holds a 2-byte code per element of `val`,
+   * read through the same pk_meta; code_tab[blk_tab_off[b] + c] is the value of code c in block b.  A block with an
+   * empty table is read from `val`, which stays.  code_lds = LDS bytes of the block that needs most (staging rows,
+   * zero rows, table). */
+  int coded;
+  const unsigned short* code;
+  const double* code_tab;
+  const int* blk_tab_off;
+  int code_lds;
 } pa_spmm_plan_t;
 /* phase 0: interior blocks, 1: halo-reading blocks, 2: all.  exact != 0: read `val` even where val32 is set, and
  * leave every Gram request (pa_k_spmm_gram_arm) as it is. */

@@ -214,15 +214,21 @@ template <int TS> struct spmm_row { static constexpr int stride = TS == 8 ? TS +
 
 // VT: the type the values are held in (float: the fp32 copy of the packed array, widened here -- exactly -- right in
 // front of the FMAs)
+// VT = unsigned short: codes into the block's table of values in LDS (spmm_code.h); tab[code] has the 64 bits the
+// packed array holds at that place, read right in front of the FMAs.
 template <int TS, int RL, typename VT = double>
 __device__ __forceinline__ void spmm_runs_fma(const double* sx, const int (&sl)[spmm_ru<RL>::n],
-                                              const VT (&vv)[RL * spmm_ru<RL>::n], double (&acc)[TS]) {
+                                              const VT (&vv)[RL * spmm_ru<RL>::n], double (&acc)[TS],
+                                              const double* tab = nullptr) {
   constexpr int TSP = spmm_row<TS>::stride;
 #pragma unroll
   for (int j = 0; j < spmm_ru<RL>::n; ++j) {
     const double* __restrict__ xr = sx + (size_t)sl[j] * TSP;
 #pragma unroll
-    for (int i = 0; i < RL; ++i) spmm_fma_row<TS>(acc, (double)vv[RL * j + i], xr + i * TSP);
+    for (int i = 0; i < RL; ++i) {
+      if constexpr (sizeof(VT) == 2) spmm_fma_row<TS>(acc, tab[vv[RL * j + i]], xr + i * TSP);
+      else spmm_fma_row<TS>(acc, (double)vv[RL * j + i], xr + i * TSP);
+    }
   }
 }
 
@@ -250,12 +256,12 @@ __device__ __forceinline__ void spmm_pack_meta(const pk_u64* __restrict__ mp, in
   }
 }
 // VT = float: the fp32 copy of the packed array (k_plan_round_values) behind the same masks and offsets -- element
-// indices, so the lane's byte offset is << 2 and the fetch a 4-byte load.
+// indices, so the lane's byte offset is << 2 and the fetch a 4-byte load.  VT = unsigned short: the codes, << 1.
 template <typename VT>
 __device__ __forceinline__ void spmm_runs_load_pack(const unsigned short* __restrict__ cp, const VT* __restrict__ vpk,
                                                     const spmm_pk& M, unsigned lane, int g, int len, int (&sl)[3],
                                                     VT (&vv)[9]) {
-  constexpr int SH = sizeof(VT) == 8 ? 3 : 2;
+  constexpr int SH = sizeof(VT) == 8 ? 3 : sizeof(VT) == 4 ? 2 : 1;
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
     const int kc = min(g * 3 + j, len - 1);
@@ -285,7 +291,7 @@ __device__ __forceinline__ void spmm_runs_block(
     const int* __restrict__ order, const double* __restrict__ X,
     const double* __restrict__ Xh, double* __restrict__ Y,
     const double* __restrict__ Rg, double* __restrict__ gpart, int gbase, int logical, int coff,
-    const pk_u64* __restrict__ meta);
+    const pk_u64* __restrict__ meta, const double* __restrict__ tabg = nullptr, int ntab = 0);
 
 template <int TS, int XS, bool GRAM, int RL = 3, bool PACK = false, typename VT = double>
 __device__ __forceinline__ void spmm_runs_body(
@@ -311,7 +317,8 @@ __device__ __forceinline__ void spmm_runs_body(
 // One block of slices: `logical` = its place in the launch's list, `coff` = first of the TS columns.
 // PACK: `val` is the packed value array and `meta` its masks and offsets; everything but the value fetch is
 // the same code.  VT = float (PACK only): `val` is the fp32 copy of the packed array; the two register sets hold
-// floats, and the FMAs, their order and the staging are those of VT = double.
+// floats, and the FMAs, their order and the staging are those of VT = double.  VT = unsigned short (PACK only): `val`
+// is the code array and tabg / ntab the block's table (ntab >= 1), which the workgroup copies behind its staging rows.
 template <int TS, int XS, bool GRAM, int RL, bool PACK, typename VT>
 __device__ __forceinline__ void spmm_runs_block(
     int m, const long long* __restrict__ sl_off, const int* __restrict__ sl_len,
@@ -322,10 +329,12 @@ __device__ __forceinline__ void spmm_runs_block(
     const int* __restrict__ order, const double* __restrict__ X,
     const double* __restrict__ Xh, double* __restrict__ Y,
     const double* __restrict__ Rg, double* __restrict__ gpart, int gbase, int logical, int coff,
-    const pk_u64* __restrict__ meta) {
+    const pk_u64* __restrict__ meta, const double* __restrict__ tabg, int ntab) {
   static_assert(!GRAM || (TS == 4 && XS == 4), "the fused Gram block is built for 4-column panels");
   static_assert(!PACK || (RL == 3 && TS == XS && TS <= 4), "the packed values are read by the narrow run kernels");
-  static_assert(PACK || sizeof(VT) == 8, "fp32 values: the packed run plan only");
+  static_assert(PACK || sizeof(VT) == 8, "fp32 values and codes: the packed run plan only");
+  constexpr bool CODE = sizeof(VT) == 2;
+  const double* tab = nullptr;      // CODE: the block's table in LDS
   extern __shared__ double sx[];
   const int b = order[logical];
   const int s0 = blk_slice[b], s1 = blk_slice[b + 1];
@@ -396,6 +405,15 @@ __device__ __forceinline__ void spmm_runs_block(
       for (int it = 0; it < SB; ++it) dst[(size_t)L[it] * HP + j] = v[it];
     }
     if constexpr (RL == 3) { if (tid < 2 * H) dst[(size_t)(nst + tid / H) * HP + tid % H] = make_double2(0.0, 0.0); }    // (a run may reach two rows past the last one)
+    if constexpr (CODE) {
+      // the table behind the two zero rows: unconditional loads, lanes beyond the last entry repeat it
+      double* tl = sx + (size_t)(nst + 2) * (2 * HP);
+      for (int base = 0; base < ntab; base += WG) {
+        const int i = min(base + tid, ntab - 1);
+        tl[i] = tabg[i];
+      }
+      tab = tl;
+    }
   }
   __syncthreads();
   double gw = 0.0, gg = 0.0;      // GRAM: D[i][j] of the lane's 4 x 4 block (lane = 16 i + 4 q + j)
@@ -419,27 +437,27 @@ __device__ __forceinline__ void spmm_runs_block(
           spmm_runs_load_pack(cp, val, pN, lane, 2 * i + 1, len, slB, vB);
           spmm_pack_meta(mp, min(2 * i + 2, ngt - 1), len, pN);
           __builtin_amdgcn_sched_barrier(0);
-          spmm_runs_fma<TS, RL, VT>(sx, slA, vA, acc);
+          spmm_runs_fma<TS, RL, VT>(sx, slA, vA, acc, tab);
           __builtin_amdgcn_sched_barrier(0);
           spmm_runs_load_pack(cp, val, pN, lane, min(2 * i + 2, ngt - 1), len, slA, vA);
           spmm_pack_meta(mp, min(2 * i + 3, ngt - 1), len, pN);
           __builtin_amdgcn_sched_barrier(0);
-          spmm_runs_fma<TS, RL, VT>(sx, slB, vB, acc);
+          spmm_runs_fma<TS, RL, VT>(sx, slB, vB, acc, tab);
           __builtin_amdgcn_sched_barrier(0);
         }
-        if (ngt & 1) spmm_runs_fma<TS, RL, VT>(sx, slA, vA, acc);
+        if (ngt & 1) spmm_runs_fma<TS, RL, VT>(sx, slA, vA, acc, tab);
       } else {
         for (int i = 0; i < (ngt >> 1); ++i) {
           spmm_runs_load<RL>(cp, vp, lane, 2 * i + 1, len, slB, vB);
           __builtin_amdgcn_sched_barrier(0);      // (keeps the requests in front of the sums of the group before)
-          spmm_runs_fma<TS, RL, VT>(sx, slA, vA, acc);
+          spmm_runs_fma<TS, RL, VT>(sx, slA, vA, acc, tab);
           __builtin_amdgcn_sched_barrier(0);
           spmm_runs_load<RL>(cp, vp, lane, min(2 * i + 2, ngt - 1), len, slA, vA);
           __builtin_amdgcn_sched_barrier(0);
-          spmm_runs_fma<TS, RL, VT>(sx, slB, vB, acc);
+          spmm_runs_fma<TS, RL, VT>(sx, slB, vB, acc, tab);
           __builtin_amdgcn_sched_barrier(0);
         }
-        if (ngt & 1) spmm_runs_fma<TS, RL, VT>(sx, slA, vA, acc);
+        if (ngt & 1) spmm_runs_fma<TS, RL, VT>(sx, slA, vA, acc, tab);
       }
     }
     const int nr = sl_nrows[s], row_s = sl_row0[s];
@@ -532,6 +550,65 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(5))) void k_
                                       ext_rows, order, nlist, X, Xh, Y, Rg, gpart, gbase, meta);
 }
 
+// The packed run kernels on 2-byte codes (spmm_code.h).  A block with a table reads `code` through the masks and
+// offsets of the pack and looks the values up in LDS; a block without one (its table did not fit behind its staging
+// rows) reads the packed fp64 array as k_spmm_runs_pack<TS, double> does.  The choice is wavefront-uniform and made
+// once per workgroup.  Same grid, staging and occupancy.
+template <int TS, bool GRAM>
+__device__ __forceinline__ void spmm_runs_body_code(
+    int m, const long long* __restrict__ sl_off, const int* __restrict__ sl_len,
+    const int* __restrict__ sl_row0, const int* __restrict__ sl_nrows,
+    const unsigned short* __restrict__ slot16, const double* __restrict__ val, const unsigned short* __restrict__ code,
+    const double* __restrict__ tabs, const int* __restrict__ blk_tab_off, const pk_u64* __restrict__ meta,
+    const int* __restrict__ blk_slice, const int* __restrict__ blk_ext_off,
+    const int* __restrict__ blk_nlow, const int* __restrict__ ext_rows,
+    const int* __restrict__ order, int nlist, const double* __restrict__ X,
+    const double* __restrict__ Xh, double* __restrict__ Y,
+    const double* __restrict__ Rg, double* __restrict__ gpart, int gbase) {
+  const int cpx = (nlist + 7) >> 3;
+  const int logical = (blockIdx.x & 7) * cpx + (blockIdx.x >> 3);
+  if (logical >= nlist) return;
+  const int b = order[logical];
+  const int t0 = __builtin_amdgcn_readfirstlane(blk_tab_off[b]);
+  const int nt = __builtin_amdgcn_readfirstlane(blk_tab_off[b + 1]) - t0;
+  if (nt > 0)
+    spmm_runs_block<TS, TS, GRAM, 3, true, unsigned short>(m, sl_off, sl_len, sl_row0, sl_nrows, slot16, code, blk_slice,
+                                                           blk_ext_off, blk_nlow, ext_rows, order, X, Xh, Y, Rg, gpart,
+                                                           gbase, logical, 0, meta, tabs + t0, nt);
+  else
+    spmm_runs_block<TS, TS, GRAM, 3, true, double>(m, sl_off, sl_len, sl_row0, sl_nrows, slot16, val, blk_slice,
+                                                   blk_ext_off, blk_nlow, ext_rows, order, X, Xh, Y, Rg, gpart, gbase,
+                                                   logical, 0, meta);
+}
+
+template <int TS>
+__global__ __launch_bounds__(WG, 5) void k_spmm_runs_code(
+    int m, const long long* __restrict__ sl_off, const int* __restrict__ sl_len,
+    const int* __restrict__ sl_row0, const int* __restrict__ sl_nrows,
+    const unsigned short* __restrict__ slot16, const double* __restrict__ val, const unsigned short* __restrict__ code,
+    const double* __restrict__ tabs, const int* __restrict__ blk_tab_off, const pk_u64* __restrict__ meta,
+    const int* __restrict__ blk_slice, const int* __restrict__ blk_ext_off,
+    const int* __restrict__ blk_nlow, const int* __restrict__ ext_rows,
+    const int* __restrict__ order, int nlist, const double* __restrict__ X,
+    const double* __restrict__ Xh, double* __restrict__ Y) {
+  spmm_runs_body_code<TS, false>(m, sl_off, sl_len, sl_row0, sl_nrows, slot16, val, code, tabs, blk_tab_off, meta, blk_slice,
+                                 blk_ext_off, blk_nlow, ext_rows, order, nlist, X, Xh, Y, nullptr, nullptr, 0);
+}
+
+__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(5))) void k_spmm_runs_gram_code(
+    int m, const long long* __restrict__ sl_off, const int* __restrict__ sl_len,
+    const int* __restrict__ sl_row0, const int* __restrict__ sl_nrows,
+    const unsigned short* __restrict__ slot16, const double* __restrict__ val, const unsigned short* __restrict__ code,
+    const double* __restrict__ tabs, const int* __restrict__ blk_tab_off, const pk_u64* __restrict__ meta,
+    const int* __restrict__ blk_slice, const int* __restrict__ blk_ext_off,
+    const int* __restrict__ blk_nlow, const int* __restrict__ ext_rows,
+    const int* __restrict__ order, int nlist, const double* __restrict__ X,
+    const double* __restrict__ Xh, double* __restrict__ Y,
+    const double* __restrict__ Rg, double* __restrict__ gpart, int gbase) {
+  spmm_runs_body_code<4, true>(m, sl_off, sl_len, sl_row0, sl_nrows, slot16, val, code, tabs, blk_tab_off, meta, blk_slice,
+                               blk_ext_off, blk_nlow, ext_rows, order, nlist, X, Xh, Y, Rg, gpart, gbase);
+}
+
 template <int TS>
 __global__ __launch_bounds__(WG) void k_pack_rows(int n, const int* __restrict__ idx,
                                                   const double* __restrict__ X,
@@ -559,12 +636,20 @@ static int launch_spmm(const pa_spmm_plan_t* pl, const int* order, int nlist, co
                        const double* Xh, double* Y, bool exact) {
   if (nlist <= 0) return 0;
   const bool f32 = pl->val32 && !exact;
+  // (the codes are exact: an exact product reads them too; beside a fp32 copy the exact product reads fp64)
+  const bool coded = pl->coded && !pl->val32;
+  if (coded && !(pl->runs && pl->packed && (TS == 2 || TS == 4) && pl->code && pl->code_tab && pl->blk_tab_off &&
+                 pl->code_lds <= 32 * 1024)) {
+    pa_rt_set_error("codes beside a plan that is no packed run plan at 2 or 4 columns, or a table beyond the LDS budget (stride %d, %d bytes)", TS, pl->code_lds);
+    return 1;
+  }
   if (f32 && !(pl->runs && pl->packed && TS <= 4)) {
     pa_rt_set_error("a fp32 copy of the values beside a plan that is no packed run plan at up to 4 columns (stride %d)", TS);
     return 1;
   }
   if constexpr (TS == 4) {
-    const size_t lds = (size_t)pl->stage_cap * TS * 8;
+    size_t lds = (size_t)pl->stage_cap * TS * 8;
+    if (coded && (size_t)pl->code_lds > lds) lds = (size_t)pl->code_lds;      // (staging rows + table of the block that needs most)
     // (an exact product neither serves nor ends a request)
     if (!exact && g_sg.armed && (pl->runs || pl->staged) && lds <= 64 * 1024 && X == g_sg.X && Y == g_sg.Y &&
         g_sg.count >= 0 && g_sg.count + nlist <= g_sg.cap) {
@@ -576,6 +661,11 @@ static int launch_spmm(const pa_spmm_plan_t* pl, const int* order, int nlist, co
                   pl->sl_len, pl->sl_row0, pl->sl_nrows, pl->col16, pl->val32, pl->pk_meta, pl->blk_slice,
                   pl->blk_ext_off, pl->blk_nlow, pl->ext_rows, order, nlist, X, Xh, Y, g_sg.R, g_sg.partials,
                   g_sg.count);
+      else if (pl->runs && pl->packed && coded)
+        PA_LAUNCH(k_spmm_runs_gram_code, dim3(cpx * 8), dim3(WG), lds_gram, cur_stream(), pl->m, pl->sl_off,
+                  pl->sl_len, pl->sl_row0, pl->sl_nrows, pl->col16, pl->val, pl->code, pl->code_tab, pl->blk_tab_off,
+                  pl->pk_meta, pl->blk_slice, pl->blk_ext_off, pl->blk_nlow, pl->ext_rows, order, nlist, X, Xh, Y,
+                  g_sg.R, g_sg.partials, g_sg.count);
       else if (pl->runs && pl->packed)
         PA_LAUNCH(k_spmm_runs_gram_pack<double>, dim3(cpx * 8), dim3(WG), lds_gram, cur_stream(), pl->m, pl->sl_off,
                   pl->sl_len, pl->sl_row0, pl->sl_nrows, pl->col16, pl->val, pl->pk_meta, pl->blk_slice,
@@ -612,8 +702,17 @@ static int launch_spmm(const pa_spmm_plan_t* pl, const int* order, int nlist, co
   }
   if (pl->runs && pl->packed) {       // the value array without its zeros: the narrow run kernel reads it
     if constexpr (TS <= 4) {
-      const size_t lds = (size_t)pl->stage_cap * TS * 8;
+      size_t lds = (size_t)pl->stage_cap * TS * 8;
       const int cpx = (nlist + 7) / 8;
+      if constexpr (TS == 2 || TS == 4) {
+        if (coded) {
+          if ((size_t)pl->code_lds > lds) lds = (size_t)pl->code_lds;
+          PA_LAUNCH((k_spmm_runs_code<TS>), dim3(cpx * 8), dim3(WG), lds, cur_stream(), pl->m, pl->sl_off, pl->sl_len,
+                    pl->sl_row0, pl->sl_nrows, pl->col16, pl->val, pl->code, pl->code_tab, pl->blk_tab_off, pl->pk_meta,
+                    pl->blk_slice, pl->blk_ext_off, pl->blk_nlow, pl->ext_rows, order, nlist, X, Xh, Y);
+          return kfail("k_spmm_runs_code");
+        }
+      }
       if (f32)
         PA_LAUNCH((k_spmm_runs_pack<TS, float>), dim3(cpx * 8), dim3(WG), lds, cur_stream(), pl->m, pl->sl_off,
                   pl->sl_len, pl->sl_row0, pl->sl_nrows, pl->col16, pl->val32, pl->pk_meta, pl->blk_slice,
