@@ -187,3 +187,164 @@ def test_gram_finish_refusal_is_reported_and_harmless(panels):
     finally:
         for d in bufs:
             L.pa_rt_free(d)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The paths the plain calls above do not take: the factor and alpha formed inside k_trsm_update (gram != NULL), the
+# lazy coefficients of k_update_z, Z^T Z as its by-product, the packing of the send rows.  Through the pa_k_*
+# launchers on raw device buffers (dense_dev.py), against dense_ref.py's longdouble references within their derived
+# bounds (test_dense_ref_cpu.py); every test prints its worst ratio to the bound (pytest -s).
+import dense_ref as D
+from dense_dev import Dev
+
+
+@pytest.fixture
+def dev():
+    d = Dev()
+    yield d
+    d.close()
+
+
+@pytest.mark.parametrize("keep", [0, 1])
+@pytest.mark.parametrize("m", [5, 10007])
+@pytest.mark.parametrize("ts,t", [(2, 2), (4, 3), (4, 4), (8, 7), (8, 8), (16, 15), (16, 16)])
+def test_trsm_update_from_gram(dev, m, ts, t, keep):
+    """gram = [W ; G^T] on the device: workgroup 0 writes U = chol(W) and alpha = U^-T G (backward error), every row
+    is updated with them; with ukeep P and AP stay raw and the factor is kept."""
+    import os
+    assert "PREALPS_TRSM_MFMA" not in os.environ
+    nc = t
+    rng = np.random.default_rng(m + 17 * t + ts + keep)
+    P, AP, X, R = (D.panel(rng, m, ts) for _ in range(4))
+    A = rng.standard_normal((4 * t, t))
+    W, G = A.T @ A, rng.standard_normal((t, nc))
+    dP, dAP, dX, dR = (dev.up(a) for a in (P, AP, X, R))
+    dgram = dev.upf(np.vstack([W, G.T]))
+    dU, dalpha, dinfo, dkeep = dev.zeros(t * t * 8), dev.zeros(t * nc * 8), dev.up(np.array([4, 0], dtype=np.int32)), dev.zeros(t * t * 8)
+    drtr = dev.zeros(512 * ts * 8)
+    nblk = C.c_int(0)
+    rc = dev.L.pa_k_trsm_update(m, ts, t, nc, dU, dalpha, dP, dAP, dX, dR, drtr, C.byref(nblk), 0, None, dinfo, None,
+                                dgram, dkeep if keep else None)
+    assert rc == 0, dev.error()
+    assert dev.down(dinfo, (2,), np.int32)[0] == 0
+    Ufull, alpha = dev.downf(dU, t, t), dev.downf(dalpha, t, nc)
+    U = np.triu(Ufull)
+    assert np.all(np.diag(U) > 0)
+    zero = np.zeros((t, t))
+    r = max(D.chol_backward(U, W, zero, t), D.alpha_backward(U, alpha, G, np.zeros((t, nc)), t))
+    ref = D.trsm_update(P, AP, X, R, U, alpha, t, nc)
+    bnd = D.trsm_update_bound(P, AP, X, R, U, alpha, t, nc, ts >= 8)
+    got = [dev.down(d, (m, ts)) for d in (dP, dAP, dX, dR)]
+    if keep:
+        assert got[0].tobytes() == P.tobytes() and got[1].tobytes() == AP.tobytes()
+        assert dev.downf(dkeep, t, t).tobytes() == Ufull.tobytes()
+        r = max(r, D.ratio(got[2], ref[2], bnd[2]), D.ratio(got[3], ref[3], bnd[3]))
+    else:
+        r = max([r] + [D.ratio(g, rf, b) for g, rf, b in zip(got, ref, bnd)])
+    print("trsm_update from gram m=%d ts=%d t=%d keep=%d: worst ratio %.3g" % (m, ts, t, keep, r))
+    assert r <= 1.0
+
+
+def _lazy_cases():
+    for ts in (2, 4, 8, 16):
+        for t in sorted({1, ts - 1, ts}):
+            for a_hi in (0, t):
+                yield ts, t, a_hi
+
+
+@pytest.mark.parametrize("m", [7, 4099])
+@pytest.mark.parametrize("ts,t,a_hi", list(_lazy_cases()))
+def test_update_z_lazy(dev, m, ts, t, a_hi):
+    """ucur / uprev given: Z' = Z Ui - V0 Ui (Ui^T G1 Ui) - V1 Up (Up^T G2 Ui) from the raw panels and Gram blocks."""
+    rng = np.random.default_rng(m + 100 * ts + 10 * t + a_hi)
+    Z, V0, V1 = D.panel(rng, m, ts), D.panel(rng, m, ts), D.panel(rng, m, ts)
+    U, Up = D.factor(rng, t), D.factor(rng, t)
+    beta = rng.standard_normal((t + a_hi, t))
+    ldb = t + a_hi + 1
+    dZ, dV0, dV1 = dev.up(Z), dev.up(V0), dev.up(V1)
+    dbeta, dU, dUp = dev.upf(beta, ldb), dev.upf(U), dev.upf(Up)
+
+    def call(nc):
+        return dev.L.pa_k_update_z(m, ts, t, a_hi, nc, dbeta, ldb, dV0, dV1 if a_hi else None, dZ, None, None, dU, dUp,
+                                   None, 0, None)
+
+    if t > 1:
+        assert call(t - 1) == 1
+        assert "square blocks" in dev.error()
+        assert dev.down(dZ, (m, ts)).tobytes() == Z.tobytes()
+    assert call(t) == 0, dev.error()
+    V1r = V1 if a_hi else None
+    r = D.ratio(dev.down(dZ, (m, ts)), D.lazy_update_z(Z, V0, V1r, U, Up, beta, t),
+                D.lazy_update_z_bound(Z, V0, V1r, U, Up, beta, t))
+    for d, a in ((dV0, V0), (dV1, V1)):
+        assert dev.down(d, (m, ts)).tobytes() == a.tobytes()
+    print("update_z lazy m=%d ts=%d t=%d a_hi=%d: ratio %.3g" % (m, ts, t, a_hi, r))
+    assert r <= 1.0
+
+
+@pytest.mark.parametrize("m", [7, 4099])
+@pytest.mark.parametrize("ts", [8, 16])
+@pytest.mark.parametrize("less", [3, 0])
+def test_update_z_leaves_ztz(dev, m, ts, less):
+    """zz_part (8 / 16 columns, not lazy): one ts x ts block of Z'^T Z' per workgroup, summed by pa_k_finish."""
+    zc = ts - less
+    rng = np.random.default_rng(m + ts + less)
+    Z, V0, V1 = D.panel(rng, m, ts), D.panel(rng, m, ts), D.panel(rng, m, ts)
+    beta = rng.standard_normal((2 * ts, ts))
+    dZ, dV0, dV1, dbeta = dev.up(Z), dev.up(V0), dev.up(V1), dev.upf(beta)
+    dzz = dev.zeros(dev.L.pa_gram_max_blocks() * 2 * ts * ts * 8)      # (a Gram buffer: pa_k_finish's shares lie behind the blocks)
+    dout = dev.zeros(zc * zc * 8)
+    nblk = C.c_int(-1)
+    rc = dev.L.pa_k_update_z(m, ts, ts, ts, ts, dbeta, 2 * ts, dV0, dV1, dZ, None, None, None, None, dzz, zc, C.byref(nblk))
+    assert rc == 0, dev.error()
+    assert nblk.value == min(2048, -(-m // 1024))
+    assert dev.L.pa_k_finish(dzz, nblk.value, 1, ts, zc, 0, zc, dout, zc) == 0, dev.error()
+    V = np.hstack([V0, V1])
+    Zn = D.update_z(Z, V, beta, ts)
+    Za, cz = D.update_z_abs(Z, V, beta, ts)
+    r = D.ratio(dev.down(dZ, (m, ts)), Zn, (cz + D.SPARE) * D.UNIT * Za)
+    r2 = D.ratio(dev.downf(dout, zc, zc), D.gram(Zn[:, :zc], Zn[:, :zc]),
+                 D.gram_bound(Za[:, :zc], Za[:, :zc], c_in=2 * cz + D.SPARE))
+    print("update_z with Z^T Z m=%d ts=%d cols=%d: Z %.3g, Z^T Z %.3g" % (m, ts, zc, r, r2))
+    assert max(r, r2) <= 1.0
+
+
+@pytest.mark.parametrize("lazy", [0, 1])
+@pytest.mark.parametrize("m", [7, 4099])
+@pytest.mark.parametrize("ts", [2, 4])
+def test_update_z_packs_the_send_rows(dev, m, ts, lazy):
+    """pa_k_update_z_pack: the next update also writes the rows the neighbours need into the send buffer -- rows in
+    no, one and three slots -- and only the next one."""
+    t = ts
+    rng = np.random.default_rng(m + ts + lazy)
+    Z, V0, V1 = D.panel(rng, m, ts), D.panel(rng, m, ts), D.panel(rng, m, ts)
+    U, Up = D.factor(rng, t), D.factor(rng, t)
+    beta = rng.standard_normal((2 * t, t))
+    cnt = rng.choice([0, 1, 3], size=m)
+    cnt[:3] = [0, 1, 3]
+    off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int32)
+    nslot = int(off[-1])
+    slot = rng.permutation(nslot + 5)[:nslot].astype(np.int32)         # (distinct; five slots nobody writes)
+    dZ, dV0, dV1, dbeta = dev.up(Z), dev.up(V0), dev.up(V1), dev.upf(beta)
+    dU, dUp = dev.upf(U), dev.upf(Up)
+    doff, dslot, dsend = dev.up(off), dev.up(slot), dev.zeros((nslot + 5) * ts * 8)
+
+    def update():
+        return dev.L.pa_k_update_z(m, ts, t, t, t, dbeta, 2 * t, dV0, dV1, dZ, None, None, dU if lazy else None,
+                                   dUp if lazy else None, None, 0, None)
+
+    assert dev.L.pa_k_update_z_pack(8, doff, dslot, dsend) == 0
+    assert dev.L.pa_k_update_z_pack(ts, doff, dslot, dsend) == 1
+    assert update() == 0, dev.error()
+    Zn, send = dev.down(dZ, (m, ts)), dev.down(dsend, (nslot + 5, ts))
+    want = np.zeros_like(send)
+    for row in range(m):
+        want[slot[off[row]:off[row + 1]]] = Zn[row]
+    assert send.tobytes() == want.tobytes()
+    ref = D.lazy_update_z(Z, V0, V1, U, Up, beta, t) if lazy else D.update_z(Z, np.hstack([V0, V1]), beta, t)
+    Za, cz = D.update_z_abs(Z, np.hstack([V0, V1]), beta, t)
+    bnd = D.lazy_update_z_bound(Z, V0, V1, U, Up, beta, t) if lazy else (cz + D.SPARE) * D.UNIT * Za
+    assert D.ratio(Zn, ref, bnd) <= 1.0
+    assert update() == 0, dev.error()                                  # the one-shot is spent
+    assert dev.down(dsend, (nslot + 5, ts)).tobytes() == send.tobytes()
+    assert dev.down(dZ, (m, ts)).tobytes() != Zn.tobytes()
