@@ -327,7 +327,21 @@ int preAlps_ECGSolveGuess(preAlps_ECG_t* ecg, int nrhs, const double* rhs, int l
  * Every entry above works in the operator's internal space: it takes the right-hand side and returns the solution of
  * A' = P D A D P^T, where P groups the rows part by part (preAlps_OperatorGetPermPtr: perm[new] = old) and D = diag(d),
  * d_i = sqrt(1 / max_j |a_ij|), is the scaling of preAlps_OperatorBuild and of preAlps_OperatorBuildFromCSR with
- * scale != 0.  The entries below solve A x = b as the caller stated it.  They are for one process, where N = m.
+ * scale != 0.  The entries below solve A x = b as the caller stated it, on one process (N = m) or on several.
+ *   Several processes (collective calls; a preAlps_hip_loopback shard counts as one of several): b, x0 and x stay what
+ * they are for one process -- columns indexed by the caller's GLOBAL row, leading dimension >= N, on the host or on the
+ * device -- and every rank passes arrays of that shape.  A rank reads only the rows it owns, perm[row_off .. row_off + m)
+ * (preAlps_OperatorGetOwnedRows), and writes only those rows of x: every other row of the caller's x keeps its bits, so
+ * a sum over the ranks of arrays that started at zero is the whole solution.  sys_res, sys_normb, sys_hist, res_hist,
+ * ecg->res, ecg->normb and the iteration count are global, the same words on every rank.  Host arrays go up whole (N
+ * doubles per column; the gather picks the owned rows), so no rank makes a host pass over the permutation.  With
+ * PREALPS_SYS_STOP_ORIGINAL the per-system sums travel in the collective that carries the residual norm anyway: an
+ * iteration costs no all-reduce more than one of preAlps_ECGSolve on the same ranks; the start costs one more than that
+ * of preAlps_ECGSolveGuess, and without the flag the finish has one for sys_res.  What one rank alone can find wrong --
+ * a leading dimension, a NaN in its rows, a failed allocation -- is agreed on before any rank returns: that rank
+ * returns its reason, the others "another process of the group ...".
+ *   preAlps_OperatorGetOwnedRows: *rows = perm + row_off (library-owned, the caller's rows this process owns, in the
+ * operator's local order) and *m = their count; one process: the whole permutation.  Works in plan-only mode.
  *   preAlps_OperatorGetScalingPtr: the vector d, N doubles, entry i for row i of the matrix the operator was built
  * from (the caller's order).  The array is library-owned; preAlps_OperatorUpdateValues writes the new vector into the
  * same allocation (after its last refusal: a refused update leaves the old one), preAlps_OperatorFree releases it.
@@ -363,8 +377,8 @@ int preAlps_ECGSolveGuess(preAlps_ECG_t* ecg, int nrhs, const double* rhs, int l
  *   A guess under which every system already meets its threshold, in whichever metric is selected, comes back as x,
  * bit for bit, after no iteration (*n_hist = 0).
  *   Refused (the message names the entry point): everything preAlps_ECGInitializeGuess refuses -- nrhs < 1 or
- * enlFac % nrhs != 0, s against the number of parts, ORTHODIR_FUSED, more than one process or a preAlps_hip_loopback
- * shard, a right-hand side of norm zero, a start residual that is not finite, a system that starts at exactly zero
+ * enlFac % nrhs != 0, s against the number of parts, ORTHODIR_FUSED, an operator built for another process group than
+ * the one that calls, ADAPT_BS and the coarse space on several processes, a right-hand side of norm zero, a start residual that is not finite, a system that starts at exactly zero
  * beside ones that do not -- and ldb, ldx0 or ldx < N, b or x == NULL, a right-hand side that is not finite, unknown
  * flags.  After a refusal the operator and the preconditioner are usable as before.  HIP graphs and PREALPS_ECG_POLL
  * are off for such a solver, as for several systems.  The solver object is released before the entry returns.
@@ -372,11 +386,13 @@ int preAlps_ECGSolveGuess(preAlps_ECG_t* ecg, int nrhs, const double* rhs, int l
  * caller's units, fresh -- formed from b and x, not from a recurrence: one start from the guess x at s = 1 on a
  * temporary solver of width nrhs (the gather, the library's own product, R0), the norm kernel on R0, and a free.
  * nrhs <= 16 (what the per-system arrays of a solver hold); flags: PREALPS_SYS_DEVICE or 0.  No preconditioner is
- * needed.  It refuses what the start refuses (a zero or non-finite right-hand side, a non-finite x, more than one
- * process); a residual of exactly zero is an answer here, not a refusal. */
+ * needed.  It refuses what the start refuses (a zero or non-finite right-hand side, a non-finite x, an operator built
+ * for another process group); a residual of exactly zero is an answer here, not a refusal.  Several processes:
+ * collective, x is read at the owned rows, its halo comes through the library's exchange, and the sums are reduced. */
 #define PREALPS_SYS_DEVICE        1   /* b, x0, x are device pointers */
 #define PREALPS_SYS_STOP_ORIGINAL 2   /* stop on ||b_j - A x_j|| <= tol ||b_j|| in the caller's units */
 int preAlps_OperatorGetScalingPtr(double** d, int* n);
+int preAlps_OperatorGetOwnedRows(int** rows, int* m);
 int preAlps_ECGSolveSystem(preAlps_ECG_t* ecg, int nrhs, const double* b, int ldb,
                            const double* x0, int ldx0, double* x, int ldx, int flags,
                            double* res_hist, int* bs_hist, double* sys_hist, double* sys_normb,
@@ -406,7 +422,8 @@ int preAlps_OperatorSystemResiduals(int nrhs, const double* b, int ldb, const do
  * last pass -- a pass that the budget cut short may not have recovered from its restart yet -- so its residuals are
  * row *n_passes or row *n_passes - 1 of pass_res, whichever has the smaller ratio.  (ecg_refine.h states the rule.)
  *   Refused: what preAlps_ECGSolveSystem refuses, max_passes outside 1 .. 16, nrhs > 16, a NULL among n_passes,
- * pass_iters, pass_res and status.  One process, like the entry it wraps. */
+ * pass_iters, pass_res and status.  Several processes, like the entry it wraps: every pass decision reads reduced norms,
+ * so it falls alike on every rank. */
 #define PREALPS_REFINE_CONVERGED         0
 #define PREALPS_REFINE_OUT_OF_PASSES     1
 #define PREALPS_REFINE_OUT_OF_ITERATIONS 2

@@ -1,6 +1,6 @@
 // dense_device.h -- what more than one of the dense panel units (dense_gram.hip, dense_update.hip,
-// dense_panels.hip) uses: the workgroup-wide Cholesky / alpha step, the column sums of a workgroup, the note to
-// a polling host, and the launch grids.
+// dense_panels.hip, dense_system.hip) uses: the workgroup-wide Cholesky / alpha step, the column sums of a workgroup, the note to
+// a polling host, the fixed tree of the per-system sums, and the launch grids.
 // Private to those units; like kernels_common.h every unit gets its own copy.
 #pragma once
 #include "kernels_common.h"
@@ -146,6 +146,27 @@ __device__ __forceinline__ void note_to_host(double* host, const double* src, do
   __hip_atomic_store(host + 1, src[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   __threadfence_system();
   if (seq != 0.0) __hip_atomic_store(host + 2, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// The per-system sums of the stopping test: the sum over the s columns of system j (ascending) of the sum over the
+// blocks of rtr[blk*ts + c] (the column sums of R^2 an update kernel or k_colnorm2 left).  One workgroup; 16 threads
+// per column take the blocks b = l, l + 16, ... in turn and are folded by a fixed tree, so the k values are
+// reproducible.  group_fold: that sum in thread j < k (0 elsewhere); called by the whole workgroup, red: WG doubles.
+__device__ __forceinline__ double group_fold(const double* __restrict__ rtr, int nblk, int ts, int k, int s, double* red) {
+  const int c = threadIdx.x >> 4, l = threadIdx.x & 15;
+  double v = 0.0;
+  if (c < k * s)
+    for (int b = l; b < nblk; b += 16) v += rtr[(size_t)b * ts + c];
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int off = 8; off > 0; off >>= 1) {
+    if (l < off) red[threadIdx.x] += red[threadIdx.x + off];
+    __syncthreads();
+  }
+  double g = 0.0;
+  if (threadIdx.x < k)
+    for (int q = 0; q < s; ++q) g += red[(threadIdx.x * s + q) << 4];
+  return g;
 }
 
 inline int grid_rows(int m, int per_thread_rows = 1) {

@@ -240,27 +240,7 @@ __global__ __launch_bounds__(WG) void k_guess_start(int m, int k, int s, const d
   block_sum_cols<TS>(accr, rsums + (size_t)blockIdx.x * TS);
 }
 
-// The per-system sums of the stopping test: the sum over the s columns of system j (ascending) of the sum over the
-// blocks of rtr[blk*ts + c] (the column sums of R^2 an update kernel or k_colnorm2 left).  One workgroup; 16 threads
-// per column take the blocks b = l, l + 16, ... in turn and are folded by a fixed tree, so the k values are
-// reproducible.  group_fold: that sum in thread j < k (0 elsewhere); called by the whole workgroup, red: WG doubles.
-__device__ __forceinline__ double group_fold(const double* __restrict__ rtr, int nblk, int ts, int k, int s, double* red) {
-  const int c = threadIdx.x >> 4, l = threadIdx.x & 15;
-  double v = 0.0;
-  if (c < k * s)
-    for (int b = l; b < nblk; b += 16) v += rtr[(size_t)b * ts + c];
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int off = 8; off > 0; off >>= 1) {
-    if (l < off) red[threadIdx.x] += red[threadIdx.x + off];
-    __syncthreads();
-  }
-  double g = 0.0;
-  if (threadIdx.x < k)
-    for (int q = 0; q < s; ++q) g += red[(threadIdx.x * s + q) << 4];
-  return g;
-}
-
+// (group_fold, the fixed tree of the per-system sums: dense_device.h)
 // One process: the values go to device memory and to pinned host words, which the host reads once the launch or
 // event behind this one has completed (it keys on nothing this kernel writes).
 __global__ __launch_bounds__(WG) void k_group_norms(const double* __restrict__ rtr, int nblk, int ts, int k, int s,

@@ -1,6 +1,7 @@
 // dense_system.hip -- the caller's own system around the ECG block iteration (preAlps_ECGSolveSystem): the gather of
 // B and X0 from the caller's order and units into the staging arrays of the start, the scatter of the solutions back,
-// and the per-system residual norms in the caller's units, with their C launchers (pa_device.h).  The iteration works
+// and the per-system residual norms in the caller's units (on several processes: folded behind the words a collective of
+// the iteration carries, k_sys_norms_ride), with their C launchers (pa_device.h).  The iteration works
 // on A' = P D A D P^T; local row i is the caller's row src[i] and dl[i] = d[src[i]] its scaling factor (1.0 when the
 // operator is unscaled), so b' = dl * b[src], x0' = x0[src] / dl, x[src] = dl * x' and r[src] = r' / dl.
 // See dense_gram.hip for the layout of panels.
@@ -94,6 +95,40 @@ __global__ __launch_bounds__(WG) void k_sys_norms(int m, int k, int s, const dou
   block_sum_cols<TS>(acc, part + (size_t)blockIdx.x * TS);
 }
 
+// Xout(src[i], j) = Xin(src[i], j): the rows this process owns of a guess that is already the answer, bit for bit.
+__global__ __launch_bounds__(WG) void k_sys_copy_rows(int m, int k, const int* __restrict__ src, const double* __restrict__ Xin,
+                                                      size_t ldin, double* __restrict__ Xout, size_t ldout) {
+  const size_t stride = (size_t)gridDim.x * WG;
+  for (size_t row = (size_t)blockIdx.x * WG + threadIdx.x; row < (size_t)m; row += stride) {
+    const size_t at = (size_t)src[row];
+    for (int j = 0; j < k; ++j) Xout[at + (size_t)j * ldout] = Xin[at + (size_t)j * ldin];
+  }
+}
+
+// The caller's metric on several processes: the sums are this process's share, so -- as k_group_norms_ride does for
+// several systems -- they go behind the two words a collective of the iteration carries anyway.  buf[0] = the local
+// scaled sum of squares of all of R, folded from rtr group by group with the groups added in ascending j (the
+// additions of k_group_norms_ride, so the same bits), buf[1] = the Cholesky status, buf[2 + j] = the fold of the
+// partial sums k_sys_norms left (one column per system, s = 1): system j's share of ||b_j - A x_j||^2 in the caller's
+// units.  One workgroup; nothing else is written.
+__global__ __launch_bounds__(WG) void k_sys_norms_ride(const double* __restrict__ rtr, int rtr_nblk,
+                                                       const double* __restrict__ sys, int sys_nblk, int ts, int k, int s,
+                                                       const int* __restrict__ info, double* __restrict__ buf) {
+  __shared__ double red[WG];
+  __shared__ double grp[16];
+  const double g = group_fold(rtr, rtr_nblk, ts, k, s, red);
+  if (threadIdx.x < k) grp[threadIdx.x] = g;
+  __syncthreads();      // (grp is complete, and red has been read: the second fold may write it)
+  const double o = group_fold(sys, sys_nblk, ts, k, 1, red);
+  if (threadIdx.x < k) buf[2 + threadIdx.x] = o;
+  if (threadIdx.x == 0) {
+    double all = 0.0;
+    for (int j = 0; j < k; ++j) all += grp[j];
+    buf[0] = all;
+    buf[1] = info ? (double)info[0] : 0.0;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -133,6 +168,28 @@ int pa_k_sys_norms(int m, int ts, int k, int s, const double* R, const double* d
   *nblk = blocks;
   TS_DISPATCH(ts, PA_LAUNCH((k_sys_norms<TS_>), dim3(blocks), dim3(WG), 0, cur_stream(), m, k, s, R, dl, part));
   return kfail("k_sys_norms");
+}
+
+int pa_k_sys_copy_rows(int m, int k, const int* src, const double* Xin, int ldin, double* Xout, int ldout) {
+  if (m < 0 || k < 1 || !src || !Xin || !Xout || ldin < m || ldout < m) {
+    pa_rt_set_error("pa_k_sys_copy_rows: %d rows of %d columns, leading dimensions %d / %d", m, k, ldin, ldout);
+    return 1;
+  }
+  PA_LAUNCH(k_sys_copy_rows, dim3(update_grid(m, 4)), dim3(WG), 0, cur_stream(), m, k, src, Xin, (size_t)ldin, Xout,
+            (size_t)ldout);
+  return kfail("k_sys_copy_rows");
+}
+
+int pa_k_sys_norms_ride(const double* rtr_part, int rtr_nblk, const double* sys_part, int sys_nblk, int ts, int k, int s,
+                        const int* info, double* buf) {
+  if (sys_args_bad("pa_k_sys_norms_ride", 0, ts, k, s)) return 1;
+  if (!buf || !rtr_part || !sys_part || rtr_nblk < 0 || sys_nblk < 0) {
+    pa_rt_set_error("pa_k_sys_norms_ride: no buffer for the %d sums, or no partial sums to fold", k);
+    return 1;
+  }
+  PA_LAUNCH(k_sys_norms_ride, dim3(1), dim3(WG), 0, cur_stream(), rtr_part, rtr_nblk, sys_part, sys_nblk, ts, k, s, info,
+            buf);
+  return kfail("k_sys_norms_ride");
 }
 
 }  // extern "C"

@@ -183,7 +183,7 @@ int pa_ecg_reset_state(preAlps_ECG_t* ecg, ecg_priv_t* pv, int nrhs, int guess, 
   pa_ecg_switch_t sw;
   pa_ecg_switches(&in, &sw);
   pv->rotate = sw.rotate; pv->fuse = sw.fuse; pv->lazy_norm = sw.lazy_norm; pv->lazy_stop = sw.lazy_stop;
-  pv->use_graphs = sw.use_graphs; pv->poll = sw.poll; pv->ride = sw.ride;
+  pv->use_graphs = sw.use_graphs; pv->poll = sw.poll; pv->ride = sw.ride; pv->ride_sys = sw.ride_sys;
   pv->solve_first = solve_first_switch();
   pv->x_defer = pa_env_flag("PREALPS_ECG_X_DEFER", 1) != 0;
   pv->x_pending = 0;
@@ -299,8 +299,9 @@ int _preAlps_ECGSplit(double* x, CPLM_Mat_Dense_t* XSplit, int colIndex) {
  * iteration's R, on the same stream (the update kernels of fused_update, update_iterate and solve_first_step; in
  * stopping_queue nothing has touched R since); R never takes part in the rotation of the direction panels, and its
  * pointer is taken from the descriptor at the moment of the launch. */
-/* Several processes (pv->ride): the sums are local, and go behind the pair [norm^2, status] at `dst` that the next
- * collective carries (d_res2, or the slot behind beta when the norm is summed with beta); dst is unused otherwise. */
+/* Several processes (pv->ride, and with the caller's metric pv->ride_sys): the sums are local, and go behind the pair
+ * [norm^2, status] at `dst` that the next collective carries (d_res2, or the slot behind beta when the norm is summed
+ * with beta); dst is unused otherwise. */
 int pa_ecg_queue_group_norms(preAlps_ECG_t* ecg, ecg_priv_t* pv, double* dst) {
   if (pv->ride) {
     PA_CHECK(pa_k_group_norms_ride(pv->d_rtr_part, pv->rtr_nblk, pv->ts, pv->nrhs, pv->sgrp, pv->d_info, dst));
@@ -309,7 +310,12 @@ int pa_ecg_queue_group_norms(preAlps_ECG_t* ecg, ecg_priv_t* pv, double* dst) {
     int nb = 0;
     const int k = pv->nrhs > 1 ? pv->nrhs : 1;
     PA_CHECK(pa_k_sys_norms(pv->m, pv->ts, k, pv->sgrp, ecg->R->val, pv->d_dl, pv->d_sys_part, &nb));
-    PA_CHECK(pa_k_group_norms(pv->d_sys_part, nb, pv->ts, k, 1, pv->d_grp, pv->h_grp));
+    if (pv->ride_sys) {
+      /* several processes: this process's share, folded behind the pair at dst with the scaled norm of all of R */
+      PA_CHECK(pa_k_sys_norms_ride(pv->d_rtr_part, pv->rtr_nblk, pv->d_sys_part, nb, pv->ts, k, pv->sgrp, pv->d_info, dst));
+      pv->grp_dst = dst;
+    } else
+      PA_CHECK(pa_k_group_norms(pv->d_sys_part, nb, pv->ts, k, 1, pv->d_grp, pv->h_grp));
   } else if (pv->nrhs > 1)
     PA_CHECK(pa_k_group_norms(pv->d_rtr_part, pv->rtr_nblk, pv->ts, pv->nrhs, pv->sgrp, pv->d_grp, pv->h_grp));
   return 0;
@@ -317,8 +323,8 @@ int pa_ecg_queue_group_norms(preAlps_ECG_t* ecg, ecg_priv_t* pv, double* dst) {
 int pa_ecg_stopping_queue(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
   int T = ecg->enlFac;
   int single = pa_world_size() == 1;
-  if (pv->ride) {
-    /* several systems on several processes: pa_k_group_norms_ride has left [norm^2, status | g_0^2 .. g_k-1^2] of
+  if (pa_ecg_rides(pv)) {
+    /* several systems, or the caller's metric, on several processes: pa_k_group_norms_ride / pa_k_sys_norms_ride has left [norm^2, status | g_0^2 .. g_k-1^2] of
      * this process at grp_dst behind the last update (from R itself when nothing is left of one); ONE all-reduce
      * of 2 + k words where one system reduces its norm, and the k global sums follow the pair to the host */
     if (pv->rtr_valid == RTR_NONE) {
@@ -639,16 +645,16 @@ static int orthogonalise_z(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
        * below passes them on to the pinned words the host reads (a copy here costs a launch and
        * 8 us of idle stream behind it);
        * several systems on several processes: their k local sums lie right behind the pair
-       * (pa_k_group_norms_ride), ride in the same collective, and reach h_grp ahead of the event below */
-      if (pa_allreduce(pv->d_beta, cnt + 2 + (pv->ride ? pv->nrhs : 0))) return 1;
-      if (pv->ride) PA_CHECK(pa_rt_d2h_async(pv->h_grp, pv->lazy_ptr + 2, (size_t)pv->nrhs * sizeof(double)));
+       * (pa_k_group_norms_ride; the caller's metric: pa_k_sys_norms_ride), ride in the same collective, and reach h_grp ahead of the event below */
+      if (pa_allreduce(pv->d_beta, cnt + 2 + (pa_ecg_rides(pv) ? pv->nrhs : 0))) return 1;
+      if (pa_ecg_rides(pv)) PA_CHECK(pa_rt_d2h_async(pv->h_grp, pv->lazy_ptr + 2, (size_t)pv->nrhs * sizeof(double)));
       note = pv->lazy_ptr;
       pv->rtr_valid = RTR_NONE;
     } else {
       if (pa_allreduce(pv->d_beta, cnt)) return 1;
       if (pv->lazy_ptr && pv->rtr_valid == RTR_SUMMED) {   /* (beta not where expected: reduce the norm by itself) */
-        if (pa_allreduce(pv->lazy_ptr, pv->ride ? 2 + pv->nrhs : 1)) return 1;
-        if (pv->ride) PA_CHECK(pa_rt_d2h_async(pv->h_grp, pv->lazy_ptr + 2, (size_t)pv->nrhs * sizeof(double)));
+        if (pa_allreduce(pv->lazy_ptr, pa_ecg_rides(pv) ? 2 + pv->nrhs : 1)) return 1;
+        if (pa_ecg_rides(pv)) PA_CHECK(pa_rt_d2h_async(pv->h_grp, pv->lazy_ptr + 2, (size_t)pv->nrhs * sizeof(double)));
         PA_CHECK(pa_rt_d2h_async(pv->h_pin, pv->lazy_ptr, 2 * sizeof(double)));
         PA_CHECK(pa_rt_event_record(pv->ev_res));
         pv->wait_seq = 0.0;

@@ -80,7 +80,7 @@ static int graph_iteration(preAlps_ECG_t* ecg, ecg_priv_t* pv, int* rci_request,
  * that order forms the first alpha of the next call with pa_k_gram_finish, and so must this one to give the same
  * bits; a call therefore returns in the state "AP = A P is queued" of the RCI protocol (rci 0), as it always did. */
 static int solve_first_applies(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
-  return pa_ecg_in_own_loop() > 0 && ecg->P->info.n == 4 && pv->ts == 4 && !pv->ride &&      /* (ride: several processes) */
+  return pa_ecg_in_own_loop() > 0 && ecg->P->info.n == 4 && pv->ts == 4 && !pa_ecg_rides(pv) &&      /* (several processes) */
          pa_ecg_solve_first_rule(pv->solve_first, pa_world_size(), ecg->ortho_alg, ecg->bs_red, ecg->enlFac, pv->fuse,
                                  pv->lazy_norm, pv->lazy_stop, pv->bj_cap > 0, pv->spmm_cap > 0, pv->use_graphs);
 }
@@ -133,7 +133,7 @@ static int solve_first_step(preAlps_ECG_t* ecg, ecg_priv_t* pv, int ahead, int* 
   if (xm == PA_ECG_X_SKIP) pa_ecg_x_owed(pv);
   else pv->x_pending = 0;
   pv->rtr_nblk = nb;
-  if (pa_ecg_queue_group_norms(ecg, pv, NULL)) return 1;      /* (never pv->ride: solve_first_applies) */
+  if (pa_ecg_queue_group_norms(ecg, pv, NULL)) return 1;      /* (never riding: solve_first_applies) */
   pv->uu_cur ^= 1;
   ecg->iter++;
   /* the norm of the new residual (and the Cholesky status) straight to the pinned words the host reads */
@@ -313,7 +313,8 @@ int preAlps_ECGSolveGuess(preAlps_ECG_t* ecg, int nrhs, const double* rhs, int l
                            .x0 = x0, .ldx0 = ldx0, .sys_res0 = sys_res0};
   return solve_in_own_loop(ecg, (double*)rhs, sol, res_hist, bs_hist, max_hist, n_hist, &mu);
 }
-/* preAlps_ECGSolveGuess around the gather and the scatter: A x = b as the caller stated it (one process: N = m). */
+/* preAlps_ECGSolveGuess around the gather and the scatter: A x = b as the caller stated it (one process: N = m; several:
+ * the arrays stay global, and a rank reads and writes the rows it owns). */
 /* the refusals of a system solve that its arguments alone decide; who: the entry they name */
 static int system_args_refused(const char* who, const preAlps_ECG_t* ecg, int nrhs, const double* b, int ldb,
                                const double* x0, int ldx0, const double* x, int ldx, int flags) {
@@ -322,6 +323,8 @@ static int system_args_refused(const char* who, const preAlps_ECG_t* ecg, int nr
   if (!ecg || !b || !x) return pa_fail_at(who, " wrong test 'ecg != NULL && b != NULL && x != NULL'");
   if (nrhs < 1) return pa_fail_at(who, "nrhs = %d: at least one right-hand side is needed", nrhs);
   if (flags & ~(PREALPS_SYS_DEVICE | PREALPS_SYS_STOP_ORIGINAL)) return pa_fail_at(who, "flags = %d holds unknown bits", flags);
+  /* (several processes: a leading dimension is one rank's argument, so the start takes the verdict to its agreement) */
+  if (pa_world_size() > 1 || pa_comm_is_loopback()) return 0;
   if (ldb < op->N) return pa_fail_at(who, "ldb = %d is smaller than the %d rows of the matrix", ldb, op->N);
   if (x0 && ldx0 < op->N) return pa_fail_at(who, "ldx0 = %d is smaller than the %d rows of the matrix", ldx0, op->N);
   if (ldx < op->N) return pa_fail_at(who, "ldx = %d is smaller than the %d rows of the matrix", ldx, op->N);
@@ -331,7 +334,7 @@ int preAlps_ECGSolveSystem(preAlps_ECG_t* ecg, int nrhs, const double* b, int ld
                            int ldx, int flags, double* res_hist, int* bs_hist, double* sys_hist, double* sys_normb,
                            double* sys_res, int max_hist, int* n_hist) {
   if (system_args_refused(__func__, ecg, nrhs, b, ldb, x0, ldx0, x, ldx, flags)) return 1;
-  const sys_in_t in = {b, ldb, x0, ldx0, (flags & PREALPS_SYS_DEVICE) != 0, (flags & PREALPS_SYS_STOP_ORIGINAL) != 0, 0};
+  const sys_in_t in = {b, ldb, x0, ldx0, (flags & PREALPS_SYS_DEVICE) != 0, (flags & PREALPS_SYS_STOP_ORIGINAL) != 0, 0, ldx};
   const multi_args_t mu = {.nrhs = nrhs, .sys_hist = sys_hist, .sys_normb = sys_normb, .sys = &in, .sys_x = x, .sys_ldx = ldx,
                            .sys_res = sys_res};
   return solve_in_own_loop(ecg, NULL, NULL, res_hist, bs_hist, max_hist, n_hist, &mu);
@@ -401,7 +404,7 @@ int preAlps_ECGSolveSystemRefined(preAlps_ECG_t* ecg, int nrhs, const double* b,
       g.pass = p; g.iters_used = used; g.verdict = PA_REFINE_CONVERGED;      /* (what stands when the gate is not asked) */
       mu.gate = refine_gate; mu.gate_ctx = &g;
     }
-    const sys_in_t in = {b, ldb, start, p > 0 ? N : ldx0, device, (flags & PREALPS_SYS_STOP_ORIGINAL) != 0, 0};
+    const sys_in_t in = {b, ldb, start, p > 0 ? N : ldx0, device, (flags & PREALPS_SYS_STOP_ORIGINAL) != 0, 0, ldx};
     mu.sys = &in;
     int nh = 0;
     ecg->maxIter = max_iter - used;      /* a pass gets what is left (> 0 wherever a pass runs) */

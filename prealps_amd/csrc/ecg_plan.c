@@ -48,6 +48,8 @@ void pa_ecg_switches(const pa_ecg_switch_in_t* in, pa_ecg_switch_t* out) {
   /* (a loopback shard of a group of ONE is a single process in every branch of the iteration -- the world size is
    * what they read -- and has nothing to reduce: it keeps pa_k_group_norms and the pinned mirror) */
   out->ride = in->nrhs > 1 && !in->metric && in->world > 1;
+  /* the caller's metric on several processes: its sums are this process's share too, and ride the same way */
+  out->ride_sys = in->metric && in->world > 1;
   /* With more than one process every collective costs tens of microseconds.  The norm of the
    * new residual is only needed for the stopping decision, so the driver loops of this library
    * (preAlps_ECGSolve / ECGAdvance) let it travel with the beta all-reduce of the same

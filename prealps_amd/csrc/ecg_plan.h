@@ -51,7 +51,10 @@ typedef struct {
   int graphs;                     /* the graph request: 0, 1, or 2 = for any process group */
   int poll;                       /* -1: unset, else 0 / 1 */
 } pa_ecg_switch_in_t;
-typedef struct { int rotate, fuse, lazy_norm, lazy_stop, use_graphs, poll, ride; } pa_ecg_switch_t;
+/* ride: several systems on several processes; ride_sys: the caller's metric on several processes (whatever nrhs):
+ * in both the per-system sums of the stopping test travel behind the pair [norm^2, status] of a collective the
+ * iteration has anyway (ecg.c: pa_ecg_queue_group_norms).  ride_sys stands last: the fields before it keep their place. */
+typedef struct { int rotate, fuse, lazy_norm, lazy_stop, use_graphs, poll, ride, ride_sys; } pa_ecg_switch_t;
 void pa_ecg_switches(const pa_ecg_switch_in_t* in, pa_ecg_switch_t* out);
 
 int pa_ecg_solve_first_rule(int on, int nprocs, int ortho_alg, int bs_red, int enlFac, int fuse, int lazy_norm,

@@ -121,7 +121,13 @@ typedef struct {
   int metric;
   const double* d_dl;
   double* d_sys_part;
+  /* The caller's metric on several processes (ride_sys; a preAlps_hip_loopback shard of such a group too): pa_k_sys_norms
+   * leaves this process's share in d_sys_part, and pa_k_sys_norms_ride folds it behind the pair at grp_dst exactly
+   * where ride puts the sums of several systems: [norm^2, status | g_0^2 .. g_nrhs-1^2], nrhs >= 1 words behind the
+   * pair, in the same collective.  Every site that reads `ride` reads pa_ecg_rides instead. */
+  int ride_sys;
 } ecg_priv_t;
+static inline int pa_ecg_rides(const ecg_priv_t* pv) { return pv->ride || pv->ride_sys; }
 
 static inline ecg_priv_t* priv_of(preAlps_ECG_t* ecg) {
   if (!ecg || !ecg->iwork) return NULL;
@@ -135,8 +141,11 @@ static inline ecg_priv_t* priv_of(preAlps_ECG_t* ecg) {
  * and units of the matrix the operator was built from, on the host or (device) on the device.  pa_k_sys_gather fills
  * the staging arrays d_B / d_X0 that the host path uploads into -- b' = dl * b[src], x0' = x0[src] / dl -- and leaves
  * the caller's ||b_j||^2; what follows the uploads is the same code.  metric: the stopping test is the caller's;
- * probe: only the start's norms are wanted, so a system that starts at exactly zero is no refusal. */
-typedef struct { const double* b; int ldb; const double* x0; int ldx0; int device, metric, probe; } sys_in_t;
+ * probe: only the start's norms are wanted, so a system that starts at exactly zero is no refusal.
+ * Several processes: the arrays are still the caller's global ones; a rank reads and writes the rows it owns.  ldx: the
+ * leading dimension of the solution array (0: there is none), kept here because on several processes the verdicts on
+ * the leading dimensions are agreed on by the start instead of being returned at once. */
+typedef struct { const double* b; int ldb; const double* x0; int ldx0; int device, metric, probe; int ldx; } sys_in_t;
 
 typedef struct {      /* what preAlps_ECGSolveMulti adds to the arguments of preAlps_ECGSolve; nrhs = 0: the latter */
   int nrhs, ldrhs, ldsol;

@@ -19,6 +19,9 @@
  *   Several processes: every rank passes its own rows, A X0 is the distributed product, the start's local sums are
  * reduced in one all-reduce, and in the iteration the per-system sums ride on the collective of the residual norm
  * (pv->ride); what one rank alone can find wrong is agreed on before any rank returns (ranks_agree).
+ *   The caller's own system on several processes: b, x0 and x stay the caller's global arrays, the gather and the
+ * scatter touch the rows this rank owns, the caller's-units sums of the start take one more all-reduce
+ * (reduce_system_sums), and in the iteration they ride like the sums of several systems (pv->ride_sys).
  */
 #include <math.h>
 #include <stdlib.h>
@@ -73,13 +76,17 @@ typedef struct {
   int k, s, m, multi;
   const double* rhs; int ldrhs; const double* x0; int ldx0; const sys_in_t* sys;
   size_t mm, cols;        /* max(m, 1); columns of the staging array: k, with a guess 2k */
+  size_t nn;              /* max(N, 1): the rows of the caller's own arrays (one process: N = m) */
   const int* d_src;       /* the caller's own system: the operator's row map */
+  int gblk;               /* ... and the blocks of partial sums its gather left in d_sys_part */
 } start_t;
 /* The staging buffers of a start: B (and X0) go up once (m*k doubles each) with p % s of every row; the kernels write R0
  * (and X0's panel) and leave the sums of squares.  d_raw: the caller's host arrays go up as they are, then through the
- * gather; device arrays are gathered where they lie.  h_b1: one system in the caller's units: its scaled right-hand
+ * gather (whole, the N rows of every column: on several processes the gather then picks the rows this rank owns, and the
+ * ranks need no host pass over the permutation); device arrays are gathered where they lie.  gblk: the blocks of partial
+ * sums the gather left in d_sys_part.  h_b1: one system in the caller's units: its scaled right-hand
  * side comes back for the host sum (m doubles, once per solve).  d_X0 / d_pcol lie in d_B's allocation. */
-typedef struct { int* pcol; double* d_B; double* d_raw; double* h_b1; double* d_X0; int* d_pcol; } staging_t;
+typedef struct { int* pcol; double* d_B; double* d_raw; double* h_b1; double* d_X0; int* d_pcol; int gblk; } staging_t;
 static void staging_release(staging_t* st) {
   pa_rt_free(st->d_B);
   pa_rt_free(st->d_raw);
@@ -92,7 +99,7 @@ static int staging_acquire(const start_t* c, staging_t* st) {   /* 1: a buffer i
   memset(st, 0, sizeof(*st));
   st->pcol = (int*)malloc(c->mm * sizeof(int));
   st->d_B = (double*)pa_rt_malloc(c->mm * c->cols * sizeof(double) + c->mm * sizeof(int));
-  st->d_raw = (sys && !sys->device) ? (double*)pa_rt_malloc(c->mm * c->cols * sizeof(double)) : NULL;
+  st->d_raw = (sys && !sys->device) ? (double*)pa_rt_malloc(c->nn * c->cols * sizeof(double)) : NULL;
   st->h_b1 = (sys && c->k == 1) ? (double*)malloc(c->mm * sizeof(double)) : NULL;
   if (!st->pcol || !st->d_B || (sys && !sys->device && !st->d_raw) || (sys && c->k == 1 && !st->h_b1)) return 1;
   st->d_pcol = (int*)(st->d_B + c->mm * c->cols);
@@ -110,15 +117,17 @@ static int upload_and_gather(const start_t* c, staging_t* st) {
   int rc = pa_rt_h2d(st->d_pcol, st->pcol, (size_t)m * sizeof(int));
   if (sys) {
     const double* gb = sys->b; const double* gx = c->x0;
-    int gldb = sys->ldb, gldx = c->ldx0, gblk = 0;
+    int gldb = sys->ldb, gldx = c->ldx0;
+    const int N = c->op->N;
     if (!sys->device) {
-      for (int j = 0; j < k && !rc; ++j) rc = pa_rt_h2d(st->d_raw + (size_t)j * m, sys->b + (size_t)j * sys->ldb, (size_t)m * sizeof(double));
+      for (int j = 0; j < k && !rc; ++j) rc = pa_rt_h2d(st->d_raw + (size_t)j * N, sys->b + (size_t)j * sys->ldb, (size_t)N * sizeof(double));
       for (int j = 0; c->x0 && j < k && !rc; ++j)
-        rc = pa_rt_h2d(st->d_raw + (size_t)(k + j) * m, c->x0 + (size_t)j * c->ldx0, (size_t)m * sizeof(double));
-      gb = st->d_raw; gx = c->x0 ? st->d_raw + c->mm * k : NULL; gldb = gldx = m;
+        rc = pa_rt_h2d(st->d_raw + (size_t)(k + j) * N, c->x0 + (size_t)j * c->ldx0, (size_t)N * sizeof(double));
+      gb = st->d_raw; gx = c->x0 ? st->d_raw + c->nn * k : NULL; gldb = gldx = N;
     }
-    rc = rc || pa_k_sys_gather(m, pv->ts, k, c->d_src, pv->d_dl, gb, gldb, gx, gldx, st->d_B, st->d_X0, pv->d_sys_part, &gblk) ||
-         pa_k_group_norms(pv->d_sys_part, gblk, pv->ts, k, 1, pv->d_grp + 32, pv->h_grp + 32);
+    rc = rc || pa_k_sys_gather(m, pv->ts, k, c->d_src, pv->d_dl, gb, gldb, gx, gldx, st->d_B, st->d_X0, pv->d_sys_part, &st->gblk) ||
+         /* (several processes: the partial sums wait in d_sys_part for reduce_system_sums) */
+         (!c->multi && pa_k_group_norms(pv->d_sys_part, st->gblk, pv->ts, k, 1, pv->d_grp + 32, pv->h_grp + 32));
   } else if (c->ldrhs == m) rc = rc || pa_rt_h2d(st->d_B, c->rhs, (size_t)m * k * sizeof(double));
   else for (int j = 0; j < k && !rc; ++j) rc = pa_rt_h2d(st->d_B + (size_t)j * m, c->rhs + (size_t)j * c->ldrhs, (size_t)m * sizeof(double));
   if (c->x0) {
@@ -203,6 +212,30 @@ static int reduce_start_sums(const start_t* c, int mine, double nb1) {
   for (int j = 0; j < k && !rc; ++j) { pv->h_grp[16 + j] = h[1 + j]; if (c->x0) pv->h_grp[j] = h[1 + k + j]; }
   return rc;
 }
+/* The caller's metric on several processes: ONE more all-reduce, of [a process failed | the caller's b_0^2 .. b_k-1^2 |
+ * the start residuals in the caller's units, k words].  The first k sums are the fold of what the gather left in
+ * d_sys_part (gblk blocks), the others pa_k_sys_norms on R0 folded the same way (the stream keeps the first fold ahead of
+ * the launch that writes d_sys_part again); both go to d_grp[1 ..), which the first all-reduce has done with.  Every
+ * rank enters it: the verdicts ahead of it fell alike on all of them.  The global sums land in h_grp[32 ..) and
+ * h_grp[0 ..), where one process finds them. */
+static int reduce_system_sums(const start_t* c) {
+  ecg_priv_t* pv = c->pv;
+  const int k = c->k;
+  double* const d_red = pv->d_grp;
+  double h[1 + 2 * 16];
+  int nb = 0;
+  const int mine = pa_k_group_norms(pv->d_sys_part, c->gblk, pv->ts, k, 1, d_red + 1, NULL) ||
+                   pa_k_sys_norms(c->m, pv->ts, k, c->s, c->ecg->R->val, pv->d_dl, pv->d_sys_part, &nb) ||
+                   pa_k_group_norms(pv->d_sys_part, nb, pv->ts, k, 1, d_red + 1 + k, NULL);
+  int rc = mine ? FAIL_AS(c->who, "%s", pa_rt_error()) : 0;
+  h[0] = mine ? 1.0 : 0.0;
+  const int up = pa_rt_h2d(d_red, h, sizeof(double));
+  if (pa_allreduce(d_red, 1 + 2 * k) || up || pa_rt_d2h(h, d_red, (size_t)(1 + 2 * k) * sizeof(double)))
+    rc = mine ? 1 : FAIL_AS(c->who, "%s", pa_rt_error());
+  else if (h[0] != 0.0) rc = mine ? 1 : FAIL_AS(c->who, "another process of the group could not form its norms (its own message says why)");
+  for (int j = 0; j < k && !rc; ++j) { pv->h_grp[32 + j] = h[1 + j]; pv->h_grp[j] = h[1 + k + j]; }
+  return rc;
+}
 /* The verdicts on the sums in h_grp, the per-system norms, ecg->normb; *r2: with a guess, ||R0||_F^2. */
 static int start_verdicts(const start_t* c, double* r2) {
   preAlps_ECG_t* ecg = c->ecg;
@@ -236,7 +269,8 @@ static int start_verdicts(const start_t* c, double* r2) {
   }
   if (!rc && pv->metric) {
     /* the caller's metric: both sides of every test in the caller's units, the start's included */
-    if (pa_ecg_queue_group_norms(ecg, pv, NULL) || pa_rt_sync()) rc = FAIL_AS(who, "%s", pa_rt_error());
+    if (c->multi) rc = reduce_system_sums(c);
+    else if (pa_ecg_queue_group_norms(ecg, pv, NULL) || pa_rt_sync()) rc = FAIL_AS(who, "%s", pa_rt_error());
     for (int j = 0; j < k && !rc; ++j) {
       pv->sys_normb[j] = sqrt(pv->h_grp[32 + j]);
       pv->sys_res[j] = sqrt(pv->h_grp[j]);
@@ -262,20 +296,24 @@ int pa_ecg_start_systems(const char* who, preAlps_ECG_t* ecg, int nrhs, const do
   int bad = 0;
   if (!sys && ldrhs < m) bad = FAIL_AS(who, "ldrhs = %d is smaller than the %d local rows", ldrhs, m);
   else if (!sys && x0 && ldx0 < m) bad = FAIL_AS(who, "ldx0 = %d is smaller than the %d local rows", ldx0, m);
+  /* the caller's own system states global rows (one process: its entry has returned these already) */
+  else if (sys && sys->ldb < op->N) bad = FAIL_AS(who, "ldb = %d is smaller than the %d rows of the matrix", sys->ldb, op->N);
+  else if (sys && x0 && ldx0 < op->N)
+    bad = FAIL_AS(who, "%s = %d is smaller than the %d rows of the matrix", sys->probe ? "ldx" : "ldx0", ldx0, op->N);
+  else if (sys && sys->ldx && sys->ldx < op->N) bad = FAIL_AS(who, "ldx = %d is smaller than the %d rows of the matrix", sys->ldx, op->N);
   if (bad && !multi) return 1;
   if (ecg->ortho_alg == ORTHODIR_FUSED)
     return FAIL_AS(who, "ORTHODIR_FUSED decides inside preAlps_ECGIterate on one sum: no per-system stopping test");
-  /* the caller's own system states global rows; and a shard cut for another process group (the operator was built
-   * before preAlps_hip_set_world / preAlps_hip_loopback changed it) holds other rows than the sums would assume */
-  if (multi && (sys || op->world != pa_world_size() || op->rank != pa_world_rank() || op->loopback != pa_comm_is_loopback()))
-    return FAIL_AS(who, "%s need a single process (%d processes%s)%s",
+  /* a shard cut for another process group (the operator was built before preAlps_hip_set_world / preAlps_hip_loopback
+   * changed it) holds other rows than the sums, and the row map of the caller's own system, would assume */
+  if (multi && (op->world != pa_world_size() || op->rank != pa_world_rank() || op->loopback != pa_comm_is_loopback()))
+    return FAIL_AS(who, "%s need a single process (%d processes%s) or an operator built by the process group as it is now",
                    sys ? "the caller's own system, its row map and its norms"
                        : x0 ? "an initial guess and several right-hand sides" : "several right-hand sides", pa_world_size(),
-                   pa_comm_is_loopback() ? ", preAlps_hip_loopback shard" : "",
-                   sys ? "" : " or an operator built by the process group as it is now");
-  if (multi && ecg->bs_red != NO_BS_RED && (k > 1 || x0))
+                   pa_comm_is_loopback() ? ", preAlps_hip_loopback shard" : "");
+  if (multi && ecg->bs_red != NO_BS_RED && (k > 1 || x0 || sys))
     return FAIL_AS(who, "block-size reduction (ADAPT_BS) with %s needs a single process (%d processes%s)",
-                   x0 ? "an initial guess" : "several right-hand sides", pa_world_size(),
+                   sys ? "the caller's own system" : x0 ? "an initial guess" : "several right-hand sides", pa_world_size(),
                    pa_comm_is_loopback() ? ", preAlps_hip_loopback shard" : "");
   /* ---- acquire and agree ---- */
   if (multi) {
@@ -308,9 +346,10 @@ int pa_ecg_start_systems(const char* who, preAlps_ECG_t* ecg, int nrhs, const do
   int rc = pa_ecg_reset_state(ecg, pv, k, x0 != NULL, sys && sys->metric) ? 1 : 0;
   if (rc && !multi) { _preAlps_ECGFree(ecg); return 1; }
   start_t c = {.who = who, .ecg = ecg, .pv = pv, .op = op, .k = k, .s = s, .m = m, .multi = multi, .rhs = rhs, .ldrhs = ldrhs,
-               .x0 = x0, .ldx0 = ldx0, .sys = sys, .mm = (size_t)(m > 0 ? m : 1), .cols = (size_t)k * (x0 ? 2 : 1)};
-  if (sys) {
-    if (pa_operator_system_map(&c.d_src, &pv->d_dl)) { _preAlps_ECGFree(ecg); return 1; }
+               .x0 = x0, .ldx0 = ldx0, .sys = sys, .mm = (size_t)(m > 0 ? m : 1), .nn = (size_t)(op->N > 0 ? op->N : 1), .cols = (size_t)k * (x0 ? 2 : 1)};
+  if (sys && pa_operator_system_map(&c.d_src, &pv->d_dl)) {      /* (several processes: one rank's failure, so it travels) */
+    if (!multi) { _preAlps_ECGFree(ecg); return 1; }
+    rc = 1;
   }
   staging_t st;
   if (staging_acquire(&c, &st) && !rc)
@@ -322,6 +361,7 @@ int pa_ecg_start_systems(const char* who, preAlps_ECG_t* ecg, int nrhs, const do
   /* ---- sums: the host sum of one system, then the one all-reduce ---- */
   if (!rc && st.h_b1 && pa_rt_d2h(st.h_b1, st.d_B, (size_t)m * sizeof(double))) rc = FAIL_AS(who, "%s", pa_rt_error());
   const double nb1 = (!rc && k == 1) ? sum_one_system(&c, sys ? st.h_b1 : rhs) : 0.0;
+  c.gblk = st.gblk;
   staging_release(&st);
   if (rc == START_QUIT) { _preAlps_ECGFree(ecg); return 1; }
   if (multi) rc = reduce_start_sums(&c, rc, nb1);
@@ -392,23 +432,40 @@ int preAlps_ECGFinalizeMulti(preAlps_ECG_t* ecg, double* sol, int ldsol) {
 /* The end of a system solve: the recurrence residual norms in the caller's units (one pa_k_sys_norms on R, whichever
  * metric stopped the loop: with the caller's metric the launch and the data of the last stopping test, so the same
  * bits), the solutions scattered into the caller's order and units -- as_x0: the guess itself, copied -- and the
- * solver released.  Returns after the stream has drained. */
+ * solver released.  Returns after the stream has drained.
+ *   Several processes: the caller's x is the global array, and this rank writes the rows it owns and no other (the
+ * scatter does on the device; a host x receives them from a copy of the scattered columns, row by row of the map).
+ * The norms are global: with the caller's metric they ARE the last stopping test's (pv->sys_res: reduced then, the same
+ * words on every rank), otherwise this rank's sums are reduced here, in the one collective a finish has. */
 int pa_ecg_finish_system(preAlps_ECG_t* ecg, const multi_args_t* mu, int as_x0) {
   ecg_priv_t* pv = priv_of(ecg);
   if (!pv) return PA_FAIL("solver not initialised");
-  if (pa_ecg_flush_x(ecg, pv)) return 1;
   const pa_operator_info_t* op = pa_operator_info();
   const sys_in_t* in = mu->sys;
-  const int m = pv->m, k = pv->nrhs > 1 ? pv->nrhs : 1, s = pv->sgrp;
-  const size_t mm = (size_t)(m > 0 ? m : 1);
+  const int multi = pa_world_size() > 1 || pa_comm_is_loopback();
+  const int m = pv->m, k = pv->nrhs > 1 ? pv->nrhs : 1, s = pv->sgrp, N = op ? op->N : m;
+  const size_t nn = (size_t)(N > 0 ? N : 1);
   const int* d_src = NULL; const double* d_dl = NULL;
+  const int* h_src = op ? op->perm + op->row_off : NULL;
   double* tmp = NULL;
+  double* h_tmp = NULL;
   int nb = 0;
-  int rc = !op || pa_operator_system_map(&d_src, &d_dl);
-  if (!rc && (pa_k_sys_norms(m, pv->ts, k, s, ecg->R->val, d_dl, pv->d_sys_part, &nb) ||
-              pa_k_group_norms(pv->d_sys_part, nb, pv->ts, k, 1, pv->d_grp, pv->h_grp)))
+  int rc = pa_ecg_flush_x(ecg, pv) || !op || pa_operator_system_map(&d_src, &d_dl);
+  const int reduce = multi && !pv->metric;
+  if (!rc && !(multi && pv->metric) &&
+      (pa_k_sys_norms(m, pv->ts, k, s, ecg->R->val, d_dl, pv->d_sys_part, &nb) ||
+       pa_k_group_norms(pv->d_sys_part, nb, pv->ts, k, 1, pv->d_grp, reduce ? NULL : pv->h_grp)))
     rc = PA_FAIL("%s", pa_rt_error());
-  if (!rc && as_x0) {
+  /* (entered whatever this rank has met: its peers are in it) */
+  if (reduce && (pa_allreduce(pv->d_grp, k) || pa_rt_d2h(pv->h_grp, pv->d_grp, (size_t)k * sizeof(double))) && !rc)
+    rc = PA_FAIL("%s", pa_rt_error());
+  if (!rc && as_x0 && multi) {
+    /* the rows this rank owns of the guess, bit for bit */
+    if (in->device) rc = pa_k_sys_copy_rows(m, k, d_src, in->x0, in->ldx0, mu->sys_x, mu->sys_ldx);
+    else for (int j = 0; j < k; ++j) for (int i = 0; i < m; ++i)
+      mu->sys_x[h_src[i] + (size_t)j * mu->sys_ldx] = in->x0[h_src[i] + (size_t)j * in->ldx0];
+    if (rc) rc = PA_FAIL("%s", pa_rt_error());
+  } else if (!rc && as_x0) {
     for (int j = 0; j < k && !rc; ++j) {
       if (in->device) rc = pa_rt_d2d(mu->sys_x + (size_t)j * mu->sys_ldx, in->x0 + (size_t)j * in->ldx0, (size_t)m * sizeof(double));
       else memcpy(mu->sys_x + (size_t)j * mu->sys_ldx, in->x0 + (size_t)j * in->ldx0, (size_t)m * sizeof(double));
@@ -418,18 +475,25 @@ int pa_ecg_finish_system(preAlps_ECG_t* ecg, const multi_args_t* mu, int as_x0) 
     double* d_out = mu->sys_x;
     int ld = mu->sys_ldx;
     if (!in->device) {
-      tmp = (double*)pa_rt_malloc(mm * k * sizeof(double));
-      if (!tmp) rc = PA_FAIL("buffers for %d solutions: %s", k, pa_rt_error());
-      d_out = tmp; ld = m;
+      tmp = (double*)pa_rt_malloc(nn * k * sizeof(double));
+      if (multi) h_tmp = (double*)malloc(nn * k * sizeof(double));
+      if (!tmp || (multi && !h_tmp)) rc = PA_FAIL("buffers for %d solutions: %s", k, tmp ? "out of host memory" : pa_rt_error());
+      d_out = tmp; ld = N;
     }
     if (!rc && pa_k_sys_scatter(m, pv->ts, k, s, pv->d_X, d_src, d_dl, d_out, ld)) rc = PA_FAIL("%s", pa_rt_error());
-    /* (d_out holds the caller's rows: row src[i] of column j at src[i] + j*m, the order of the caller's x) */
-    for (int j = 0; tmp && j < k && !rc; ++j)
-      if (pa_rt_d2h(mu->sys_x + (size_t)j * mu->sys_ldx, tmp + (size_t)j * m, (size_t)m * sizeof(double)))
+    /* (d_out holds the caller's rows: row src[i] of column j at src[i] + j*N, the order of the caller's x) */
+    if (tmp && multi && !rc) {
+      if (pa_rt_d2h(h_tmp, tmp, nn * k * sizeof(double))) rc = PA_FAIL("%s", pa_rt_error());
+      for (int j = 0; j < k && !rc; ++j) for (int i = 0; i < m; ++i)
+        mu->sys_x[h_src[i] + (size_t)j * mu->sys_ldx] = h_tmp[h_src[i] + (size_t)j * N];
+    }
+    for (int j = 0; tmp && !multi && j < k && !rc; ++j)
+      if (pa_rt_d2h(mu->sys_x + (size_t)j * mu->sys_ldx, tmp + (size_t)j * N, (size_t)N * sizeof(double)))
         rc = PA_FAIL("%s", pa_rt_error());
   }
   if (!rc && pa_rt_sync()) rc = PA_FAIL("%s", pa_rt_error());
-  for (int j = 0; j < k && !rc && mu->sys_res; ++j) mu->sys_res[j] = sqrt(pv->h_grp[j]);
+  for (int j = 0; j < k && !rc && mu->sys_res; ++j) mu->sys_res[j] = (multi && pv->metric) ? pv->sys_res[j] : sqrt(pv->h_grp[j]);
+  free(h_tmp);
   pa_rt_free(tmp);
   _preAlps_ECGFree(ecg);
   return rc;
@@ -437,7 +501,9 @@ int pa_ecg_finish_system(preAlps_ECG_t* ecg, const multi_args_t* mu, int as_x0) 
 
 /* A fresh ||b_j - A x_j|| and ||b_j|| in the caller's units: one start from the guess x at s = 1 on a temporary solver
  * of width nrhs -- the gather, the library's own product, R0 -- pa_k_sys_norms on its R0, and a free.  No
- * preconditioner is needed, and nothing of an iteration is queued. */
+ * preconditioner is needed, and nothing of an iteration is queued.  Several processes: collective; b and x are the
+ * global arrays, read at the rows this rank owns (the halo of x comes through the library's exchange), and the norms
+ * are the reduced ones, the same words on every rank. */
 int preAlps_OperatorSystemResiduals(int nrhs, const double* b, int ldb, const double* x, int ldx, int flags, double* res,
                                     double* normb) {
   const pa_operator_info_t* op = pa_operator_info();
@@ -446,13 +512,15 @@ int preAlps_OperatorSystemResiduals(int nrhs, const double* b, int ldb, const do
   if (nrhs < 1 || nrhs > 16)
     return PA_FAIL("nrhs = %d: between 1 and 16 systems at a time (what the per-system arrays of a solver hold)", nrhs);
   if (flags & ~PREALPS_SYS_DEVICE) return PA_FAIL("flags = %d: only PREALPS_SYS_DEVICE applies here", flags);
-  if (ldb < op->N) return PA_FAIL("ldb = %d is smaller than the %d rows of the matrix", ldb, op->N);
-  if (ldx < op->N) return PA_FAIL("ldx = %d is smaller than the %d rows of the matrix", ldx, op->N);
+  /* (several processes: the start agrees on the leading dimensions, as it does for a solve) */
+  const int multi = pa_world_size() > 1 || pa_comm_is_loopback();
+  if (!multi && ldb < op->N) return PA_FAIL("ldb = %d is smaller than the %d rows of the matrix", ldb, op->N);
+  if (!multi && ldx < op->N) return PA_FAIL("ldx = %d is smaller than the %d rows of the matrix", ldx, op->N);
   preAlps_ECG_t e;
   memset(&e, 0, sizeof(e));
   e.globPbSize = op->N; e.locPbSize = op->m; e.enlFac = nrhs; e.maxIter = 1; e.tol = 1e-5;
   e.ortho_alg = ORTHODIR; e.bs_red = NO_BS_RED;
-  const sys_in_t in = {b, ldb, x, ldx, (flags & PREALPS_SYS_DEVICE) != 0, 1, 1};
+  const sys_in_t in = {b, ldb, x, ldx, (flags & PREALPS_SYS_DEVICE) != 0, 1, 1, 0};
   int rci = 0;
   if (pa_ecg_start_systems(__func__, &e, nrhs, NULL, 0, x, ldx, &rci, &in)) return 1;
   ecg_priv_t* pv = priv_of(&e);

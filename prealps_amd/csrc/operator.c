@@ -741,6 +741,13 @@ int preAlps_OperatorGetScalingPtr(double** d, int* n) {
   *d = g_op.info.scaling; *n = g_op.info.N;
   return 0;
 }
+/* The caller's rows this process owns, in the operator's local order: the slice of the permutation the row map is cut from. */
+int preAlps_OperatorGetOwnedRows(int** rows, int* m) {
+  if (!g_op.info.built) return PA_FAIL("operator not built");
+  if (!rows || !m) return PA_FAIL(" wrong test 'rows != NULL && m != NULL'");
+  *rows = g_op.info.perm + g_op.info.row_off; *m = g_op.info.m;
+  return 0;
+}
 /* The device copy of the row map, cut at the first system solve and again when the values (and so d) have moved. */
 int pa_operator_system_map(const int** src, const double** dl) {
   pa_operator_t* o = &g_op;

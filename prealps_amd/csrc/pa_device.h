@@ -302,6 +302,14 @@ int pa_k_sys_scatter(int m, int ts, int k, int s, const double* X, const int* sr
 /* part[blk*ts + j] = the block's share of sum_i ((sum of R[i][c] over the columns of system j, ascending) / dl[i])^2
  * (*nblk blocks): ||b_j - A x_j||^2 in the caller's units once pa_k_group_norms with s = 1 has folded them. */
 int pa_k_sys_norms(int m, int ts, int k, int s, const double* R, const double* dl, double* part, int* nblk);
+/* Xout(src[i], j) = Xin(src[i], j) for the m rows of the map and k columns (device arrays, the caller's order). */
+int pa_k_sys_copy_rows(int m, int k, const int* src, const double* Xin, int ldin, double* Xout, int ldout);
+/* The caller's metric on several processes, for a collective to carry: buf[0] = the local scaled sum of squares of all of
+ * R, folded from rtr_part (rtr_nblk blocks of column sums) as pa_k_group_norms_ride folds it -- the same bits --,
+ * buf[1] = *info (NULL: 0), buf[2 + j] = the fold of sys_part (sys_nblk blocks, what pa_k_sys_norms left) for system j;
+ * buf: 2 + k doubles on the device, nothing else is written.  Refuses k * s > ts and a NULL buf. */
+int pa_k_sys_norms_ride(const double* rtr_part, int rtr_nblk, const double* sys_part, int sys_nblk, int ts, int k, int s,
+                        const int* info, double* buf);
 
 /* ---- block-Jacobi apply (block_jacobi.c:93-109, K8) --------------------- */
 typedef struct {

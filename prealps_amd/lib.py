@@ -86,7 +86,7 @@ EXPORTS = [
     "preAlps_ECGInitializeMulti", "preAlps_ECGSystemResiduals", "preAlps_ECGFinalizeMulti", "preAlps_ECGSolveMulti",
     "preAlps_ECGInitializeGuess", "preAlps_ECGSolveGuess", "preAlps_hip_system_columns",
     "preAlps_OperatorUpdateValues", "preAlps_BlockJacobiUpdateValues",
-    "preAlps_OperatorGetScalingPtr", "preAlps_ECGSolveSystem", "preAlps_OperatorSystemResiduals",
+    "preAlps_OperatorGetScalingPtr", "preAlps_OperatorGetOwnedRows", "preAlps_ECGSolveSystem", "preAlps_OperatorSystemResiduals",
     "preAlps_BlockJacobiSetCoarseSpace", "preAlps_BlockJacobiClearCoarseSpace",
     "preAlps_BlockJacobiGetCoarseAggregates",
     "preAlps_hip_set_operator_precision", "preAlps_ECGSolveSystemRefined",
@@ -138,6 +138,7 @@ def load():
                                                 C.c_int, pd, pi, pd, pd, pd, C.c_int, pi, C.c_int, pi, pi, pd, pi]
     L.preAlps_OperatorSystemResiduals.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, pd, pd]
     L.preAlps_OperatorGetScalingPtr.argtypes = [C.POINTER(pd), pi]
+    L.preAlps_OperatorGetOwnedRows.argtypes = [C.POINTER(pi), pi]
     L._preAlps_ECGReset.argtypes = [pe, pd, pi]
     L.preAlps_BlockOperator.argtypes = [_PD, _PD]
     L.preAlps_BlockJacobiApply.argtypes = [_PD, _PD]

@@ -436,6 +436,16 @@ class EcgProblem:
             return None
         return np.ctypeslib.as_array(d, shape=(n.value,)).copy()
 
+    @property
+    def owned_rows(self):
+        """preAlps_OperatorGetOwnedRows: a NumPy copy of the caller's rows this process owns, perm[row_off : row_off + m],
+        in the operator's local order.  One process: the whole permutation; the ranks' slices partition 0 .. N-1."""
+        rows, m = C.POINTER(C.c_int)(), C.c_int()
+        check(self.L.preAlps_OperatorGetOwnedRows(C.byref(rows), C.byref(m)), "preAlps_OperatorGetOwnedRows")
+        if m.value == 0:
+            return np.zeros(0, dtype=np.int32)
+        return np.ctypeslib.as_array(rows, shape=(m.value,)).copy()
+
     def _system_args(self, what, b, x0, x0_name):
         """The checks solve_system and system_residuals share, before any library call: ("host" | "device", k, one
         column given as a vector).  Raises ValueError."""
@@ -488,7 +498,11 @@ class EcgProblem:
                      max_iter=1000, refine=False, max_passes=4):
         """preAlps_ECGSolveSystem: A x = b as the caller stated it -- the rows in the order of the matrix this problem
         was built from, the values in its units -- for one system (b of shape (N,)) or k systems (b of shape (N, k), t a
-        multiple of k), with or without a starting value x0 of the same shape.  One process.
+        multiple of k), with or without a starting value x0 of the same shape.
+        On a distributed=True or shard= problem the call is collective and b, x0 and x keep that global shape on every
+        rank: a rank reads the rows it owns (owned_rows) and the result's x holds them, with zeros in every other row, so
+        a SUM all-reduce of x over the ranks is the whole solution; iters, res, normb, sys_res, sys_normb and sys_hist are
+        global and the same on every rank.
         stop="original" (the default: this method exists so that tol means the caller's): iterate until
         ||b_j - A x_j|| <= tol * ||b_j|| for every j, both norms in the caller's units; "scaled": the library's own test
         on the scaled system, as solve / solve_multi apply it -- then the iterate is theirs bit for bit.
@@ -522,7 +536,9 @@ class EcgProblem:
             flags |= _l.SYS_DEVICE
             bk, pb, ldb = self._device_columns(b)
             xk, px0, ldx0 = (None, None, 0) if x0 is None else self._device_columns(x0)
-            x = torch.empty((k, N), dtype=torch.float64, device=bk.device).t()     # strides (1, N)
+            # strides (1, N); several ranks: zeros in the rows this rank does not own
+            alloc = torch.zeros if self.comm_kind != "none" else torch.empty
+            x = alloc((k, N), dtype=torch.float64, device=bk.device).t()
             px, ldx = x.data_ptr(), max(N, 1)
             self._order_torch_stream()
         else:
@@ -570,7 +586,8 @@ class EcgProblem:
     def system_residuals(self, B, X):
         """preAlps_OperatorSystemResiduals: (res, normb) with res[j] = ||b_j - A x_j|| and normb[j] = ||b_j|| in the
         caller's order and units, formed afresh from B and X (shape (N,) or (N, k), k <= 16; NumPy arrays or float64 CUDA
-        tensors, as solve_system takes them).  Needs no preconditioner."""
+        tensors, as solve_system takes them).  Needs no preconditioner.  On a distributed=True or shard= problem: collective,
+        B and X global as for solve_system (X is read at the rows this rank owns), the norms global."""
         kind, k, _ = self._system_args("system_residuals", B, X, "X")
         L = self.L
         N = self.N
