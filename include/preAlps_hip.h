@@ -515,7 +515,10 @@ int preAlps_hip_panel_permute_solve(const CPLM_Mat_Dense_t* Z, CPLM_Mat_Dense_t*
  * 0: no class has them, e.g. PREALPS_BJ_G4=0), "bj_g4_bytes" (bytes of those records as stored: half in single
  * precision; "bj_factor_bytes" does not count them), "bj_g4_last_ring" / "bj_g4_last_bits" /
  * "bj_g4_last_pipelined" (the last launch that read them: LDS ring depth, storage bits of the records, 1 = the
- * pipelined few-blocks chain), "ecg_graph_captures" / "ecg_graph_replays" (iteration segments captured and graphs
+ * pipelined few-blocks chain), "bj_share_classes" / "bj_shared_blocks" / "bj_share_distinct_g4_bytes" (identical
+ * diagonal blocks read one block's records, PREALPS_BJ_SHARE: classes found by the create, blocks that read another
+ * block's records now -- after preAlps_BlockJacobiUpdateValues those that still do -- and the bytes of the one-copy
+ * records that are read at all; "bj_share_s": seconds of the create's class pass), "ecg_graph_captures" / "ecg_graph_replays" (iteration segments captured and graphs
  * launched by the driver loops so far, preAlps_hip_graphs), "ecg_x_skips" / "ecg_x_flushes" (row passes of the
  * library's loops that left X alone so far, and owed updates of X that a stop paid with a launch of its own,
  * PREALPS_ECG_X_DEFER), "spmm_precision" (64 / 32: storage of the values the plan in use streams, 0: no plan

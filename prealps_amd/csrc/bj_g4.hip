@@ -37,9 +37,14 @@
 //     forward in ascending and backward in descending order; a lane fetches its A-operand entry with
 //     one ds_read_b64 (rows outside the record are clamped onto its all-zero row).
 //
-// Stored: 8 N (w + 4) bytes.  HBM bytes per apply: each sweep streams them once, 16 N (w + 4) + 16 N t
-// (PMC: 702-713 MB per launch on the headline problem = 1.08-1.09 x the algorithmic bytes, 6.1-6.3 TB/s,
-// 0.97-0.99 of what a plain read kernel streams on the same device; profiles/r0*_pmc_hbm_traffic_elasticity.json).
+// Stored: 8 N (w + 4) bytes.  Bytes REQUESTED per apply: each sweep streams them once, 16 N (w + 4) + 16 N t.
+// HBM bytes per apply: those of the records that are read at all.  A block that repeats an earlier one bit for bit
+// reads that block's records (off2[p] is the read offset, bj_share.h), so on a matrix assembled from one element
+// matrix nearly the whole stream comes out of the L2: on the headline problem 145 of 5670 blocks are distinct, the
+// PMC figure (FETCH_SIZE) fell from 700 MB to 100 MB per launch and the launch from 125 to 77 us
+// (profiles/r20_pmc_bj_share.txt).  With every block distinct, or PREALPS_BJ_SHARE=0, it is what it was: 702-713 MB
+// per launch = 1.08-1.09 x the algorithmic bytes, 6.1-6.3 TB/s, 0.97-0.99 of what a plain read kernel streams on the
+// same device (profiles/r0*_pmc_hbm_traffic_elasticity.json).
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>

@@ -8,6 +8,7 @@
 
 #include "pa_host.h"
 #include "bj_build.h"
+#include "bj_share.h"
 #include "coarse_space.h"
 
 /* The coarse space attached to the preconditioner (preAlps_BlockJacobiSetCoarseSpace): what the caller gave, kept on
@@ -35,6 +36,15 @@ typedef struct {
   double* d_Lf; double* d_Lb; double* d_invd_f; double* d_invd_b;
   double* d_Lf2; double* d_Lb2; long long* d_off2;     /* paired records of the narrow classes (optional) */
   double pairs_bytes;
+  /* Where the apply READS a block's records (bj_share.h): off_read[p] = off[rep[p]], off2_read[p] = off2[rep[p]].
+   * Every block keeps its own slot at off / off2 and every set-up kernel keeps writing it; the plan gets these two.
+   * A refresh turns a block whose band no longer equals its representative's back to its own slot
+   * (bj_refactor.hip: k_bj_share_check); the pointers never change, so captured graphs stay valid. */
+  long long* d_off_read; long long* d_off2_read;
+  int* d_rep; int* d_share_list; unsigned long long* d_share_cnt;   /* rep, the blocks with rep[p] != p, the check's two sums */
+  int share_on, share_classes, share_members, shared_blocks;       /* members: blocks with rep[p] != p at the create */
+  long long shared_elems2;                                         /* second-record elements of the blocks that share now */
+  double share_s;                                                  /* seconds of the class pass */
   void* d_Lg4; int g4_bits; double g4_bytes;                   /* one-copy records of bj_g4.hip (optional) */
   int* d_class_list[PA_BJ_MAX_CLASSES];                        /* the block list of every class of the layout */
   const int* class_list_c[PA_BJ_MAX_CLASSES];
@@ -47,6 +57,7 @@ typedef struct {
    * copies of the per-block arrays and of the factor order, the switches as the create read them, and what tells
    * that operator and panel are still the create's. */
   int* h_row0; int* h_nrows; int* h_bw; int* h_grow0; int* h_map_f; char* h_is_nd;
+  int* h_rep;                    /* np: the block whose records a block read at the create (bj_share.h), never changed */
   int row_off, dev_factor, dev_wmax, nd_bits;
   const int* A_rowptr;           /* rowPtr of the create's A */
   int op_build;                  /* pa_operator_build_count() at the create */

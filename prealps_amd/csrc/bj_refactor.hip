@@ -38,7 +38,47 @@ __global__ __launch_bounds__(WG) void k_bj_band_assemble(const unsigned* __restr
   }
 }
 
+// Does block p = list[blockIdx.x] still repeat its representative rep[p] (bj_share.h) under the new values?  One
+// workgroup compares the two assembled bands, nrows (bw + 1) doubles at boff[p] and boff[rep[p]], as 64-bit words
+// (the equality of the create: -0.0 is not +0.0), and sets the block's read offsets: the representative's if every
+// word is equal, the block's own if not -- the own slot is always written by the set-up kernels that follow.
+// cnt[0] += 1 and cnt[1] += (elements of the block's second record) for a block that still shares; the caller zeroes cnt.
+// off2 / off2_read are null when no class has second records.
+__global__ __launch_bounds__(WG) void k_bj_share_check(const int* __restrict__ list, const int* __restrict__ rep,
+                                                      const int* __restrict__ nrows, const int* __restrict__ bw,
+                                                      const long long* __restrict__ boff, const double* __restrict__ band,
+                                                      const long long* __restrict__ off, const long long* __restrict__ off2,
+                                                      long long* __restrict__ off_read, long long* __restrict__ off2_read,
+                                                      unsigned long long* __restrict__ cnt) {
+  const int p = list[blockIdx.x], r = rep[p];
+  const int b = nrows[p], w = bw[p];
+  const size_t n = (size_t)b * (size_t)(w + 1);
+  const unsigned long long* __restrict__ x = reinterpret_cast<const unsigned long long*>(band + boff[p]);
+  const unsigned long long* __restrict__ y = reinterpret_cast<const unsigned long long*>(band + boff[r]);
+  int differ = 0;
+  for (size_t i = threadIdx.x; i < n; i += WG) differ |= x[i] != y[i];
+  differ = __syncthreads_or(differ);
+  if (threadIdx.x == 0) {
+    const int from = differ ? p : r;
+    off_read[p] = off[from];
+    if (off2_read) off2_read[p] = off2[from];
+    if (!differ) {
+      atomicAdd(&cnt[0], 1ull);
+      atomicAdd(&cnt[1], (unsigned long long)(8 * ((b + 7) / 8)) * (unsigned long long)(w + 4));
+    }
+  }
+}
+
 }  // namespace
+
+extern "C" int pa_k_bj_share_check(const int* list, int count, const int* rep, const int* nrows, const int* bw,
+                                   const long long* boff, const double* band, const long long* off, const long long* off2,
+                                   long long* off_read, long long* off2_read, unsigned long long* cnt) {
+  if (count <= 0) return 0;
+  PA_LAUNCH(k_bj_share_check, dim3((unsigned)count), dim3(WG), 0, cur_stream(), list, rep, nrows, bw, boff, band, off, off2,
+            off_read, off2_read, cnt);
+  return kfail("k_bj_share_check");
+}
 
 extern "C" int pa_k_bj_band_assemble(const unsigned* src, const unsigned* dst, const int* chunk_blk,
                                      const unsigned* chunk_first, size_t nchunks, const long long* boff,

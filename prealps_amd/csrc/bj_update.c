@@ -90,9 +90,21 @@ static int bj_refactor_bands(pa_bj_t* s, const pa_operator_info_t* op, int* wrot
     if (pa_rt_event_record(e0) || pa_rt_memset(d_band, 0, btot * sizeof(double)) || pa_rt_memset(s->d_fail, 0, sizeof(int)) ||
         pa_k_bj_band_assemble(s->d_bm_src, s->d_bm_dst, s->d_bm_chunk_blk, s->d_bm_chunk_first, s->bm_nchunks, s->d_boff,
                               d_pv, d_band) ||
+        /* new values can split a class of identical blocks: every block that read another one's records at the
+         * create is compared with it again, on the assembled bands, and reads its own records if they differ
+         * (sharing only shrinks here; blocks that became equal are found by a fresh create) */
+        (s->share_members > 0 &&
+         (pa_rt_memset(s->d_share_cnt, 0, 2 * sizeof(unsigned long long)) ||
+          pa_k_bj_share_check(s->d_share_list, s->share_members, s->d_rep, s->d_nrows, s->d_bw, s->d_boff, d_band, s->d_off,
+                              s->d_off2, s->d_off_read, s->d_off2_read, s->d_share_cnt))) ||
         pa_bj_factor_launch(s, s->d_slist, s->d_blist, s->d_boff, d_band, s->d_fail, &fail))
       rc = BJU_FAIL("factorising the diagonal blocks on the device failed: %s", pa_rt_error());
     *spd_fail = fail;
+    if (!rc && s->share_members > 0) {
+      unsigned long long cnt[2];
+      if (pa_rt_d2h(cnt, s->d_share_cnt, sizeof(cnt))) rc = BJU_FAIL("%s", pa_rt_error());
+      else { s->shared_blocks = (int)cnt[0]; s->shared_elems2 = (long long)cnt[1]; }
+    }
   }
   if (!rc && fail == 0) {     /* the second layouts, from the new plain records */
     if (s->d_Lg4 && pa_bj_launch_g4(s)) rc = BJU_FAIL("k_bj_g4_setup failed");
@@ -157,6 +169,13 @@ int pa_bj_update_stat(const char* key, double* value) {
   else if (!strcmp(key, "bj_update_copy_s")) *value = on ? s->upd_copy_s : 0.0;
   else if (!strcmp(key, "bj_update_kernel_s")) *value = on ? s->upd_kernel_s : 0.0;
   else if (!strcmp(key, "bj_update_total_s")) *value = on ? s->upd_total_s : 0.0;
+  /* the classes of identical blocks (bj_share.h): classes at the create, blocks that read another block's records
+   * now (after a refresh: those that still do), bytes of the one-copy records that are read at all */
+  else if (!strcmp(key, "bj_share_classes")) *value = on ? s->share_classes : 0;
+  else if (!strcmp(key, "bj_shared_blocks")) *value = on ? s->shared_blocks : 0;
+  else if (!strcmp(key, "bj_share_distinct_g4_bytes"))
+    *value = on && s->d_Lg4 ? (s->g4_bits == 32 ? 4.0 : 8.0) * (double)(s->lay.tot2 - s->shared_elems2) : 0.0;
+  else if (!strcmp(key, "bj_share_s")) *value = on ? s->share_s : 0.0;
   else if (!strcmp(key, "bj_records_address")) *value = on ? (double)(size_t)s->d_Lf : 0.0;
   else if (!strcmp(key, "bj_g4_address")) *value = on ? (double)(size_t)s->d_Lg4 : 0.0;
   else if (!strcmp(key, "bj_coarse_max_dofs")) *value = PA_COARSE_MAX_DOFS;

@@ -90,6 +90,8 @@ void preAlps_BlockJacobiFree(void) {
   pa_rt_free(s->d_map_f); pa_rt_free(s->d_map_b);
   pa_rt_free(s->d_Lf); pa_rt_free(s->d_Lb); pa_rt_free(s->d_invd_f); pa_rt_free(s->d_invd_b);
   pa_rt_free(s->d_Lf2); pa_rt_free(s->d_Lb2); pa_rt_free(s->d_off2); pa_rt_free(s->d_Lg4);
+  pa_rt_free(s->d_off_read); pa_rt_free(s->d_off2_read); pa_rt_free(s->d_rep); pa_rt_free(s->d_share_list); pa_rt_free(s->d_share_cnt);
+  free(s->h_rep);
   for (int c = 0; c < PA_BJ_MAX_CLASSES; ++c) pa_rt_free(s->d_class_list[c]);
   pa_bj_layout_free(&s->lay);
   free(s->h_row0); free(s->h_nrows); free(s->h_bw); free(s->h_grow0); free(s->h_map_f); free(s->h_is_nd);
@@ -110,6 +112,7 @@ typedef struct {
   int dev_factor;             /* PREALPS_BJ_FACTOR != host */
   int wide_from;              /* PREALPS_BJ_WIDE_FROM, negative: absent */
   int want_g4, want_pairs;    /* PREALPS_BJ_G4 / PREALPS_BJ_PAIRS != 0 */
+  int share;                  /* PREALPS_BJ_SHARE != 0: identical blocks read one block's records (bj_share.h) */
 } bj_switches_t;
 
 /* Storage bits of a factor: the value set through the API, else the switch `name` (double / single). */
@@ -145,7 +148,67 @@ static int bj_read_switches(bj_switches_t* sw) {
   if (e && *e) { sw->wide_from = atoi(e); if (sw->wide_from < 0) sw->wide_from = 0; }
   sw->want_g4 = !(getenv("PREALPS_BJ_G4") && atoi(getenv("PREALPS_BJ_G4")) == 0);
   sw->want_pairs = !(getenv("PREALPS_BJ_PAIRS") && atoi(getenv("PREALPS_BJ_PAIRS")) == 0);
+  sw->share = !(getenv("PREALPS_BJ_SHARE") && atoi(getenv("PREALPS_BJ_SHARE")) == 0);
   return 0;
+}
+
+/* ---- stage 1b: the classes of identical blocks (bj_share.h) -------------------- */
+/* Before the bands are handed on: a narrow block whose band is assembled row-major may read the records of the
+ * lowest-numbered block with the same rows, bandwidth and band bytes (with PREALPS_BJ_FACTOR=host the bands hold
+ * the factor: identical factors share as well).  Wide / entry-list blocks and sparse-factored blocks read their
+ * own.  share == 0 (PREALPS_BJ_SHARE=0): every block its own. */
+static int bj_share_pass(pa_bj_t* s, const pa_bj_build_t* B, int share) {
+  const int np = B->np;
+  const double t0 = pa_wtime();
+  s->h_rep = (int*)malloc((size_t)(np ? np : 1) * sizeof(int));
+  char* el = (char*)malloc((size_t)(np ? np : 1));
+  if (!s->h_rep || !el) { free(el); return BJ_FAIL("out of host memory for the classes of %d blocks", np); }
+  for (int p = 0; p < np; ++p) el[p] = share && !B->is_nd[p] && B->bands[p] && B->bw[p] <= s->lay.wide_from;
+  const pa_bj_share_in_t in = {.np = np, .nrows = B->nrows, .bw = B->bw, .eligible = el, .bands = B->bands,
+                               .threads = pa_host_threads(), .hash_mask = ~0ull};
+  const int rc = pa_bj_share_classes(&in, s->h_rep, &s->share_classes);
+  free(el);
+  if (rc) return BJ_FAIL("out of host memory for the classes of %d blocks", np);
+  s->share_on = share; s->share_members = 0; s->shared_elems2 = 0;
+  for (int p = 0; p < np; ++p)
+    if (s->h_rep[p] != p) { ++s->share_members; s->shared_elems2 += 8LL * ((B->nrows[p] + 7) / 8) * (B->bw[p] + 4); }
+  s->shared_blocks = s->share_members;
+  s->share_s = pa_wtime() - t0;
+  if (getenv("PREALPS_SETUP_TRACE"))
+    fprintf(stderr, "[setup] block classes (%d of %d blocks share, %d classes)  %.3f s\n", s->share_members, np,
+            s->share_classes, s->share_s);
+  return 0;
+}
+
+/* The read offsets on the device, and what the refresh's k_bj_share_check needs: rep and the list of the blocks
+ * that read another block's records. */
+static int bj_upload_share(pa_bj_t* s) {
+  const int np = s->np, nm = s->share_members;
+  const size_t np1 = (size_t)np + 1;
+  const pa_bj_layout_t* L = &s->lay;
+  long long* h = (long long*)malloc(2 * np1 * sizeof(long long));
+  int* list = (int*)malloc((size_t)(nm ? nm : 1) * sizeof(int));
+  int rc = 0, x = 0;
+  if (!h || !list) { free(h); free(list); return BJ_FAIL("out of host memory for the read offsets of %d blocks", np); }
+  for (int p = 0; p < np; ++p) {
+    h[p] = L->off[s->h_rep[p]]; h[np1 + p] = L->off2[s->h_rep[p]];
+    if (s->h_rep[p] != p) list[x++] = p;
+  }
+  /* (Up to 8 -- and 64 -- members of a class as own readers, the others spread over them round-robin, against
+   * contention for the L2 channels of one record: measured, no gain -- DESIGN.md section 4p.) */
+  h[np] = L->off[np]; h[np1 + np] = L->off2[np];
+  s->d_off_read = (long long*)pa_rt_malloc(np1 * sizeof(long long));
+  if (s->d_off2) s->d_off2_read = (long long*)pa_rt_malloc(np1 * sizeof(long long));
+  s->d_rep = (int*)pa_rt_malloc((size_t)(np ? np : 1) * sizeof(int));
+  s->d_share_list = (int*)pa_rt_malloc((size_t)(nm ? nm : 1) * sizeof(int));
+  s->d_share_cnt = (unsigned long long*)pa_rt_malloc(2 * sizeof(unsigned long long));
+  if (!s->d_off_read || (s->d_off2 && !s->d_off2_read) || !s->d_rep || !s->d_share_list || !s->d_share_cnt ||
+      pa_rt_h2d(s->d_off_read, h, np1 * sizeof(long long)) ||
+      (s->d_off2 && pa_rt_h2d(s->d_off2_read, h + np1, np1 * sizeof(long long))) ||
+      pa_rt_h2d(s->d_rep, s->h_rep, (size_t)np * sizeof(int)) || pa_rt_h2d(s->d_share_list, list, (size_t)nm * sizeof(int)))
+    rc = BJ_FAIL("uploading the read offsets failed: %s", pa_rt_error());
+  free(h); free(list);
+  return rc;
 }
 
 /* ---- stage 2: the device arrays of the records ----------------------------------- */
@@ -441,10 +504,12 @@ static int bj_second_layouts(pa_bj_t* s, int band_bits) {
 static void bj_fill_plan(pa_bj_t* s) {
   pa_bj_plan_t* pl = &s->plan;
   const pa_bj_layout_t* L = &s->lay;
-  pl->nparts = s->np; pl->row0 = s->d_row0; pl->nrows = s->d_nrows; pl->bw = s->d_bw; pl->off = s->d_off;
+  /* the apply kernels take off[p] / off2[p] as the base of a block's records only: they get the READ offsets (a
+   * block that repeats an earlier one reads that one's records, bj_share.h); invd, the maps and row0 stay per block */
+  pl->nparts = s->np; pl->row0 = s->d_row0; pl->nrows = s->d_nrows; pl->bw = s->d_bw; pl->off = s->d_off_read;
   pl->map_f = s->d_map_f; pl->map_b = s->d_map_b; pl->Lf = s->d_Lf; pl->Lb = s->d_Lb;
   pl->invd_f = s->d_invd_f; pl->invd_b = s->d_invd_b;
-  pl->Lf2 = s->d_Lf2; pl->Lb2 = s->d_Lb2; pl->off2 = s->d_off2;
+  pl->Lf2 = s->d_Lf2; pl->Lb2 = s->d_Lb2; pl->off2 = s->d_off2_read;
   pl->Lg4 = s->d_Lg4; pl->g4_bits = s->d_Lg4 ? s->g4_bits : 0; pl->class_g4 = L->class_g4; pl->class_bmax = L->class_bmax;
   pl->nclass = L->nclass; pl->class_R = L->class_R; pl->class_count = L->class_count;
   pl->class_wmax = L->class_wmax;
@@ -510,6 +575,7 @@ int preAlps_BlockJacobiCreate(CPLM_Mat_CSR_t* A, int* rowPos, int sizeRowPos, in
     if (lrc == PA_BJ_BANDWIDTH) rc = BJ_FAIL("%s", err);
     else if (lrc) rc = BJ_FAIL("out of host memory for the layout of %d blocks", in.np);
   }
+  if (!rc) rc = bj_share_pass(s, &B, sw.share);
   if (!rc) rc = bj_alloc_records(s);
   if (!rc) rc = bj_layout_host(s, &B);
   if (!rc) rc = bj_upload_classes(s);
@@ -519,6 +585,7 @@ int preAlps_BlockJacobiCreate(CPLM_Mat_CSR_t* A, int* rowPos, int sizeRowPos, in
     rc = pa_bj_nd_handoff("preAlps_BlockJacobiCreate", A, in.np, B.is_nd, s->lay.nnd, B.row0, B.nrows, in.grow, in.m, sw.nd_bits,
                           in.row_off);
   if (!rc) rc = bj_second_layouts(s, sw.band_bits);
+  if (!rc) rc = bj_upload_share(s);
   if (!rc) rc = bj_keep_decisions(s, &B, &in);
   pa_bj_build_free(&B);
   if (rc) { preAlps_BlockJacobiFree(); return rc; }

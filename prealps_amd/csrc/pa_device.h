@@ -404,6 +404,12 @@ int pa_k_bj_apply(const pa_bj_plan_t* pl, int ts, const double* in, double* out)
  * map (bj_band_map.h); band zeroed beforehand, everything on the device. */
 int pa_k_bj_band_assemble(const unsigned* src, const unsigned* dst, const int* chunk_blk, const unsigned* chunk_first,
                           size_t nchunks, const long long* boff, const double* pv, double* band);
+/* bj_refactor.hip: for the `count` blocks p of `list`, off_read[p] / off2_read[p] = off / off2 of rep[p] if the assembled
+ * bands of p and rep[p] are the same 64-bit words, of p itself if not; cnt[0] += blocks that still share, cnt[1] += the
+ * elements of their second records (cnt zeroed by the caller; off2 / off2_read may be null) */
+int pa_k_bj_share_check(const int* list, int count, const int* rep, const int* nrows, const int* bw, const long long* boff,
+                        const double* band, const long long* off, const long long* off2, long long* off_read,
+                        long long* off2_read, unsigned long long* cnt);
 
 /* ---- coarse correction of the two-level block-Jacobi preconditioner (coarse.hip) -------------------------
  * out(:, :ncols) += Z Einv Z^T in(:, :ncols), every array on the device, fp64.  Z as zv (m x k row major: row i of

@@ -2,7 +2,7 @@
  * pa_host.h -- internal declarations shared by the C host sources of
  * libprealps_hip.so (context.c, operator.c, the preconditioner: block_jacobi.c, bj_update.c, bj_coarse.c, which
  * share bj_priv.h, and the solver: ecg.c, ecg_start.c, ecg_loops.c, which share ecg_priv.h).  spmm_plan.c,
- * ecg_plan.c, mtx_read.c, op_build.c, bj_band_map.c and bj_build.c stand apart: each includes its own header only
+ * ecg_plan.c, mtx_read.c, op_build.c, bj_band_map.c, bj_build.c and bj_share.c stand apart: each includes its own header only
  * (and pa_alloc.h, the allocation of large host arrays; bj_build.h takes the window rule from pa_device.h).
  */
 #ifndef PA_HOST_H
