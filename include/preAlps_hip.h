@@ -182,13 +182,28 @@ int preAlps_BlockJacobiUpdateValues(void);
  * (device), "bj_coarse_setup_s" (host seconds of the last build with its upload), "bj_coarse_builds" (the set and
  * every refresh since), "bj_coarse_applies", "bj_coarse_einv_address": 0 without a coarse space; and
  * "bj_coarse_max_dofs".
- *   Refused, the preconditioner left as it was (a coarse space set earlier included): no operator or no
- * preconditioner; more than one process or a preAlps_hip_loopback shard; plan-only mode; k out of range; ldv < N; a
- * non-finite entry of V; naggr * k above the cap; an empty aggregate or one out of range; a singular E. */
+ *   Several processes (preAlps_hip_set_world / the MPI binding): the call is collective and gives the Z and E one
+ * process would form from the same matrix, partition, vectors and aggregates.  Every rank passes the same global V (all
+ * N rows, as b of preAlps_ECGSolveSystem) and the same part_aggregate -- nparts entries for the parts of ALL ranks, an
+ * aggregate may span ranks -- or NULL: one aggregate per part when the global nparts * k fits the cap, otherwise every
+ * rank cuts the quotient graph of its own parts (edges to other ranks' parts dropped) into max(1, floor(floor(cap / k)
+ * * np_rank / nparts)) aggregates, numbered rank after rank, so that no default aggregate spans ranks.  Every rank forms
+ * its share E_r from its own rows, the shares are summed by the all-reduce hook, and every rank factors the same bits:
+ * a singular E is refused on all ranks alike; what one rank alone meets (a non-finite entry in its copy of V, no
+ * memory, a failed upload) is agreed on before any rank returns, and the ranks not at fault report that another process
+ * refused.  The device keeps the rows of Einv that the rank's own aggregates need ("bj_coarse_bytes" is the rank's
+ * own), and an apply costs exactly one all-reduce more (of the nc x stride coarse vector, on the library stream).
+ * preAlps_BlockJacobiUpdateValues refreshes collectively; preAlps_BlockJacobiClearCoarseSpace must be called on every
+ * rank.  Nothing about speed on two or more devices has been measured.
+ *   Refused, the preconditioner left as it was (a coarse space set earlier included) -- on several processes on every
+ * rank: no operator or no preconditioner; a preAlps_hip_loopback shard (it lacks the other ranks' rows of E); plan-only
+ * mode; k out of range; ldv < N; a non-finite entry of V; naggr * k above the cap; an empty aggregate or one out of
+ * range; a singular E. */
 int preAlps_BlockJacobiSetCoarseSpace(int k, const double* V, int ldv, const int* part_aggregate, int naggr);
 int preAlps_BlockJacobiClearCoarseSpace(void);
-/* The aggregates of the attached coarse space: part_aggregate[p] for every part (nparts ints, the caller's array) --
- * what the caller gave, or the default the library chose -- and *naggr (may be NULL).  Refused without a coarse space. */
+/* The aggregates of the attached coarse space: part_aggregate[p] for every part (nparts ints, the caller's array; on
+ * several processes the parts of all of them) -- what the caller gave, or the default the library chose -- and *naggr
+ * (may be NULL).  Refused without a coarse space. */
 int preAlps_BlockJacobiGetCoarseAggregates(int* part_aggregate, int* naggr);
 /* k-way partition of the adjacency graph of a square matrix with a structurally symmetric
  * pattern (0-based CSR, diagonal stored) into nparts compact, balanced parts:
@@ -378,7 +393,7 @@ int preAlps_ECGSolveGuess(preAlps_ECG_t* ecg, int nrhs, const double* rhs, int l
  * bit for bit, after no iteration (*n_hist = 0).
  *   Refused (the message names the entry point): everything preAlps_ECGInitializeGuess refuses -- nrhs < 1 or
  * enlFac % nrhs != 0, s against the number of parts, ORTHODIR_FUSED, an operator built for another process group than
- * the one that calls, ADAPT_BS and the coarse space on several processes, a right-hand side of norm zero, a start residual that is not finite, a system that starts at exactly zero
+ * the one that calls, ADAPT_BS on several processes, a right-hand side of norm zero, a start residual that is not finite, a system that starts at exactly zero
  * beside ones that do not -- and ldb, ldx0 or ldx < N, b or x == NULL, a right-hand side that is not finite, unknown
  * flags.  After a refusal the operator and the preconditioner are usable as before.  HIP graphs and PREALPS_ECG_POLL
  * are off for such a solver, as for several systems.  The solver object is released before the entry returns.

@@ -16,8 +16,11 @@
 typedef struct {
   int on;
   int k, naggr, nc, nchunks, n;
+  int nparts;                 /* entries of part_aggregate */
   double* V;                  /* the caller's vectors, n x k column major, in the caller's order and units */
-  int* part_aggregate;        /* np */
+  int* part_aggregate;        /* the operator's nparts: the parts of all processes */
+  int multi;                  /* attached on several processes: d_Einv holds the nrows rows of the inverse listed in d_rows */
+  int nrows; int* d_rows;
   double* d_zv; int* d_ch_row0; int* d_ch_nrows; int* d_ch_aggr; int* d_agg_ptr; int* d_agg_chunk;
   double* d_Einv; double* d_partial; double* d_c; double* d_y;
   pa_coarse_plan_t plan;
@@ -90,7 +93,8 @@ int pa_bj_launch_pairs(const pa_bj_t* s);
 
 /* ---- bj_coarse.c ------------------------------------------------------------------------------------------ */
 void pa_bj_coarse_release(pa_bj_coarse_t* co);
-/* after new values: zv, E and Einv again into the same device arrays; a failure drops the coarse space */
+/* after new values: zv, E and Einv again into the same device arrays; a failure drops the coarse space.  Collective on
+ * several processes, where the failure of one drops it on all. */
 int pa_bj_coarse_refresh(pa_bj_t* s, const pa_operator_info_t* op);
 
 #endif

@@ -131,15 +131,18 @@ int preAlps_BlockJacobiUpdateValues(void) {
     return BJU_FAIL("the preconditioner was created with PREALPS_BJ_FACTOR=host, its records come from the host "
                     "Cholesky: free and create instead");
   int rc = 0, wrote = 0, spd_fail = 0;
+  /* a coarse space on several processes is refreshed collectively below: a process whose own factor fails tells the
+   * others before it returns, so that none waits for it there */
+  const int co_ranks = s->co.on && s->co.multi;
   s->upd_copy_s = s->upd_kernel_s = 0.0;
   if (s->np - s->nd_blocks > 0) {
     rc = bj_ensure_band_map(s, op);
-    if (rc) return rc;                      /* (nothing of the factor has been touched) */
+    if (rc) { if (co_ranks) pa_ranks_agree(1, NULL); return rc; }      /* (nothing of the factor has been touched) */
     rc = bj_refactor_bands(s, op, &wrote, &spd_fail);
     if (!rc && spd_fail > 0)
       rc = BJU_FAIL("diagonal block is not SPD (global row %d)",
                     pa_bj_fail_global_row(s->row_off, s->h_map_f, s->h_row0, s->h_nrows, s->np, spd_fail));
-    if (rc && !wrote) return rc;
+    if (rc && !wrote) { if (co_ranks) pa_ranks_agree(1, NULL); return rc; }
   }
   /* the blocks with the sparse factor: created again from the new panel, with the arguments of the create */
   if (!rc && s->nd_blocks > 0) {
@@ -148,10 +151,15 @@ int preAlps_BlockJacobiUpdateValues(void) {
     if (!rc) { s->nd_rebuilt = s->nd_blocks; s->factor_bytes = 2.0 * 8.0 * (double)s->lay.tot + pa_nd_factor_bytes(); }
   }
   /* the records hold the new values in part, or not even a factor: there is no old preconditioner to go back to */
-  if (rc) { preAlps_BlockJacobiFree(); return rc; }
+  if (rc) { if (co_ranks) pa_ranks_agree(1, NULL); preAlps_BlockJacobiFree(); return rc; }
   ++s->updates;
   pa_bj_values_epoch_sync();
-  if (s->co.on) rc = pa_bj_coarse_refresh(s, op);
+  if (co_ranks && pa_ranks_agree(0, NULL)) {
+    if (pa_rt_sync()) { /* nothing more to report */ }
+    pa_bj_coarse_release(&s->co);
+    pa_bj_apply_epoch_bump();
+    rc = BJU_FAIL("another process could not refresh its block factor: the coarse space was dropped, the refreshed block factor stays");
+  } else if (s->co.on) rc = pa_bj_coarse_refresh(s, op);
   s->upd_total_s = pa_wtime() - t_all;
   return rc;
 }

@@ -3,6 +3,8 @@
 // stream.  All of it is bandwidth work: two passes over a panel (in, then out read-modify-write), one over the
 // m x k array zv each, and one streaming pass over the nc x nc inverse.  No atomics: every sum has one fixed
 // order (lane, wavefront, workgroup, chunk list), so two applies of the same input agree in bits.
+// Several processes: the coarse vector is summed over the ranks between the gather and the product with the inverse,
+// of which a rank keeps the rows its own aggregates need (k_coarse_einv_rows).
 #include "kernels_common.h"
 
 namespace {
@@ -104,6 +106,49 @@ __global__ __launch_bounds__(WG) void k_coarse_einv(int nc, const double* __rest
   }
 }
 
+// y[rows[x]] = slab[x] . c for the nrows listed rows of the inverse (several processes: a rank keeps the rows its own
+// aggregates need).  k_coarse_einv with a row list: a workgroup owns CO_RB consecutive entries of the list and streams
+// their slab rows once, 8 bytes per lane, coalesced; the fold is the same -- lane, wavefront, the four wavefronts
+// through LDS in a fixed order -- so a row's sum has one order.  Rows of y outside the list are not written.
+template <int TS>
+__global__ __launch_bounds__(WG) void k_coarse_einv_rows(int nc, int nrows, const int* __restrict__ rows,
+                                                         const double* __restrict__ slab, const double* __restrict__ c,
+                                                         double* __restrict__ y) {
+  __shared__ double red[WG / 64][CO_RB][TS];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int x0 = blockIdx.x * CO_RB;
+  double acc[CO_RB][TS];
+#pragma unroll
+  for (int rr = 0; rr < CO_RB; ++rr)
+#pragma unroll
+    for (int cc = 0; cc < TS; ++cc) acc[rr][cc] = 0.0;
+  for (int j = tid; j < nc; j += WG) {
+    double cj[TS];
+    load_row<TS>(c, (size_t)j, cj);
+#pragma unroll
+    for (int rr = 0; rr < CO_RB; ++rr) {
+      const double e = x0 + rr < nrows ? slab[(size_t)(x0 + rr) * nc + j] : 0.0;
+#pragma unroll
+      for (int cc = 0; cc < TS; ++cc) acc[rr][cc] += e * cj[cc];
+    }
+  }
+#pragma unroll
+  for (int rr = 0; rr < CO_RB; ++rr)
+#pragma unroll
+    for (int cc = 0; cc < TS; ++cc) {
+      double v = acc[rr][cc];
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+      if (lane == 0) red[wave][rr][cc] = v;
+    }
+  __syncthreads();
+  if (tid < CO_RB * TS) {
+    const int rr = tid / TS, cc = tid % TS;
+    if (x0 + rr < nrows)
+      y[(size_t)rows[x0 + rr] * TS + cc] = ((red[0][rr][cc] + red[1][rr][cc]) + red[2][rr][cc]) + red[3][rr][cc];
+  }
+}
+
 // out[i][c] += sum_a zv[i][a] y[g*k + a][c] over the rows of the chunk, the lane layout of k_coarse_restrict
 template <int TS>
 __global__ __launch_bounds__(WG) void k_coarse_prolong_add(int k, int ncols, const double* __restrict__ zv,
@@ -141,6 +186,22 @@ __global__ __launch_bounds__(WG) void k_coarse_prolong_add(int k, int ncols, con
 
 }  // namespace
 
+extern "C" int pa_allreduce(double* dev_buf, int count);     // pa_host.h: the sum over the processes, on the library stream
+
+extern "C" int pa_k_coarse_einv_rows(int nc, int nrows, const int* rows, const double* slab, const double* c, double* y, int ts) {
+  if (!rows || !slab || !c || !y) {
+    pa_rt_set_error("pa_k_coarse_einv_rows: wrong test 'rows != NULL && slab != NULL && c != NULL && y != NULL'");
+    return 1;
+  }
+  if (nc < 1 || nrows < 1 || nrows > nc) {
+    pa_rt_set_error("pa_k_coarse_einv_rows: %d rows of %d coarse unknowns", nrows, nc);
+    return 1;
+  }
+  TS_DISPATCH(ts, PA_LAUNCH(k_coarse_einv_rows<TS_>, dim3((nrows + CO_RB - 1) / CO_RB), dim3(WG), 0, cur_stream(), nc, nrows,
+                            rows, slab, c, y));
+  return kfail("k_coarse_einv_rows");
+}
+
 extern "C" int pa_k_coarse_apply(const pa_coarse_plan_t* pl, int ts, int ncols, const double* in, double* out) {
   if (!pl || !pl->zv || !pl->Einv || !pl->partial || !pl->c || !pl->y || pl->nchunks <= 0 || pl->nc <= 0 ||
       pl->k < 1 || pl->k > CO_MAXK || pl->nc != pl->naggr * pl->k) {
@@ -158,9 +219,17 @@ extern "C" int pa_k_coarse_apply(const pa_coarse_plan_t* pl, int ts, int ncols, 
   PA_LAUNCH(k_coarse_gather, dim3((nc * ts + WG - 1) / WG), dim3(WG), 0, cur_stream(), k, ts, nc, pl->agg_ptr,
             pl->agg_chunk, pl->partial, pl->c);
   if (kfail("k_coarse_gather")) return 1;
-  TS_DISPATCH(ts, PA_LAUNCH(k_coarse_einv<TS_>, dim3((nc + CO_RB - 1) / CO_RB), dim3(WG), 0, cur_stream(), nc, pl->Einv,
-                            pl->c, pl->y));
-  if (kfail("k_coarse_einv")) return 1;
+  if (pl->rows) {      // several processes: c summed over the ranks, then the rank's own rows of the inverse
+    if (pa_allreduce(pl->c, nc * ts)) {
+      pa_rt_set_error("pa_k_coarse_apply: the all-reduce of the %d x %d coarse vector failed", nc, ts);
+      return 1;
+    }
+    if (pa_k_coarse_einv_rows(nc, pl->nrows, pl->rows, pl->Einv, pl->c, pl->y, ts)) return 1;
+  } else {
+    TS_DISPATCH(ts, PA_LAUNCH(k_coarse_einv<TS_>, dim3((nc + CO_RB - 1) / CO_RB), dim3(WG), 0, cur_stream(), nc, pl->Einv,
+                              pl->c, pl->y));
+    if (kfail("k_coarse_einv")) return 1;
+  }
   TS_DISPATCH(ts, PA_LAUNCH(k_coarse_prolong_add<TS_>, dim3(pl->nchunks), dim3(WG), 0, cur_stream(), k, ncols, pl->zv,
                             pl->ch_row0, pl->ch_nrows, pl->ch_aggr, pl->y, out));
   return kfail("k_coarse_prolong_add");

@@ -18,7 +18,7 @@
  * entry point the refusals name.
  *   Several processes: every rank passes its own rows, A X0 is the distributed product, the start's local sums are
  * reduced in one all-reduce, and in the iteration the per-system sums ride on the collective of the residual norm
- * (pv->ride); what one rank alone can find wrong is agreed on before any rank returns (ranks_agree).
+ * (pv->ride); what one rank alone can find wrong is agreed on before any rank returns (pa_ranks_agree).
  *   The caller's own system on several processes: b, x0 and x stay the caller's global arrays, the gather and the
  * scatter touch the rows this rank owns, the caller's-units sums of the start take one more all-reduce
  * (reduce_system_sums), and in the iteration they ride like the sums of several systems (pv->ride_sys).
@@ -54,7 +54,7 @@ int preAlps_hip_system_columns(int s, int* pcol) {
  * solver's pool), NULL: one is allocated.  The collective is entered whatever the upload of the flag returned -- a
  * process whose copy failed reports its failure afterwards, its peers are not left waiting for it; only a process
  * that holds no word and cannot allocate one (8 bytes) has nothing to hand to the hook and fails alone. */
-static int ranks_agree(int bad, double* word) {
+int pa_ranks_agree(int bad, double* word) {
   if (pa_world_size() == 1 || pa_comm_is_loopback()) return bad != 0;
   if (pa_mpi_active()) return pa_mpi_agree(bad);
   double h = bad ? 1.0 : 0.0;
@@ -69,7 +69,7 @@ static int ranks_agree(int bad, double* word) {
 
 /* One start, as its stages see it.  multi: several processes (the one-shard rehearsal of preAlps_hip_loopback counts as
  * one of several): every rank passes its own rows.  What a rank finds wrong with ITS arguments or resources is a local
- * verdict: it does not return on it but takes it to ranks_agree, so that either every rank goes on or every rank
+ * verdict: it does not return on it but takes it to pa_ranks_agree, so that either every rank goes on or every rank
  * returns the refusal and none is left waiting in a collective.  One process: every refusal returns at once. */
 typedef struct {
   const char* who; preAlps_ECG_t* ecg; ecg_priv_t* pv; const pa_operator_info_t* op;
@@ -158,7 +158,7 @@ static int start_from_guess(const start_t* c, staging_t* st, int rc) {
   double* const d_red = pv->d_grp;
   int nblk = 0;
   /* A X0 is the distributed product, with its halo exchange: no process enters it unless all of them do */
-  if (multi && ranks_agree(rc, d_red + 47)) {
+  if (multi && pa_ranks_agree(rc, d_red + 47)) {
     if (!rc) FAIL_AS(c->who, "another process of the group could not stage its rows (its own message says why)");
     return START_QUIT;
   }
@@ -321,7 +321,7 @@ int pa_ecg_start_systems(const char* who, preAlps_ECG_t* ecg, int nrhs, const do
     /* (plan-only mode has no device: the verdicts on the arguments are agreed on, then the start is refused) */
     const int have = !bad && !pa_operator_plan_only() && _preAlps_ECGMalloc(ecg) == 0;
     if (!bad && !pa_operator_plan_only() && !have) bad = 1;
-    if (ranks_agree(bad, have ? priv_of(ecg)->d_grp + 47 : NULL)) {    /* (a word of the pool; pa_ecg_reset_state zeroes it again) */
+    if (pa_ranks_agree(bad, have ? priv_of(ecg)->d_grp + 47 : NULL)) {    /* (a word of the pool; pa_ecg_reset_state zeroes it again) */
       if (have) _preAlps_ECGFree(ecg);
       return bad ? 1 : FAIL_AS(who, "another process of the group refused this start (its own message says why)");
     }
@@ -340,7 +340,7 @@ int pa_ecg_start_systems(const char* who, preAlps_ECG_t* ecg, int nrhs, const do
     _preAlps_ECGFree(ecg);
     return FAIL_AS(who, "locPbSize %d differs from the operator's %d rows", ecg->locPbSize, m);
   }
-  /* from here on every process of several holds a solver, and a failure of its own (rc) travels: to ranks_agree ahead
+  /* from here on every process of several holds a solver, and a failure of its own (rc) travels: to pa_ranks_agree ahead
    * of the product of a guess, whose halo exchange the peers would wait in, and as the first word of the one
    * all-reduce of the start's sums */
   int rc = pa_ecg_reset_state(ecg, pv, k, x0 != NULL, sys && sys->metric) ? 1 : 0;

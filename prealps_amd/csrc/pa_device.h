@@ -418,7 +418,12 @@ int pa_k_bj_share_check(const int* list, int count, const int* rep, const int* n
  * apply is reproducible in bits): k_coarse_restrict, one workgroup per chunk, partial[chunk][a][c] = sum_i zv[i][a]
  * in[i][c]; k_coarse_gather + k_coarse_einv, c[g*k + a][:] = the sum of aggregate g's chunk partials in list
  * order and y = Einv c in one pass over Einv; k_coarse_prolong_add, out[i][c] += sum_a zv[i][a] y[g(i)*k + a][c].
- * partial: nchunks * k * 16 doubles, c and y: nc * 16 doubles (scratch the plan owns). */
+ * partial: nchunks * k * 16 doubles, c and y: nc * 16 doubles (scratch the plan owns).
+ *   Several processes (rows != NULL): zv and the chunk lists are those of the rank's rows, agg_ptr lists all naggr
+ * aggregates (empty where the rank has no chunk, so the gather leaves zeros there), and Einv holds only the nrows rows
+ * of the inverse named in `rows` (ascending; the rows of the aggregates with a chunk here), nrows x nc row major.
+ * The apply is restrict, gather, pa_allreduce(c, nc * ts), k_coarse_einv_rows (y[rows[x]] = Einv[x] . c, the other
+ * rows of y are neither written nor read), prolong: one all-reduce more than on one process, on the library stream. */
 typedef struct {
   int m, k, naggr, nc, nchunks;
   const double* zv;
@@ -426,8 +431,12 @@ typedef struct {
   const int* agg_ptr; const int* agg_chunk;
   const double* Einv;
   double* partial; double* c; double* y;
+  int nrows; const int* rows;
 } pa_coarse_plan_t;
 int pa_k_coarse_apply(const pa_coarse_plan_t* pl, int ts, int ncols, const double* in, double* out);
+/* y[rows[x]][:] = slab[x][:] . c for x < nrows (slab: nrows x nc row major, c and y: nc rows of ts doubles, rows: nrows
+ * distinct ids in [0, nc)); one fixed order of additions per row, no atomics.  ts: 2, 4, 8 or 16. */
+int pa_k_coarse_einv_rows(int nc, int nrows, const int* rows, const double* slab, const double* c, double* y, int ts);
 
 /* ---- sparse block solve for large diagonal blocks (nd.c) --------------------------------- */
 /* Supernodes of a nested-dissection Cholesky factor, all blocks of the process in one numbering.

@@ -36,6 +36,9 @@ int pa_comm_is_loopback(void);
 /* sum a device buffer over the processes (no-op for one process) */
 int pa_allreduce(double* dev_buf, int count);
 long long pa_allreduce_count(void);   /* calls of the all-reduce hook so far */
+/* collective: nonzero on every process as soon as `bad` is nonzero on one (ecg_start.c); word: a device word the caller
+ * holds, NULL: one is allocated for the call */
+int pa_ranks_agree(int bad, double* word);
 int pa_exchange(const double* dev_send, const int* send_counts, double* dev_recv,
                 const int* recv_counts, const int* peers, int npeers);
 

@@ -297,7 +297,12 @@ class EcgProblem:
         (nearkernel.translations, nearkernel.rigid_body_modes).  aggregates: one aggregate id per part (numbered
         0 .. naggr - 1, none empty); None = one aggregate per part when that fits stat("bj_coarse_max_dofs"),
         otherwise the library's partition of the parts' quotient graph.  Creates the block-Jacobi factor first if
-        there is none.  A refusal raises and leaves the preconditioner (and an earlier coarse space) as it was."""
+        there is none.  A refusal raises and leaves the preconditioner (and an earlier coarse space) as it was.
+        On a distributed=True problem the call is collective: every rank passes the same GLOBAL V (all N rows) and the
+        same global aggregates (one id per part of ALL ranks, an aggregate may span ranks; None: no default aggregate
+        spans ranks, and over the cap every rank cuts the quotient graph of its own parts).  Every rank keeps only what
+        its own rows need, an apply costs one all-reduce more, and what one rank alone refuses (a NaN in its copy of V)
+        raises on every rank.  A shard= problem refuses."""
         V = np.asarray(V, dtype=np.float64)
         if V.ndim == 1:
             V = V[:, None]
@@ -323,18 +328,21 @@ class EcgProblem:
 
     def coarse_aggregates(self):
         """preAlps_BlockJacobiGetCoarseAggregates: the aggregate of every part of the attached coarse space (the
-        ones given, or the default the library chose) as an int32 array of nparts values."""
+        ones given, or the default the library chose) as an int32 array of nparts values -- on a distributed problem
+        the parts of all ranks, the same array on every rank."""
         agg, n = np.zeros(self.nparts, dtype=np.int32), C.c_int()
         check(self.L.preAlps_BlockJacobiGetCoarseAggregates(_pi(agg), C.byref(n)), "preAlps_BlockJacobiGetCoarseAggregates")
         return agg
 
     def clear_coarse_space(self):
-        """preAlps_BlockJacobiClearCoarseSpace: plain block Jacobi again, with the bits it had before."""
+        """preAlps_BlockJacobiClearCoarseSpace: plain block Jacobi again, with the bits it had before.  On a distributed
+        problem every rank must call it before the next apply or solve (the ranks' applies must launch alike)."""
         check(self.L.preAlps_BlockJacobiClearCoarseSpace(), "preAlps_BlockJacobiClearCoarseSpace")
         self._coarse = None
 
     def create_block_jacobi(self, nd_precision=None, band_precision=None, coarse=None):
-        """coarse: vectors for set_coarse_space(coarse) right after the create (default aggregates).
+        """coarse: vectors for set_coarse_space(coarse) right after the create (default aggregates; on a distributed
+        problem the global N x k array, the same on every rank, and the call is collective).
         nd_precision: storage of the sparse factors of large blocks -- None follows
         PREALPS_BJ_ND_PRECISION, "double" / "single" select it for this create (band blocks stay fp64).
         With a value, the library's setting (preAlps_hip_set_nd_precision) is 0 again afterwards: a value
