@@ -530,7 +530,9 @@ int preAlps_hip_panel_permute_solve(const CPLM_Mat_Dense_t* Z, CPLM_Mat_Dense_t*
  * 0: no class has them, e.g. PREALPS_BJ_G4=0), "bj_g4_bytes" (bytes of those records as stored: half in single
  * precision; "bj_factor_bytes" does not count them), "bj_g4_last_ring" / "bj_g4_last_bits" /
  * "bj_g4_last_pipelined" (the last launch that read them: LDS ring depth, storage bits of the records, 1 = the
- * pipelined few-blocks chain), "bj_share_classes" / "bj_shared_blocks" / "bj_share_distinct_g4_bytes" (identical
+ * pipelined few-blocks chain), "bj_g4_last_paired" (1 = that launch was the PAIR launch: two blocks of one class of
+ * identical blocks per wavefront, PREALPS_BJ_PAIR), "bj_pair_tasks" / "bj_paired_blocks" (the pair tasks of the create:
+ * wavefronts of the PAIR launch, and the blocks among them that have a partner), "bj_share_classes" / "bj_shared_blocks" / "bj_share_distinct_g4_bytes" (identical
  * diagonal blocks read one block's records, PREALPS_BJ_SHARE: classes found by the create, blocks that read another
  * block's records now -- after preAlps_BlockJacobiUpdateValues those that still do -- and the bytes of the one-copy
  * records that are read at all; "bj_share_s": seconds of the create's class pass), "ecg_graph_captures" / "ecg_graph_replays" (iteration segments captured and graphs

@@ -1195,7 +1195,8 @@ int pa_k_bj_apply(const pa_bj_plan_t* pl, int ts, const double* in, double* out)
       } else if (g_bg.armed && in == g_bg.in && out == g_bg.out) {
         g_bg.count = 0;
       }
-      rc = pa_k_bj_g4(pl, pl->class_list[c], pl->class_count[c], pl->class_wmax[c], pl->class_bmax[c], ts, ts, in, out);
+      rc = pa_k_bj_g4(pl, pl->class_list[c], pl->class_count[c], pl->class_wmax[c], pl->class_bmax[c], ts, ts, in, out,
+                      pl->class_ptask ? &pl->class_ptask[c] : nullptr);
       if (rc) return rc;
       continue;
     }

@@ -62,9 +62,9 @@
 extern "C" {
 extern const double* pa_g4_gram_prev;
 extern double* pa_g4_gram_part;
-// what the last launch was: ring depth, storage bits of the records, 1 = the pipelined few-blocks chain
-// (preAlps_hip_get_stat "bj_g4_last_ring" / "bj_g4_last_bits" / "bj_g4_last_pipelined")
-extern int pa_g4_last[3];
+// what the last launch was: ring depth, storage bits of the records, 1 = the pipelined few-blocks chain, 1 = PAIR
+// (preAlps_hip_get_stat "bj_g4_last_ring" / "bj_g4_last_bits" / "bj_g4_last_pipelined" / "bj_g4_last_paired")
+extern int pa_g4_last[4];
 }
 
 namespace {
@@ -370,26 +370,35 @@ __device__ __forceinline__ void g4_fwd_tiles(double (&T)[NC * NT], int b, int w,
 // VMEM operation among the LDS-DMAs, hand-issued so that the wait counts stay ours (the compiler's own count
 // would have to cover the chunk request and wait for it) -- and chunk (Q - 1, 1), whose wait covers everything
 // older than ITS chunk request, takes the product.  One register pair in flight; tile 0 is taken behind the sweep.
-struct g4_gram { const double* prev; unsigned base, xs; double ap, gp; };     // prev + (base + map * xs): the lane's entry of a row
+// PAIR (two blocks of one class in the wavefront, NS = 2): base, ap and gp per set; the rows of set 1 are requested
+// right behind those of set 0 (one more VMEM operation to count), and not at all when the task has no second block.
+struct g4_gram { const double* prev; unsigned base[2], xs; double ap[2], gp[2]; bool has1; };     // prev + (base + map * xs): the lane's entry of a row
 
 //
 // fp32 records (RT = float): with ring >= 4 the wait of chunk (Q - 1, 1) allows ring - 1 chunk requests to be
 // outstanding, and the load of gr.ap sits among the youngest of them (behind the request of chunk (Q, 0), in front
 // of this chunk's own) -- it is waited for explicitly before the product reads it: everything but this chunk's own
 // request, if it made one.  (ring 2: the wait above already says exactly that.)
-template <typename RT, int NC, int NT, int DQ, int Q, int H, bool GP>
+template <typename RT, int NC, int NT, int DQ, int Q, int H, bool GP, int NS>
 __device__ __forceinline__ void g4_bwd_chunk(double (&T)[NC * NT], int b, int w, const RT* __restrict__ rec,
                                              int chunk_doubles, double* lds0, int lstride, int lane, g4_lane ln,
-                                             int ring, g4_gram& gr, int trow, const unsigned (&mpk)[(NT + 3) / 4]) {
+                                             int ring, g4_gram& gr, int trow, const unsigned (&mpk)[NS * ((NT + 3) / 4)]) {
   constexpr int C = 2 * Q + H;
   const int nch = (b + 7) >> 3, nld = (chunk_doubles + 127) >> 7;
   const int cn = C - (ring - 1);
   if (cn >= 0 && C < nch - 1) g4_issue_chunk(rec, chunk_doubles, cn, lds0 + (cn & (ring - 1)) * lstride, lane);
   int extra = 0;
   if constexpr (GP && H == 0) {
-    const double* src = gr.prev + (gr.base + ((mpk[Q >> 2] >> (8 * (Q & 3))) & 255u) * gr.xs);
-    asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(gr.ap) : "v"(src) : "memory");
+    const double* src = gr.prev + (gr.base[0] + ((mpk[Q >> 2] >> (8 * (Q & 3))) & 255u) * gr.xs);
+    asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(gr.ap[0]) : "v"(src) : "memory");
     extra = ring == 2 ? 1 : 0;          // (deeper rings: not counted, the wait then covers one piece more)
+    if constexpr (NS == 2) {            // (the PAIR launch always runs ring 2)
+      if (gr.has1) {
+        const double* src1 = gr.prev + (gr.base[1] + ((mpk[(NT + 3) / 4 + (Q >> 2)] >> (8 * (Q & 3))) & 255u) * gr.xs);
+        asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(gr.ap[1]) : "v"(src1) : "memory");
+        extra = 2;
+      }
+    }
   }
   {
     // chunks requested by this sweep that lie below c: indices max(0, c - ring + 1) .. min(c - 1, nch - ring - 1)
@@ -399,9 +408,12 @@ __device__ __forceinline__ void g4_bwd_chunk(double (&T)[NC * NT], int b, int w,
   if constexpr (GP && H == 1 && Q + 1 < NT) {
     if (16 * (Q + 1) < b) {             // the rows of tile Q + 1 are here (requested before this chunk's own request)
       if constexpr (sizeof(RT) == 4) g4_wait_vm(cn >= 0 && C < nch - 1 ? nld : 0);
-      asm volatile("" : "+v"(gr.ap));
-      const double z = 16 * (Q + 1) + trow < b ? T[Q + 1] : 0.0;
-      gr.gp = __builtin_amdgcn_mfma_f64_4x4x4f64(gr.ap, z, gr.gp, 0, 0, 0);
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        asm volatile("" : "+v"(gr.ap[s]));
+        const double z = 16 * (Q + 1) + trow < b ? T[s * NT + Q + 1] : 0.0;
+        gr.gp[s] = __builtin_amdgcn_mfma_f64_4x4x4f64(gr.ap[s], z, gr.gp[s], 0, 0, 0);
+      }
     }
   }
   const unsigned cur = (unsigned)(uintptr_t)(lds_ptr)(lds0 + (C & (ring - 1)) * lstride);
@@ -409,16 +421,16 @@ __device__ __forceinline__ void g4_bwd_chunk(double (&T)[NC * NT], int b, int w,
   g4_bwd_group<RT, NC, NT, DQ, Q, 2 * H>(T, cur, w, ln);
   asm volatile("" ::: "memory");
 }
-template <typename RT, int NC, int NT, int DQ, int Q, bool GP>
+template <typename RT, int NC, int NT, int DQ, int Q, bool GP, int NS>
 __device__ __forceinline__ void g4_bwd_tiles(double (&T)[NC * NT], int b, int w, const RT* __restrict__ rec,
                                              int chunk_doubles, double* lds0, int lstride, int lane, g4_lane ln,
-                                             int ring, g4_gram& gr, int trow, const unsigned (&mpk)[(NT + 3) / 4]) {
+                                             int ring, g4_gram& gr, int trow, const unsigned (&mpk)[NS * ((NT + 3) / 4)]) {
   if constexpr (Q >= 0) {
     if (16 * Q < b) {
-      if (16 * Q + 8 < b) g4_bwd_chunk<RT, NC, NT, DQ, Q, 1, GP>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, ln, ring, gr, trow, mpk);
-      g4_bwd_chunk<RT, NC, NT, DQ, Q, 0, GP>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, ln, ring, gr, trow, mpk);
+      if (16 * Q + 8 < b) g4_bwd_chunk<RT, NC, NT, DQ, Q, 1, GP, NS>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, ln, ring, gr, trow, mpk);
+      g4_bwd_chunk<RT, NC, NT, DQ, Q, 0, GP, NS>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, ln, ring, gr, trow, mpk);
     }
-    g4_bwd_tiles<RT, NC, NT, DQ, Q - 1, GP>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, ln, ring, gr, trow, mpk);
+    g4_bwd_tiles<RT, NC, NT, DQ, Q - 1, GP, NS>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, ln, ring, gr, trow, mpk);
   }
 }
 
@@ -518,6 +530,116 @@ __device__ __forceinline__ void g4_bwd_math(double (&T)[NT], const g4_ops<DQ>& o
   g4_corner_solve<1, NT, Q>(T, o.a0, o.a1, o.a2);
 }
 
+// ---- PAIR: the plain chain on precomputed operand addresses ---------------------------------------------------
+// The PAIR launch (two column sets, three wavefronts per SIMD) has the registers for the 12 + 4 DQ LDS addresses of a
+// sweep (g4_make_pre) that the one-set launch at five wavefronts per SIMD has not: its ring is two buffers of DQ KiB
+// (a compile-time stride, as on the few-blocks chain), the buffer of chunk C is C & 1, an immediate offset of the
+// read, and a group's eight reads take no address arithmetic.  Nothing else changes: the same reads, the same wait,
+// the same matrix instructions in the same order as g4_fwd_group / g4_bwd_group with NC = 2.
+template <int NT, int DQ, int Q, int GQ, int BUF>
+__device__ __forceinline__ void g4_fwd_group_q(double (&T)[2 * NT], const g4_pre<DQ>& pre) {
+  g4_ops<DQ> o;
+  g4_read_ops_c<NT, DQ, Q, GQ, BUF>(pre, o);
+  g4_ops_wait<DQ>(o);
+  g4_corner_solve<2, NT, Q>(T, o.a0, o.a1, o.a2);
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const double yg = g4_quad_bcast<GQ>(T[c * NT + Q]);
+#pragma unroll
+    for (int dq = 0; dq < DQ; ++dq)
+      if (Q + dq < NT) T[c * NT + Q + dq] = __builtin_amdgcn_mfma_f64_4x4x4f64(o.cf[dq], yg, T[c * NT + Q + dq], 0, 0, 0);
+  }
+}
+template <int NT, int DQ, int Q, int GQ, int BUF>
+__device__ __forceinline__ void g4_bwd_group_q(double (&T)[2 * NT], const g4_pre<DQ>& pre, int blk) {
+  g4_ops<DQ> o;
+  g4_read_ops_c<NT, DQ, Q, GQ, BUF>(pre, o);
+  g4_ops_wait<DQ>(o);
+  const bool here = blk == GQ;
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    double acc = 0.0;
+#pragma unroll
+    for (int dq = 0; dq < DQ; ++dq)
+      if (Q + dq < NT) acc = __builtin_amdgcn_mfma_f64_4x4x4f64(o.cf[dq], T[c * NT + Q + dq], acc, 0, 0, 0);
+    acc += row_ror<4>(acc);
+    acc += row_ror<8>(acc);
+    T[c * NT + Q] += here ? acc : 0.0;
+  }
+  g4_corner_solve<2, NT, Q>(T, o.a0, o.a1, o.a2);
+}
+template <int NT, int DQ, int Q, int H>
+__device__ __forceinline__ void g4_fwd_chunk_q(double (&T)[2 * NT], int b, const double* __restrict__ rec, int chunk_doubles,
+                                               double* lds0, int lane, const g4_pre<DQ>& pre) {
+  constexpr int C = 2 * Q + H, LS = DQ * 128, cn = C + 1;
+  const int nch = (b + 7) >> 3, nld = (chunk_doubles + 127) >> 7;
+  if (cn < nch) g4_issue_chunk(rec, chunk_doubles, cn, lds0 + (cn & 1) * LS, lane);
+  g4_wait_vm(min(1, nch - 1 - C) * nld);
+  g4_fwd_group_q<NT, DQ, Q, 2 * H, (C & 1)>(T, pre);
+  g4_fwd_group_q<NT, DQ, Q, 2 * H + 1, (C & 1)>(T, pre);
+  asm volatile("" ::: "memory");
+}
+template <int NT, int DQ, int Q>
+__device__ __forceinline__ void g4_fwd_tiles_q(double (&T)[2 * NT], int b, const double* __restrict__ rec, int chunk_doubles,
+                                               double* lds0, int lane, const g4_pre<DQ>& pre) {
+  if constexpr (Q < NT) {
+    if (16 * Q < b) {
+      g4_fwd_chunk_q<NT, DQ, Q, 0>(T, b, rec, chunk_doubles, lds0, lane, pre);
+      if (16 * Q + 8 < b) g4_fwd_chunk_q<NT, DQ, Q, 1>(T, b, rec, chunk_doubles, lds0, lane, pre);
+      g4_fwd_tiles_q<NT, DQ, Q + 1>(T, b, rec, chunk_doubles, lds0, lane, pre);
+    }
+  }
+}
+// backward: g4_bwd_chunk with ring 2 and NS = 2 (the Gram rows of both blocks, extra = 1 or 2), the groups from `pre`
+template <int NT, int DQ, int Q, int H, bool GP>
+__device__ __forceinline__ void g4_bwd_chunk_q(double (&T)[2 * NT], int b, const double* __restrict__ rec, int chunk_doubles,
+                                               double* lds0, int lane, int blk, const g4_pre<DQ>& pre, g4_gram& gr, int trow,
+                                               const unsigned (&mpk)[2 * ((NT + 3) / 4)]) {
+  constexpr int C = 2 * Q + H, LS = DQ * 128, cn = C - 1;
+  const int nch = (b + 7) >> 3, nld = (chunk_doubles + 127) >> 7;
+  if (cn >= 0 && C < nch - 1) g4_issue_chunk(rec, chunk_doubles, cn, lds0 + (cn & 1) * LS, lane);
+  int extra = 0;
+  if constexpr (GP && H == 0) {
+    const double* src = gr.prev + (gr.base[0] + ((mpk[Q >> 2] >> (8 * (Q & 3))) & 255u) * gr.xs);
+    asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(gr.ap[0]) : "v"(src) : "memory");
+    extra = 1;
+    if (gr.has1) {
+      const double* src1 = gr.prev + (gr.base[1] + ((mpk[(NT + 3) / 4 + (Q >> 2)] >> (8 * (Q & 3))) & 255u) * gr.xs);
+      asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(gr.ap[1]) : "v"(src1) : "memory");
+      extra = 2;
+    }
+  }
+  {
+    const int lo = max(0, C - 1), hi = min(C - 1, nch - 3);
+    g4_wait_vm(max(0, hi - lo + 1) * nld + extra);
+  }
+  if constexpr (GP && H == 1 && Q + 1 < NT) {
+    if (16 * (Q + 1) < b) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        asm volatile("" : "+v"(gr.ap[s]));
+        const double z = 16 * (Q + 1) + trow < b ? T[s * NT + Q + 1] : 0.0;
+        gr.gp[s] = __builtin_amdgcn_mfma_f64_4x4x4f64(gr.ap[s], z, gr.gp[s], 0, 0, 0);
+      }
+    }
+  }
+  g4_bwd_group_q<NT, DQ, Q, 2 * H + 1, (C & 1)>(T, pre, blk);
+  g4_bwd_group_q<NT, DQ, Q, 2 * H, (C & 1)>(T, pre, blk);
+  asm volatile("" ::: "memory");
+}
+template <int NT, int DQ, int Q, bool GP>
+__device__ __forceinline__ void g4_bwd_tiles_q(double (&T)[2 * NT], int b, const double* __restrict__ rec, int chunk_doubles,
+                                               double* lds0, int lane, int blk, const g4_pre<DQ>& pre, g4_gram& gr, int trow,
+                                               const unsigned (&mpk)[2 * ((NT + 3) / 4)]) {
+  if constexpr (Q >= 0) {
+    if (16 * Q < b) {
+      if (16 * Q + 8 < b) g4_bwd_chunk_q<NT, DQ, Q, 1, GP>(T, b, rec, chunk_doubles, lds0, lane, blk, pre, gr, trow, mpk);
+      g4_bwd_chunk_q<NT, DQ, Q, 0, GP>(T, b, rec, chunk_doubles, lds0, lane, blk, pre, gr, trow, mpk);
+    }
+    g4_bwd_tiles_q<NT, DQ, Q - 1, GP>(T, b, rec, chunk_doubles, lds0, lane, blk, pre, gr, trow, mpk);
+  }
+}
+
 // forward chunk C = 2 Q + H; on entry A holds the operands of its first group (waited for)
 template <int NT, int DQ, int Q, int H>
 __device__ __forceinline__ void g4_fwd_chunk_p(double (&T)[NT], int b, const double* __restrict__ rec,
@@ -599,20 +721,45 @@ __device__ __forceinline__ void g4_bwd_tiles_p(double (&T)[NT], int b, const dou
 // launched on a 4-column slice of a wider panel), `ncol` <= 4 columns starting at `in` / `out`.
 // RT = storage type of the records (double; float = PREALPS_BJ_BAND_PRECISION=single: a record row is 16 bytes, a
 // chunk 32 (w + 4) bytes, every entry widened to fp64 before the matrix cores see it; the plain chain only).
-template <int NC, int NT, int DQ, int OCC, bool GP, bool PIPE = false, typename RT = double>
+//
+// PAIR = 1 (NC = 2, fp64 records, panels of up to 4 columns): the wavefront's two column sets are two BLOCKS that
+// read the same record (bj_share.h: one class of identical blocks), the same ncol <= 4 columns of each.  `count`
+// tasks; task pi = positions (i0, i1) of its blocks in `list`, i1 = -1: no second block.  Rows, band and record are
+// member 0's (equal for both by the class rule); row0 -- and so map_f, invd_f, the panel rows and the Gram partial
+// gpart + 32 i_c -- are each member's own.  The per-record work of a group (eight LDS reads, the address arithmetic,
+// the chunk request and its wait) is done once for both; the two corner chains are independent.  A task without
+// a second block runs set 1 on zeros: nothing of that set is loaded or stored.
+template <int NC, int NT, int DQ, int OCC, bool GP, bool PIPE = false, typename RT = double, int PAIR = 0>
 __global__ __launch_bounds__(256, OCC) void k_bj_g4(
-    const int* __restrict__ list, int count, const int* __restrict__ row0, const int* __restrict__ nrows,
-    const int* __restrict__ bw, const long long* __restrict__ off2, const int* __restrict__ map_f,
-    const RT* __restrict__ Lg4, const double* __restrict__ invd_f, int lds_per_wave, int ring, int xs, int ncol,
-    const double* __restrict__ in, double* __restrict__ out, const double* __restrict__ gprev,
-    double* __restrict__ gpart) {
+    const int* __restrict__ list, const int* __restrict__ tasks, int count, const int* __restrict__ row0,
+    const int* __restrict__ nrows, const int* __restrict__ bw, const long long* __restrict__ off2,
+    const int* __restrict__ map_f, const RT* __restrict__ Lg4, const double* __restrict__ invd_f, int lds_per_wave,
+    int ring, int xs, int ncol, const double* __restrict__ in, double* __restrict__ out,
+    const double* __restrict__ gprev, double* __restrict__ gpart) {
   static_assert(!PIPE || sizeof(RT) == 8, "the pipelined chain reads fp64 records");
+  static_assert(!PAIR || (NC == 2 && !PIPE && sizeof(RT) == 8), "PAIR: two column sets, the plain chain, fp64 records");
+  constexpr int NS = PAIR ? 2 : 1;          // column sets that are blocks of their own
+  constexpr int MPW = (NT + 3) / 4;         // registers of a block's packed row map
+  // PAIR on precomputed operand addresses (g4_fwd_chunk_q): 12 + 4 DQ registers more, which 12 tiles and DQ <= 4 leave
+  // room for at three wavefronts per SIMD; 14 / 16 tiles or DQ = 5 / 6 would spill (20 .. 204 bytes of scratch per
+  // lane), those keep the address arithmetic of the plain chain
+  constexpr bool PRE = PAIR && NT <= 12 && DQ <= 4;
   extern __shared__ double smem[];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int pi = blockIdx.x * (blockDim.x >> 6) + wave;
   if (pi >= count) return;
-  const int p = __builtin_amdgcn_readfirstlane(list[pi]);
+  int i0 = pi, i1 = -1;                     // positions in `list` (what the Gram partials are indexed by)
+  if constexpr (PAIR) {
+    i0 = __builtin_amdgcn_readfirstlane(tasks[2 * pi]);
+    i1 = __builtin_amdgcn_readfirstlane(tasks[2 * pi + 1]);
+  }
+  const bool has1 = PAIR && i1 >= 0;
+  const int p = __builtin_amdgcn_readfirstlane(list[i0]);
   const int r0 = __builtin_amdgcn_readfirstlane(row0[p]);
+  int r0b = r0;                             // PAIR: the second block's first row
+  if constexpr (PAIR) {
+    if (has1) r0b = __builtin_amdgcn_readfirstlane(row0[__builtin_amdgcn_readfirstlane(list[i1])]);
+  }
   const int b = __builtin_amdgcn_readfirstlane(nrows[p]);
   const int w = __builtin_amdgcn_readfirstlane(bw[p]);
   const long long o64 = off2[p];
@@ -640,11 +787,11 @@ __global__ __launch_bounds__(256, OCC) void k_bj_g4(
   // Where the block's rows lie in the panel: row r0 + map[j], map < b <= 256 -- four of them to a register,
   // kept across both sweeps (the addresses themselves would be NT registers; gathered again behind the
   // backward sweep they put a dependent memory latency at the end of every block).
-  unsigned mpk[(NT + 3) / 4];        // (the host checks that m * xs fits 31 bits)
+  unsigned mpk[NS * MPW];            // (the host checks that m * xs fits 31 bits); PAIR: set 1's behind set 0's
 #pragma unroll
-  for (int q = 0; q < (NT + 3) / 4; ++q) mpk[q] = 0u;
+  for (int q = 0; q < NS * MPW; ++q) mpk[q] = 0u;
   {
-    unsigned mpv[NT];
+    unsigned mpv[NS * NT];
 #pragma unroll
     for (int q = 0; q < NT; ++q) {
       const int j = 16 * q + trow;
@@ -654,19 +801,47 @@ __global__ __launch_bounds__(256, OCC) void k_bj_g4(
     // afterwards: a load inside a branch makes the compiler wait for everything in flight at the join, and
     // the NT loads of a block would come one memory latency after the other)
     const unsigned loc = (unsigned)min(lo, ncol - 1);
+    if constexpr (PAIR) {
+      // Both maps requested before either panel, both panels before the first use.  The second block's loads stand
+      // in two wavefront-uniform branches: a task without a second block skips them and keeps the zeros.
+      const int* __restrict__ mp1 = map_f + r0b;
 #pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const unsigned cc = (unsigned)min(4 * c, max(ncol - 1 - (int)loc, 0));
+      for (int q = 0; q < NT; ++q) { mpv[NT + q] = 0u; T[NT + q] = 0.0; }
+      if (has1) {
 #pragma unroll
-      for (int q = 0; q < NT; ++q) T[c * NT + q] = in[((unsigned)r0 + mpv[q]) * (unsigned)xs + loc + cc];
+        for (int q = 0; q < NT; ++q) {
+          const int j = 16 * q + trow;
+          mpv[NT + q] = (unsigned)mp1[j < b ? j : 0];
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < NT; ++q) T[q] = in[((unsigned)r0 + mpv[q]) * (unsigned)xs + loc];
+      if (has1) {
+#pragma unroll
+        for (int q = 0; q < NT; ++q) T[NT + q] = in[((unsigned)r0b + mpv[NT + q]) * (unsigned)xs + loc];
+      }
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+#pragma unroll
+        for (int q = 0; q < NT; ++q)
+          T[c * NT + q] = (16 * q + trow < b && lo < ncol) ? T[c * NT + q] : 0.0;
+    } else {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        const unsigned cc = (unsigned)min(4 * c, max(ncol - 1 - (int)loc, 0));
+#pragma unroll
+        for (int q = 0; q < NT; ++q) T[c * NT + q] = in[((unsigned)r0 + mpv[q]) * (unsigned)xs + loc + cc];
+      }
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+#pragma unroll
+        for (int q = 0; q < NT; ++q)
+          T[c * NT + q] = (16 * q + trow < b && 4 * c + lo < ncol) ? T[c * NT + q] : 0.0;
     }
 #pragma unroll
-    for (int c = 0; c < NC; ++c)
+    for (int s = 0; s < NS; ++s)
 #pragma unroll
-      for (int q = 0; q < NT; ++q)
-        T[c * NT + q] = (16 * q + trow < b && 4 * c + lo < ncol) ? T[c * NT + q] : 0.0;
-#pragma unroll
-    for (int q = 0; q < NT; ++q) mpk[q >> 2] |= mpv[q] << (8 * (q & 3));
+      for (int q = 0; q < NT; ++q) mpk[s * MPW + (q >> 2)] |= mpv[s * NT + q] << (8 * (q & 3));
   }
   // the rest of the ring behind the panel loads, so that the newest requests are all chunks
   if constexpr (PIPE) {
@@ -685,13 +860,60 @@ __global__ __launch_bounds__(256, OCC) void k_bj_g4(
     g4_read_ops_c<NT, DQ, 0, 0, 0>(pf, opA);
     g4_ops_wait<DQ>(opA);
     g4_fwd_tiles_p<NT, DQ, 0>(T, b, rec, chunk_doubles, lds0, lane, pf, opA, opB);
+  } else if constexpr (PRE) {
+    g4_pre<DQ> pf;
+    g4_make_pre<DQ, true>((unsigned)(uintptr_t)(lds_ptr)lds0, w, lf, pf);
+    g4_fwd_tiles_q<NT, DQ, 0>(T, b, rec, chunk_doubles, lds0, lane, pf);
   } else {
     g4_fwd_tiles<RT, NC, NT, DQ, 0>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, lf, ring);
   }
 
   // y = D^-2 a
-  double ga_mid = 0.0;
-  {
+  double ga_mid[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) ga_mid[s] = 0.0;
+  if constexpr (PAIR) {
+    // each block's own pivots (equal values where the blocks are equal, but read per block); a set without a block
+    // is all zeros and stays so
+    // (12 tiles: both blocks' pivots requested at once, one memory latency; 14 / 16 tiles have no room for 2 NT more
+    // registers beside the 2 NT tiles -- they spilled -- and take the blocks one after the other)
+    constexpr int DS = NT <= 12 ? 2 : 1;
+    double d[DS * NT];
+#pragma unroll
+    for (int q = 0; q < NT; ++q) { const int j = 16 * q + trow; d[q] = invd_f[r0 + (j < b ? j : 0)]; }
+    if constexpr (DS == 2) {
+#pragma unroll
+      for (int q = 0; q < NT; ++q) d[NT + q] = 0.0;
+      if (has1) {
+#pragma unroll
+        for (int q = 0; q < NT; ++q) { const int j = 16 * q + trow; d[NT + q] = invd_f[r0b + (j < b ? j : 0)]; }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      if constexpr (DS == 1) {
+        if (c == 1) {
+          asm volatile("" ::: "memory");          // (set 0 is done with d before set 1's pivots are requested)
+#pragma unroll
+          for (int q = 0; q < NT; ++q) d[q] = 0.0;
+          if (has1) {
+#pragma unroll
+            for (int q = 0; q < NT; ++q) { const int j = 16 * q + trow; d[q] = invd_f[r0b + (j < b ? j : 0)]; }
+          }
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < NT; ++q) {
+        const double dd = d[(DS == 2 ? c * NT : 0) + q];
+        const double a = T[c * NT + q];
+        T[c * NT + q] *= dd * dd;
+        if constexpr (GP) {
+          const bool on = 16 * q + trow < b;
+          ga_mid[c] = __builtin_amdgcn_mfma_f64_4x4x4f64(on ? a : 0.0, on ? T[c * NT + q] : 0.0, ga_mid[c], 0, 0, 0);
+        }
+      }
+    }
+  } else {
     const double* __restrict__ dv = invd_f + r0;
     double d[NT];
 #pragma unroll
@@ -706,14 +928,16 @@ __global__ __launch_bounds__(256, OCC) void k_bj_g4(
         // load at all here, both operands are this tile (rows beyond the block masked out)
         if constexpr (GP) {
           const bool on = 16 * q + trow < b;
-          ga_mid = __builtin_amdgcn_mfma_f64_4x4x4f64(on ? a : 0.0, on ? T[q] : 0.0, ga_mid, 0, 0, 0);
+          ga_mid[0] = __builtin_amdgcn_mfma_f64_4x4x4f64(on ? a : 0.0, on ? T[q] : 0.0, ga_mid[0], 0, 0, 0);
         }
       }
   }
   // (the last chunk of the forward sweep is the first of the backward one: it is still in its buffer,
   // and so is the one before it -- g4_bwd_chunk does not fetch that one again)
   g4_gram gr;
-  gr.prev = gprev; gr.base = 0u; gr.xs = (unsigned)xs; gr.ap = 0.0; gr.gp = 0.0;
+  gr.prev = gprev; gr.xs = (unsigned)xs; gr.has1 = has1;
+#pragma unroll
+  for (int s = 0; s < 2; ++s) { gr.base[s] = 0u; gr.ap[s] = 0.0; gr.gp[s] = 0.0; }
   {
     int l2 = lane;
     asm volatile("" : "+v"(l2));                   // (recomputed here rather than kept across the forward sweep)
@@ -724,14 +948,15 @@ __global__ __launch_bounds__(256, OCC) void k_bj_g4(
     lb.cg = (unsigned)hi2 * g4_rowb<RT>() + (unsigned)lo2 * (unsigned)sizeof(RT);    // Lt(hi, lo): the transposed corner
     lb.hi = hi2;
     lb.blk = blk2;
-    gr.base = (unsigned)r0 * (unsigned)xs + (unsigned)lo2;
+    gr.base[0] = (unsigned)r0 * (unsigned)xs + (unsigned)lo2;
+    if constexpr (PAIR) gr.base[1] = (unsigned)r0b * (unsigned)xs + (unsigned)lo2;
     if constexpr (PIPE) {
       // (few blocks: nothing to gain from spreading the rows of gprev over the sweep -- one wavefront per SIMD,
       // no burst -- so they are all requested here, in front of it, and multiplied in behind it)
       double apv[NT];
       if constexpr (GP) {
 #pragma unroll
-        for (int q = 0; q < NT; ++q) apv[q] = gprev[gr.base + ((mpk[q >> 2] >> (8 * (q & 3))) & 255u) * gr.xs];
+        for (int q = 0; q < NT; ++q) apv[q] = gprev[gr.base[0] + ((mpk[q >> 2] >> (8 * (q & 3))) & 255u) * gr.xs];
       }
       g4_pre<DQ> pb;
       g4_make_pre<DQ, false>((unsigned)(uintptr_t)(lds_ptr)lds0, w, lb, pb);
@@ -743,12 +968,16 @@ __global__ __launch_bounds__(256, OCC) void k_bj_g4(
 #pragma unroll
         for (int q = 1; q < NT; ++q) {
           const double z = 16 * q + 4 * blk2 + hi2 < b ? T[q] : 0.0;
-          gr.gp = __builtin_amdgcn_mfma_f64_4x4x4f64(apv[q], z, gr.gp, 0, 0, 0);
+          gr.gp[0] = __builtin_amdgcn_mfma_f64_4x4x4f64(apv[q], z, gr.gp[0], 0, 0, 0);
         }
-        gr.ap = apv[0];          // (tile 0 is taken below, like the spread-out variant's last request)
+        gr.ap[0] = apv[0];       // (tile 0 is taken below, like the spread-out variant's last request)
       }
+    } else if constexpr (PRE) {
+      g4_pre<DQ> pb;
+      g4_make_pre<DQ, false>((unsigned)(uintptr_t)(lds_ptr)lds0, w, lb, pb);
+      g4_bwd_tiles_q<NT, DQ, NT - 1, GP>(T, b, rec, chunk_doubles, lds0, lane, blk2, pb, gr, 4 * blk2 + hi2, mpk);
     } else {
-      g4_bwd_tiles<RT, NC, NT, DQ, NT - 1, GP>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, lb, ring, gr, 4 * blk2 + hi2, mpk);
+      g4_bwd_tiles<RT, NC, NT, DQ, NT - 1, GP, NS>(T, b, w, rec, chunk_doubles, lds0, lstride, lane, lb, ring, gr, 4 * blk2 + hi2, mpk);
     }
   }
 
@@ -756,34 +985,56 @@ __global__ __launch_bounds__(256, OCC) void k_bj_g4(
     int l3 = lane;
     asm volatile("" : "+v"(l3));                   // (addresses recomputed, not carried through both sweeps)
     const int trow3 = 4 * ((l3 >> 2) & 3) + (l3 >> 4), lo3 = l3 & 3;
-    unsigned rowoff[NT];
+    unsigned rowoff[NT];         // (PAIR: set 0's; set 1's are formed when set 0 is stored)
 #pragma unroll
     for (int q = 0; q < NT; ++q)
       rowoff[q] = ((unsigned)r0 + ((mpk[q >> 2] >> (8 * (q & 3))) & 255u)) * (unsigned)xs + lo3;
     if constexpr (GP) {          // tile 0's rows of gprev: the one operation still in flight (taken before the stores)
-      asm volatile("s_waitcnt vmcnt(0)" : "+v"(gr.ap) :: "memory");
-      gr.gp = __builtin_amdgcn_mfma_f64_4x4x4f64(gr.ap, trow3 < b ? T[0] : 0.0, gr.gp, 0, 0, 0);
-    }
+      if constexpr (PAIR) asm volatile("s_waitcnt vmcnt(0)" : "+v"(gr.ap[0]), "+v"(gr.ap[1]) :: "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" : "+v"(gr.ap[0]) :: "memory");
 #pragma unroll
-    for (int c = 0; c < NC; ++c)
+      for (int s = 0; s < NS; ++s)
+        gr.gp[s] = __builtin_amdgcn_mfma_f64_4x4x4f64(gr.ap[s], trow3 < b ? T[s * NT] : 0.0, gr.gp[s], 0, 0, 0);
+    }
+    if constexpr (PAIR) {        // each block's rows of the same ncol <= 4 columns; nothing for a set without a block
 #pragma unroll
       for (int q = 0; q < NT; ++q)
-        if (16 * q + trow3 < b && 4 * c + lo3 < ncol) out[rowoff[q] + 4 * c] = T[c * NT + q];
+        if (16 * q + trow3 < b && lo3 < ncol) out[rowoff[q]] = T[q];
+      if (has1) {
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int q = 0; q < NT; ++q) {
+          const unsigned ro = ((unsigned)r0b + ((mpk[MPW + (q >> 2)] >> (8 * (q & 3))) & 255u)) * (unsigned)xs + lo3;
+          if (16 * q + trow3 < b && lo3 < ncol) out[ro] = T[NT + q];
+        }
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+#pragma unroll
+        for (int q = 0; q < NT; ++q)
+          if (16 * q + trow3 < b && 4 * c + lo3 < ncol) out[rowoff[q] + 4 * c] = T[c * NT + q];
+    }
     // GP (4-column panels, pa_k_bj_g4_gram): the block's share of [in | gprev]^T out -- the Gram block the ECG
     // iteration forms right after the apply (beta = [AP | AP_prev]^T Z, ecg.c:510) -- while the result is still
     // in registers.  A tile (lane = 16 hi + 4 blk + lo: row 4 blk + hi, column lo) is the B operand of
     // v_mfma_f64_4x4x4 as it stands (k = hi); the A operand, row 4 blk + k of the other panel in column i = lo,
     // sits at the tile's own address.  8 x 4 per block, the layout of k_gram<4, 2>.  in^T out was formed between
     // the sweeps (ga_mid); the rows of gprev came in during the backward sweep (g4_bwd_chunk), tile 0 last.
+    // PAIR: each block's partial at its own position of the list, so the finish sums the same partials from the same
+    // places as after the one-block launch.
     if constexpr (GP) {
-      double ga = ga_mid, gp = gr.gp;
-      ga += row_ror<4>(ga); ga += row_ror<8>(ga);
-      gp += row_ror<4>(gp); gp += row_ror<8>(gp);
-      if (((l3 >> 2) & 3) == 0) {
-        const int i = l3 >> 4;
-        double* gq = gpart + (size_t)pi * 32;
-        gq[i + 8 * lo3] = ga;
-        gq[4 + i + 8 * lo3] = gp;
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        double ga = ga_mid[s], gp = gr.gp[s];
+        ga += row_ror<4>(ga); ga += row_ror<8>(ga);
+        gp += row_ror<4>(gp); gp += row_ror<8>(gp);
+        if (((l3 >> 2) & 3) == 0 && (s == 0 || has1)) {
+          const int i = l3 >> 4;
+          double* gq = gpart + (size_t)(s ? i1 : i0) * 32;
+          gq[i + 8 * lo3] = ga;
+          gq[4 + i + 8 * lo3] = gp;
+        }
       }
     }
   }
@@ -797,6 +1048,47 @@ int kfail(const char* what) {
   fprintf(stderr, "[prealps_hip] kernel launch failed: %s\n", g_err);
   return 1;
 }
+
+#ifdef G4_PAIR
+// ---- the PAIR launch (bj_g4_pair*.hip: this source with G4_PAIR set, one unit per NT) ---------------------------
+// ntasks wavefronts of two blocks each.  Always ring 2, the many-blocks configuration the rule below picks it for:
+// the hand-kept wait counts of the Gram rows (g4_bwd_chunk: extra) are written for that depth.  A ring buffer is at
+// most 6 KiB (bands up to pa_bj_g4_max_band8() = 80), four wavefronts 48 KiB: no attribute to set.  Three wavefronts
+// per SIMD by registers (profiles/r21_bj_pair_resources.txt), four by LDS.
+template <int NT, int DQ>
+int launch_pair(const pa_bj_plan_t* pl, const int* list, const int* tasks, int ntasks, int wmax, int xs, int ncol,
+                const double* in, double* out, const double* gprev, double* gpart) {
+  const int cbuf = DQ * 128;            // doubles per ring buffer: DQ KiB, a compile-time stride (g4_fwd_chunk_q)
+  if (8 * (wmax + 4) > cbuf) return 1;  // (launch_pair_dq picks DQ from wmax: wmax <= 16 DQ - 16)
+  const int ring = 2, per_wave = ring * cbuf;
+  const int waves = 4;
+  const size_t lds = (size_t)waves * per_wave * 8;
+  if (lds > 64 * 1024) return 1;
+  const int blocks = (ntasks + waves - 1) / waves;
+  const double* Lg4 = static_cast<const double*>(pl->Lg4);
+  pa_g4_last[0] = ring; pa_g4_last[1] = 64; pa_g4_last[2] = 0; pa_g4_last[3] = 1;
+  if (gpart && xs == 4 && ncol == 4)
+    PA_LAUNCH((k_bj_g4<2, NT, DQ, 3, true, false, double, 1>), dim3(blocks), dim3(64 * waves), lds, cur_stream(), list, tasks, ntasks,
+              pl->row0, pl->nrows, pl->bw, pl->off2, pl->map_f, Lg4, pl->invd_f, per_wave, ring, xs, ncol, in, out, gprev, gpart);
+  else
+    PA_LAUNCH((k_bj_g4<2, NT, DQ, 3, false, false, double, 1>), dim3(blocks), dim3(64 * waves), lds, cur_stream(), list, tasks, ntasks,
+              pl->row0, pl->nrows, pl->bw, pl->off2, pl->map_f, Lg4, pl->invd_f, per_wave, ring, xs, ncol, in, out,
+              (const double*)nullptr, (double*)nullptr);
+  return kfail("k_bj_g4 (pair)");
+}
+
+template <int NT>
+int launch_pair_dq(const pa_bj_plan_t* pl, const int* list, const int* tasks, int ntasks, int wmax, int xs, int ncol,
+                   const double* in, double* out, const double* gprev, double* gpart) {
+  switch (((wmax + 15) >> 4) + 1) {
+    case 1: case 2: case 3: return launch_pair<NT, 3>(pl, list, tasks, ntasks, wmax, xs, ncol, in, out, gprev, gpart);
+    case 4: return launch_pair<NT, 4>(pl, list, tasks, ntasks, wmax, xs, ncol, in, out, gprev, gpart);
+    case 5: return launch_pair<NT, 5>(pl, list, tasks, ntasks, wmax, xs, ncol, in, out, gprev, gpart);
+    case 6: return launch_pair<NT, 6>(pl, list, tasks, ntasks, wmax, xs, ncol, in, out, gprev, gpart);
+    default: return 1;
+  }
+}
+#else
 
 template <typename RT, int NC, int NT, int DQ, int OCC>
 int launch_occ(const int* list, int count, const pa_bj_plan_t* pl, int wmax, int xs, int ncol, const double* in, double* out) {
@@ -831,7 +1123,7 @@ int launch_occ(const int* list, int count, const pa_bj_plan_t* pl, int wmax, int
     configured = lds;
   }
   const int blocks = (count + waves - 1) / waves;
-  pa_g4_last[0] = ring; pa_g4_last[1] = 8 * (int)sizeof(RT); pa_g4_last[2] = 0;
+  pa_g4_last[0] = ring; pa_g4_last[1] = 8 * (int)sizeof(RT); pa_g4_last[2] = 0; pa_g4_last[3] = 0;
   // (fp32 records: no pipelined chain -- few blocks take the plain chain with the deep ring below, as the classes
   // outside NT == 12 && DQ <= 5 do)
   if constexpr (F64 && NC == 1 && NT == 12 && DQ <= 5) {
@@ -856,11 +1148,11 @@ int launch_occ(const int* list, int count, const pa_bj_plan_t* pl, int wmax, int
       const int blocks_f = (count + waves_f - 1) / waves_f;
       pa_g4_last[0] = G4F_RING; pa_g4_last[2] = 1;
       if (pa_g4_gram_part && xs == 4 && ncol == 4)
-        PA_LAUNCH((k_bj_g4<NC, NT, DQ, 1, true, true>), dim3(blocks_f), dim3(64 * waves_f), lds_f, cur_stream(), list, count, pl->row0,
+        PA_LAUNCH((k_bj_g4<NC, NT, DQ, 1, true, true>), dim3(blocks_f), dim3(64 * waves_f), lds_f, cur_stream(), list, (const int*)nullptr, count, pl->row0,
                   pl->nrows, pl->bw, pl->off2, pl->map_f, Lg4, pl->invd_f, per_wave_f, G4F_RING, xs, ncol, in, out,
                   pa_g4_gram_prev, pa_g4_gram_part);
       else
-        PA_LAUNCH((k_bj_g4<NC, NT, DQ, 1, false, true>), dim3(blocks_f), dim3(64 * waves_f), lds_f, cur_stream(), list, count, pl->row0,
+        PA_LAUNCH((k_bj_g4<NC, NT, DQ, 1, false, true>), dim3(blocks_f), dim3(64 * waves_f), lds_f, cur_stream(), list, (const int*)nullptr, count, pl->row0,
                   pl->nrows, pl->bw, pl->off2, pl->map_f, Lg4, pl->invd_f, per_wave_f, G4F_RING, xs, ncol, in, out,
                   (const double*)nullptr, (double*)nullptr);
       return kfail("k_bj_g4");
@@ -868,13 +1160,13 @@ int launch_occ(const int* list, int count, const pa_bj_plan_t* pl, int wmax, int
   }
   if constexpr (NC == 1) {
     if (pa_g4_gram_part && xs == 4 && ncol == 4) {
-      PA_LAUNCH((k_bj_g4<NC, NT, DQ, OCC, true, false, RT>), dim3(blocks), dim3(64 * waves), lds, cur_stream(), list, count, pl->row0,
+      PA_LAUNCH((k_bj_g4<NC, NT, DQ, OCC, true, false, RT>), dim3(blocks), dim3(64 * waves), lds, cur_stream(), list, (const int*)nullptr, count, pl->row0,
                 pl->nrows, pl->bw, pl->off2, pl->map_f, Lg4, pl->invd_f, per_wave, ring, xs, ncol, in, out,
                 pa_g4_gram_prev, pa_g4_gram_part);
       return kfail("k_bj_g4");
     }
   }
-  PA_LAUNCH((k_bj_g4<NC, NT, DQ, OCC, false, false, RT>), dim3(blocks), dim3(64 * waves), lds, cur_stream(), list, count, pl->row0,
+  PA_LAUNCH((k_bj_g4<NC, NT, DQ, OCC, false, false, RT>), dim3(blocks), dim3(64 * waves), lds, cur_stream(), list, (const int*)nullptr, count, pl->row0,
             pl->nrows, pl->bw, pl->off2, pl->map_f, Lg4, pl->invd_f, per_wave, ring, xs, ncol, in, out,
             (const double*)nullptr, (double*)nullptr);
   return kfail("k_bj_g4");
@@ -904,12 +1196,31 @@ int launch_dq(const int* list, int count, const pa_bj_plan_t* pl, int wmax, int 
     default: return 1;
   }
 }
+#endif  // G4_PAIR
 
 }  // namespace
 
 extern "C" {
 
-#ifdef G4_F32
+#ifdef G4_PAIR
+/* ---- the PAIR launch: three units (bj_g4_pair.hip, bj_g4_pair_nt14.hip, bj_g4_pair_nt16.hip), fp64 records only ---- */
+#if G4_NT == 12
+int pa_k_bj_g4_pair_nt12(const pa_bj_plan_t* pl, const int* list, const int* tasks, int ntasks, int wmax, int xs, int ncol,
+                         const double* in, double* out, const double* gprev, double* gpart) {
+  return launch_pair_dq<12>(pl, list, tasks, ntasks, wmax, xs, ncol, in, out, gprev, gpart);
+}
+#elif G4_NT == 14
+int pa_k_bj_g4_pair_nt14(const pa_bj_plan_t* pl, const int* list, const int* tasks, int ntasks, int wmax, int xs, int ncol,
+                         const double* in, double* out, const double* gprev, double* gpart) {
+  return launch_pair_dq<14>(pl, list, tasks, ntasks, wmax, xs, ncol, in, out, gprev, gpart);
+}
+#else
+int pa_k_bj_g4_pair_nt16(const pa_bj_plan_t* pl, const int* list, const int* tasks, int ntasks, int wmax, int xs, int ncol,
+                         const double* in, double* out, const double* gprev, double* gpart) {
+  return launch_pair_dq<16>(pl, list, tasks, ntasks, wmax, xs, ncol, in, out, gprev, gpart);
+}
+#endif
+#elif defined(G4_F32)
 /* ---- fp32 records: the same three units again (bj_g4_f32.hip, bj_g4_f32_nt14.hip, bj_g4_f32_nt16.hip) ---- */
 #if G4_NT == 12
 int pa_k_bj_g4_setup_f32(const int* list, int count, const int* nrows, const int* bw, const long long* off,
@@ -944,8 +1255,8 @@ int pa_k_bj_g4_f32_nt16(const pa_bj_plan_t* pl, const int* list, int count, int 
 #elif G4_NT == 12
 const double* pa_g4_gram_prev = nullptr;
 double* pa_g4_gram_part = nullptr;
-int pa_g4_last[3] = {0, 0, 0};
-int pa_bj_g4_last(int which) { return which >= 0 && which < 3 ? pa_g4_last[which] : 0; }
+int pa_g4_last[4] = {0, 0, 0, 0};
+int pa_bj_g4_last(int which) { return which >= 0 && which < 4 ? pa_g4_last[which] : 0; }
 /* The next pa_k_bj_g4 on a 4-column panel also leaves, per block (in the order of `list`), the 8 x 4 block
  * [in | prev]^T out in part (32 doubles each).  Cleared by that call. */
 void pa_k_bj_g4_gram(const double* prev, double* part) { pa_g4_gram_prev = prev; pa_g4_gram_part = part; }
@@ -966,16 +1277,49 @@ int pa_k_bj_g4_nt16(const pa_bj_plan_t* pl, const int* list, int count, int wmax
 int pa_k_bj_g4_f32(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int bmax, int xs, int ncol,
                    const double* in, double* out);
 
+int pa_k_bj_g4_pair_nt12(const pa_bj_plan_t* pl, const int* list, const int* tasks, int ntasks, int wmax, int xs, int ncol,
+                         const double* in, double* out, const double* gprev, double* gpart);
+int pa_k_bj_g4_pair_nt14(const pa_bj_plan_t* pl, const int* list, const int* tasks, int ntasks, int wmax, int xs, int ncol,
+                         const double* in, double* out, const double* gprev, double* gpart);
+int pa_k_bj_g4_pair_nt16(const pa_bj_plan_t* pl, const int* list, const int* tasks, int ntasks, int wmax, int xs, int ncol,
+                         const double* in, double* out, const double* gprev, double* gpart);
+
+/* The rule of the PAIR launch: two blocks of one class of identical blocks per wavefront, the
+ * record read once for both.  Possible at all: the class has pair tasks with at least one pair, fp64 records, a
+ * panel of up to 4 columns, bands the two-set kernels take, and no refresh has split a class since the create (a block
+ * that reads its own records again must not be served from its partner's).  PREALPS_BJ_PAIR=1: then always; =0: never;
+ * unset: the default below, and then in the many-blocks regime only (at least two blocks per SIMD -- below that the
+ * pipelined few-blocks chain stays) and when at least half of the list's blocks have a partner. */
+#define G4_PAIR_DEFAULT 1
+static int g4_pairs(const pa_bj_plan_t* pl, const pa_bj_ptask_t* pt, int count, int wmax, int bmax, int xs, int ncol) {
+  if (!pt || !pt->tasks || pt->paired < 2 || pl->pair_mode == 0 || !pl->pair_intact) return 0;
+  if (pl->g4_bits != 64 || xs > 4 || ncol > 4 || wmax > pa_bj_g4_max_band8()) return 0;
+  if (pl->pair_mode == 1) return 1;
+  if (!G4_PAIR_DEFAULT) return 0;
+  /* measured (profiles/r21_bj_pair_speed.txt): the launch gains where it runs on precomputed operand addresses -- up to
+   * 192 rows and bands up to 48 -- and gains nothing or loses elsewhere */
+  if (bmax > 192 || wmax > 48) return 0;
+  const int simds = 4 * (pa_rt_num_cus() > 0 ? pa_rt_num_cus() : 256);
+  return count >= 2 * simds && 2 * pt->paired >= count;
+}
+
 /* One class of blocks (all with at most bmax rows and bands up to wmax) on a panel of row stride xs:
  * the ncol <= 8 columns starting at `in` / `out` (more than 4: bands up to pa_bj_g4_max_band8()).  The
  * kernels for 12 / 14 / 16 register tiles are compiled in three translation units (bj_g4.hip,
  * bj_g4_nt14.hip, bj_g4_nt16.hip: the same source, G4_NT set) so that they build in parallel; those that read
  * fp32 records (PREALPS_BJ_BAND_PRECISION=single) in three more (bj_g4_f32*.hip: G4_F32 set as well). */
 int pa_k_bj_g4(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int bmax, int xs, int ncol,
-               const double* in, double* out) {
+               const double* in, double* out, const pa_bj_ptask_t* pt) {
   if (count <= 0) return 0;
   int rc;
-  if (pl->g4_bits == 32) rc = pa_k_bj_g4_f32(pl, list, count, wmax, bmax, xs, ncol, in, out);     /* fp32 records */
+  if (g4_pairs(pl, pt, count, wmax, bmax, xs, ncol)) {
+    const double* gprev = xs == 4 && ncol == 4 ? pa_g4_gram_prev : nullptr;
+    double* gpart = xs == 4 && ncol == 4 ? pa_g4_gram_part : nullptr;
+    rc = bmax > 224 ? pa_k_bj_g4_pair_nt16(pl, list, pt->tasks, pt->ntasks, wmax, xs, ncol, in, out, gprev, gpart)
+       : bmax > 192 ? pa_k_bj_g4_pair_nt14(pl, list, pt->tasks, pt->ntasks, wmax, xs, ncol, in, out, gprev, gpart)
+                    : pa_k_bj_g4_pair_nt12(pl, list, pt->tasks, pt->ntasks, wmax, xs, ncol, in, out, gprev, gpart);
+  }
+  else if (pl->g4_bits == 32) rc = pa_k_bj_g4_f32(pl, list, count, wmax, bmax, xs, ncol, in, out);     /* fp32 records */
   else if (bmax > 224) rc = pa_k_bj_g4_nt16(pl, list, count, wmax, xs, ncol, in, out);
   else if (bmax > 192) rc = pa_k_bj_g4_nt14(pl, list, count, wmax, xs, ncol, in, out);
   else rc = ncol > 4 ? launch_dq<2, 12>(list, count, pl, wmax, xs, ncol, in, out)

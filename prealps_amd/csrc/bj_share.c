@@ -2,8 +2,9 @@
  * bj_share.c -- the classes of identical diagonal blocks (bj_share.h): one hash per band (parallel over the
  * blocks), the eligible blocks sorted by (hash, rows, bandwidth, number), every block of a run compared with the
  * run's first (parallel), and the few that differ from it -- blocks that only collide -- sorted out one after the
- * other against the representatives their run has so far.
+ * other against the representatives their run has so far.  And the pair tasks of a launch list, from the classes.
  */
+#include <assert.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -70,5 +71,26 @@ int pa_bj_share_classes(const pa_bj_share_in_t* in, int* rep, int* nclass) {
   }
   *nclass = np - shared;
   free(key); free(first); free(reps); free(same);
+  return 0;
+}
+
+int pa_bj_pair_tasks(int np, const int* list, int count, const int* rep, const int* nrows, const int* bw, int* tasks,
+                     int* ntasks, int* paired) {
+  *ntasks = 0; *paired = 0;
+  if (count <= 0) return 0;
+  int* open = (int*)malloc((size_t)(np > 0 ? np : 1) * sizeof(int));      /* per class: its task that waits for a partner */
+  if (!open) return -1;
+  for (int p = 0; p < np; ++p) open[p] = -1;
+  int nt = 0, np2 = 0;
+  for (int i = 0; i < count; ++i) {
+    const int p = list[i];
+    assert(p >= 0 && p < np);
+    const int r = rep[p];
+    assert(r >= 0 && r < np && nrows[r] == nrows[p] && bw[r] == bw[p]);
+    if (open[r] >= 0) { tasks[2 * open[r] + 1] = i; open[r] = -1; np2 += 2; }
+    else { tasks[2 * nt] = i; tasks[2 * nt + 1] = -1; open[r] = nt++; }
+  }
+  free(open);
+  *ntasks = nt; *paired = np2;
   return 0;
 }

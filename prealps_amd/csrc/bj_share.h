@@ -29,4 +29,17 @@ typedef struct {
  * for every block then: nothing shares). */
 int pa_bj_share_classes(const pa_bj_share_in_t* in, int* rep, int* nclass);
 
+/* The pair tasks of one launch list (bj_g4.hip, the PAIR launch: two blocks of one class in one wavefront, the record
+ * read once for both).  list[0 .. count) = the blocks of the launch in launch order, rep[] as above (np entries).
+ * tasks[2 k], tasks[2 k + 1] = positions (i0, i1) INTO list of the two members of task k: rep[list[i0]] ==
+ * rep[list[i1]], i0 < i1; i1 = -1 for a block without a partner (the last of an odd class, a class of one, a block
+ * that is not eligible and so is its own class).  Every position appears in exactly one task; the pairs of a class are
+ * formed in list order (its first with its second, its third with its fourth, ...) and the tasks are ordered by i0.
+ * One pass over the list with one slot per block, no hash: the same list gives the same tasks.  Blocks with one rep
+ * have the same rows and bandwidth by construction; the function asserts it.  tasks: 2 * count ints, the caller's.
+ * *ntasks = tasks, *paired = blocks that have a partner (2 x the tasks with i1 >= 0).  Returns 0, or -1 out of host
+ * memory (*ntasks = *paired = 0 then). */
+int pa_bj_pair_tasks(int np, const int* list, int count, const int* rep, const int* nrows, const int* bw, int* tasks,
+                     int* ntasks, int* paired);
+
 #endif

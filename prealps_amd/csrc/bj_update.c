@@ -103,7 +103,14 @@ static int bj_refactor_bands(pa_bj_t* s, const pa_operator_info_t* op, int* wrot
     if (!rc && s->share_members > 0) {
       unsigned long long cnt[2];
       if (pa_rt_d2h(cnt, s->d_share_cnt, sizeof(cnt))) rc = BJU_FAIL("%s", pa_rt_error());
-      else { s->shared_blocks = (int)cnt[0]; s->shared_elems2 = (long long)cnt[1]; }
+      else {
+        s->shared_blocks = (int)cnt[0]; s->shared_elems2 = (long long)cnt[1];
+        /* The PAIR launch of bj_g4.hip serves a block from its partner's read offset: only while every block reads
+         * what it read at the create.  A change of that is a change of what the apply launches: captured iteration
+         * segments are taken anew. */
+        const int intact = s->shared_blocks == s->share_members;
+        if (intact != s->plan.pair_intact) { s->plan.pair_intact = intact; pa_bj_apply_epoch_bump(); }
+      }
     }
   }
   if (!rc && fail == 0) {     /* the second layouts, from the new plain records */
@@ -184,6 +191,9 @@ int pa_bj_update_stat(const char* key, double* value) {
   else if (!strcmp(key, "bj_share_distinct_g4_bytes"))
     *value = on && s->d_Lg4 ? (s->g4_bits == 32 ? 4.0 : 8.0) * (double)(s->lay.tot2 - s->shared_elems2) : 0.0;
   else if (!strcmp(key, "bj_share_s")) *value = on ? s->share_s : 0.0;
+  /* the pair tasks of the create (bj_share.h): wavefronts of the PAIR launch, blocks among them that have a partner */
+  else if (!strcmp(key, "bj_pair_tasks")) *value = on ? s->pair_tasks : 0;
+  else if (!strcmp(key, "bj_paired_blocks")) *value = on ? s->paired_blocks : 0;
   else if (!strcmp(key, "bj_records_address")) *value = on ? (double)(size_t)s->d_Lf : 0.0;
   else if (!strcmp(key, "bj_g4_address")) *value = on ? (double)(size_t)s->d_Lg4 : 0.0;
   else if (!strcmp(key, "bj_coarse_max_dofs")) *value = PA_COARSE_MAX_DOFS;

@@ -92,7 +92,7 @@ void preAlps_BlockJacobiFree(void) {
   pa_rt_free(s->d_Lf2); pa_rt_free(s->d_Lb2); pa_rt_free(s->d_off2); pa_rt_free(s->d_Lg4);
   pa_rt_free(s->d_off_read); pa_rt_free(s->d_off2_read); pa_rt_free(s->d_rep); pa_rt_free(s->d_share_list); pa_rt_free(s->d_share_cnt);
   free(s->h_rep);
-  for (int c = 0; c < PA_BJ_MAX_CLASSES; ++c) pa_rt_free(s->d_class_list[c]);
+  for (int c = 0; c < PA_BJ_MAX_CLASSES; ++c) { pa_rt_free(s->d_class_list[c]); pa_rt_free(s->d_ptask[c]); }
   pa_bj_layout_free(&s->lay);
   free(s->h_row0); free(s->h_nrows); free(s->h_bw); free(s->h_grow0); free(s->h_map_f); free(s->h_is_nd);
   pa_rt_free(s->d_bm_src); pa_rt_free(s->d_bm_dst); pa_rt_free(s->d_bm_chunk_blk); pa_rt_free(s->d_bm_chunk_first);
@@ -113,6 +113,7 @@ typedef struct {
   int wide_from;              /* PREALPS_BJ_WIDE_FROM, negative: absent */
   int want_g4, want_pairs;    /* PREALPS_BJ_G4 / PREALPS_BJ_PAIRS != 0 */
   int share;                  /* PREALPS_BJ_SHARE != 0: identical blocks read one block's records (bj_share.h) */
+  int pair;                   /* PREALPS_BJ_PAIR: 0 never two blocks per wavefront, 1 whenever a list has a pair, -1 (unset): the rule */
 } bj_switches_t;
 
 /* Storage bits of a factor: the value set through the API, else the switch `name` (double / single). */
@@ -149,6 +150,8 @@ static int bj_read_switches(bj_switches_t* sw) {
   sw->want_g4 = !(getenv("PREALPS_BJ_G4") && atoi(getenv("PREALPS_BJ_G4")) == 0);
   sw->want_pairs = !(getenv("PREALPS_BJ_PAIRS") && atoi(getenv("PREALPS_BJ_PAIRS")) == 0);
   sw->share = !(getenv("PREALPS_BJ_SHARE") && atoi(getenv("PREALPS_BJ_SHARE")) == 0);
+  const char* pe = getenv("PREALPS_BJ_PAIR");
+  sw->pair = pe && *pe ? (atoi(pe) != 0) : -1;
   return 0;
 }
 
@@ -208,6 +211,38 @@ static int bj_upload_share(pa_bj_t* s) {
       pa_rt_h2d(s->d_rep, s->h_rep, (size_t)np * sizeof(int)) || pa_rt_h2d(s->d_share_list, list, (size_t)nm * sizeof(int)))
     rc = BJ_FAIL("uploading the read offsets failed: %s", pa_rt_error());
   free(h); free(list);
+  return rc;
+}
+
+/* ---- stage 8b: the pair tasks of the classes of the layout that bj_g4.hip serves ---- */
+/* Behind the class pass and the second layouts: for every class of the layout with fp64 one-copy records, the tasks
+ * (i0, i1) of its launch list (bj_share.h), built once and uploaded once.  Whether a launch takes them is bj_g4.hip's
+ * rule; with no sharing every block is a class of one and no list has a pair. */
+static int bj_pair_pass(pa_bj_t* s, int pair_mode) {
+  const pa_bj_layout_t* L = &s->lay;
+  int rc = 0;
+  s->pair_mode = pair_mode; s->pair_tasks = 0; s->paired_blocks = 0;
+  if (!s->d_Lg4 || s->g4_bits != 64 || s->share_members == 0) return 0;
+  for (int c = 0; c < L->nclass && !rc; ++c) {
+    const int count = L->class_count[c];
+    if (!L->class_g4[c] || count < 2) continue;
+    int* tasks = (int*)malloc(2 * (size_t)count * sizeof(int));
+    int nt = 0, paired = 0;
+    if (!tasks || pa_bj_pair_tasks(s->np, L->class_list[c], count, s->h_rep, s->h_nrows, s->h_bw, tasks, &nt, &paired)) {
+      free(tasks);
+      return BJ_FAIL("out of host memory for the pair tasks of %d blocks", count);
+    }
+    if (paired > 0) {
+      s->d_ptask[c] = (int*)pa_rt_malloc(2 * (size_t)nt * sizeof(int));
+      if (!s->d_ptask[c] || pa_rt_h2d(s->d_ptask[c], tasks, 2 * (size_t)nt * sizeof(int)))
+        rc = BJ_FAIL("uploading the pair tasks failed: %s", pa_rt_error());
+      s->class_ptask[c].tasks = s->d_ptask[c]; s->class_ptask[c].ntasks = nt; s->class_ptask[c].paired = paired;
+      s->pair_tasks += nt; s->paired_blocks += paired;
+    }
+    free(tasks);
+  }
+  if (getenv("PREALPS_SETUP_TRACE"))
+    fprintf(stderr, "[setup] pair tasks (%d tasks, %d of %d blocks have a partner)\n", s->pair_tasks, s->paired_blocks, s->np);
   return rc;
 }
 
@@ -514,6 +549,7 @@ static void bj_fill_plan(pa_bj_t* s) {
   pl->nclass = L->nclass; pl->class_R = L->class_R; pl->class_count = L->class_count;
   pl->class_wmax = L->class_wmax;
   pl->class_list = s->class_list_c;
+  pl->class_ptask = s->class_ptask; pl->pair_mode = s->pair_mode; pl->pair_intact = s->shared_blocks == s->share_members;
 }
 
 /* ---- stage 10: what a later preAlps_BlockJacobiUpdateValues needs (host memory only) ---- */
@@ -587,6 +623,7 @@ int preAlps_BlockJacobiCreate(CPLM_Mat_CSR_t* A, int* rowPos, int sizeRowPos, in
   if (!rc) rc = bj_second_layouts(s, sw.band_bits);
   if (!rc) rc = bj_upload_share(s);
   if (!rc) rc = bj_keep_decisions(s, &B, &in);
+  if (!rc) rc = bj_pair_pass(s, sw.pair);
   pa_bj_build_free(&B);
   if (rc) { preAlps_BlockJacobiFree(); return rc; }
   s->factor_bytes = 2.0 * 8.0 * (double)s->lay.tot + pa_nd_factor_bytes();

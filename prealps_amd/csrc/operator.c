@@ -1266,6 +1266,7 @@ int preAlps_hip_get_stat(const char* key, double* value) {
   else if (!strcmp(key, "bj_g4_last_ring")) *value = pa_bj_g4_last(0);
   else if (!strcmp(key, "bj_g4_last_bits")) *value = pa_bj_g4_last(1);
   else if (!strcmp(key, "bj_g4_last_pipelined")) *value = pa_bj_g4_last(2);
+  else if (!strcmp(key, "bj_g4_last_paired")) *value = pa_bj_g4_last(3);
   else return pa_bj_update_stat(key, value);
   return 0;
 }

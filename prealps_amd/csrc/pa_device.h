@@ -312,6 +312,8 @@ int pa_k_sys_norms_ride(const double* rtr_part, int rtr_nblk, const double* sys_
                         const int* info, double* buf);
 
 /* ---- block-Jacobi apply (block_jacobi.c:93-109, K8) --------------------- */
+/* the pair tasks of one class: device array of (i0, i1), positions into the class's list (i1 = -1: no partner) */
+typedef struct { const int* tasks; int ntasks, paired; } pa_bj_ptask_t;
 typedef struct {
   int nparts;              /* blocks owned by this process */
   const int* row0;         /* nparts: first local row of each block */
@@ -344,6 +346,11 @@ typedef struct {
   const int* class_count;  /* host array */
   const int* class_wmax;   /* host array: widest band in the class (sizes the LDS chunks) */
   const int* const* class_list; /* host array of device pointers to part ids */
+  /* optional (NULL: absent): the pair tasks of the classes that bj_g4.hip serves from fp64 records (bj_share.h:
+   * pa_bj_pair_tasks), two blocks of one class of identical blocks per wavefront */
+  const pa_bj_ptask_t* class_ptask;  /* host array, nclass */
+  int pair_mode;           /* PREALPS_BJ_PAIR: 0 never, 1 whenever a list has a pair, -1 (absent) the rule of bj_g4.hip */
+  int pair_intact;         /* 1: every block reads the records it read at the create (no refresh has split a class) */
 } pa_bj_plan_t;
 /* Window of a wide block (rows in flight = record length, >= w + 64) for bandwidth w: a multiple of the
  * 64 / 128 / 256 rows that 1 / 2 / 4 register sets per lane hold across a wavefront.  The one rule for the
@@ -360,8 +367,9 @@ static inline PA_HOST_DEVICE int pa_bj_wide_window(int w) {
   if (W <= 2048) return W;
   return (w + 64 + 255) & ~255;
 }
+/* pt: the pair tasks of `list` (NULL: none); whether the launch pairs is decided there (bj_g4.hip: the rule) */
 int pa_k_bj_g4(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int bmax, int xs, int ncol,
-                const double* in, double* out);
+                const double* in, double* out, const pa_bj_ptask_t* pt);
 /* One-shot: the next pa_k_bj_g4 on a 4-column panel also leaves the 8 x 4 block [in | prev]^T out of every
  * block in part (32 doubles per block, in the order of its list; the layout of pa_k_gram with two panels). */
 void pa_k_bj_g4_gram(const double* prev, double* part);
@@ -380,7 +388,7 @@ int pa_k_bj_g4_setup(const int* list, int count, const int* nrows, const int* bw
 int pa_k_bj_g4_setup_f32(const int* list, int count, const int* nrows, const int* bw, const long long* off,
                           const long long* off2, const double* L, float* Lg4);
 /* the last launch of pa_k_bj_g4: 0 = ring depth, 1 = storage bits of the records it read, 2 = 1 if it was the
- * pipelined few-blocks chain */
+ * pipelined few-blocks chain, 3 = 1 if it was the PAIR launch (two blocks of one class per wavefront) */
 int pa_bj_g4_last(int which);
 /* Band Cholesky on the device for blocks with bandwidth <= pa_bj_factor_wmax(): `band` holds
  * each listed block's rows in factor order, (w+1) doubles per row (A(i, i-d) at d), at offset
