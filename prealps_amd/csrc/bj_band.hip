@@ -1187,7 +1187,7 @@ int pa_k_bj_apply(const pa_bj_plan_t* pl, int ts, const double* in, double* out)
     int rc = 1;
     static int g4_wide = -1;      /* PREALPS_BJ_G4_WIDE=0: 8-column panels stay with k_bj_mfma */
     if (g4_wide < 0) { const char* e = getenv("PREALPS_BJ_G4_WIDE"); g4_wide = e ? atoi(e) : 1; }
-    if (pl->Lg4 && pl->class_g4[c] && (ts <= 4 || (ts == 8 && g4_wide && pl->class_wmax[c] <= pa_bj_g4_max_band8()))) {   /* one copy of the factor, matrix cores (bj_g4.hip) */
+    if (pl->Lg4 && pl->class_g4[c] && pa_bj_g4_takes_panel(pl->class_wmax[c], ts, g4_wide)) {   /* one copy of the factor, matrix cores (bj_g4.hip) */
       if (ts == 4 && g_bg.armed && pl->nclass == 1 && in == g_bg.in && out == g_bg.out && pl->class_count[c] <= g_bg.cap) {
         pa_k_bj_g4_gram(g_bg.prev, g_bg.partials);      // this apply also leaves [in | prev]^T out (pa_k_bj_gram_arm)
         g_bg.count = pl->class_count[c];

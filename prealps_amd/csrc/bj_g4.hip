@@ -45,34 +45,42 @@
 // (profiles/r20_pmc_bj_share.txt).  With every block distinct, or PREALPS_BJ_SHARE=0, it is what it was: 702-713 MB
 // per launch = 1.08-1.09 x the algorithmic bytes, 6.1-6.3 TB/s, 0.97-0.99 of what a plain read kernel streams on the
 // same device (profiles/r0*_pmc_hbm_traffic_elasticity.json).
-#include <hip/hip_runtime.h>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include "pa_device.h"
+//
+// This file is compiled nine times (bj_g4*.hip set G4_NT, G4_F32, G4_PAIR): the kernels of 12 / 14 / 16 register tiles,
+// of fp64 / fp32 records and of the PAIR launch in units of their own, so that they build in parallel.  How a launch
+// is shaped is decided in bj_g4_plan.c; the host half at the end of this file maps that decision onto a kernel.
+#include "kernels_common.h"
+#include "bj_g4_plan.h"
 
 #ifndef G4_NT
 #define G4_NT 12      /* this translation unit: 12 register tiles; bj_g4_nt14.hip / bj_g4_nt16.hip set 14 / 16 */
 #endif
 
-// a launch that a replayed graph segment makes in its place is skipped (runtime.hip: pa_rt_skip)
-#define PA_LAUNCH(...) do { if (!pa_rt_skipping()) hipLaunchKernelGGL(__VA_ARGS__); } while (0)
+// What a launch needs beside its shape (pa_bj_g4_launch_t): `count` wavefronts' worth of work -- the blocks of `list`,
+// or on the PAIR launch the tasks (i0, i1) of `tasks` -- and where the Gram by-product goes (used when the shape says gp).
+typedef struct {
+  const pa_bj_plan_t* pl;
+  const int* list; const int* tasks; int count;
+  int xs, ncol; const double* in; double* out;
+  const double* gprev; double* gpart;
+} pa_bj_g4_args_t;
 
-// One-shot request for the Gram block of the next launch (pa_k_bj_g4_gram; defined in the 12-tile unit)
-extern "C" {
-extern const double* pa_g4_gram_prev;
-extern double* pa_g4_gram_part;
-// what the last launch was: ring depth, storage bits of the records, 1 = the pipelined few-blocks chain, 1 = PAIR
-// (preAlps_hip_get_stat "bj_g4_last_ring" / "bj_g4_last_bits" / "bj_g4_last_pipelined" / "bj_g4_last_paired")
-extern int pa_g4_last[4];
-}
+// Each unit exports one entry, pa_k_bj_g4_<f64 | f32 | pair>_nt<12 | 14 | 16>: the launch on the kernels it holds.
+#if defined(G4_PAIR)
+#define G4_FLAVOUR pair
+#elif defined(G4_F32)
+#define G4_FLAVOUR f32
+#else
+#define G4_FLAVOUR f64
+#endif
+#define G4_ENTRY_NAME_(f, nt) pa_k_bj_g4_##f##_nt##nt
+#define G4_ENTRY_NAME(f, nt) G4_ENTRY_NAME_(f, nt)
+#define G4_ENTRY G4_ENTRY_NAME(G4_FLAVOUR, G4_NT)
 
 namespace {
 
 typedef __attribute__((address_space(3))) void* lds_ptr;
 typedef const __attribute__((address_space(1))) void* glb_ptr;
-
-inline hipStream_t cur_stream() { return (hipStream_t)pa_rt_stream(); }
 
 // ---------------------------------------------------------------------------------- set-up ----
 // Records from the plain forward records of bj_band.hip (rec[j * wr + d - 1] = L(j+d, j) / L(j, j)):
@@ -379,6 +387,9 @@ struct g4_gram { const double* prev; unsigned base[2], xs; double ap[2], gp[2]; 
 // outstanding, and the load of gr.ap sits among the youngest of them (behind the request of chunk (Q, 0), in front
 // of this chunk's own) -- it is waited for explicitly before the product reads it: everything but this chunk's own
 // request, if it made one.  (ring 2: the wait above already says exactly that.)
+// (The Gram-row request and take below stand a second time in g4_bwd_chunk_q.  Folded into one force-inlined helper
+// they compile to other code -- the operands of the row address' multiply-add change places in all 38 GP kernels --
+// so the two copies stay.)
 template <typename RT, int NC, int NT, int DQ, int Q, int H, bool GP, int NS>
 __device__ __forceinline__ void g4_bwd_chunk(double (&T)[NC * NT], int b, int w, const RT* __restrict__ rec,
                                              int chunk_doubles, double* lds0, int lstride, int lane, g4_lane ln,
@@ -451,28 +462,6 @@ template <int DQ> struct g4_ops { double a0, a1, a2; double cf[DQ]; };
 template <int DQ>
 __device__ __forceinline__ void g4_ops_wait(g4_ops<DQ>& o) { g4_wait_cf<DQ>(o.cf, o.a0, o.a1, o.a2); }
 
-template <int NT, int DQ, int Q, int GQ, bool FWD>
-__device__ __forceinline__ void g4_read_ops(unsigned cur, int w, g4_lane ln, g4_ops<DQ>& o) {
-  asm volatile("" : "+v"(ln.cX));
-  const unsigned zero_ad = cur + (unsigned)w * 32u, mine = zero_ad + ln.cg;
-  const bool here = ln.blk == GQ;
-  // forward: steps 0, 1, 2 = columns of the corner (lanes hi == k); backward: steps 3, 2, 1 = its rows, transposed
-  const unsigned adA = (here && ln.hi == (FWD ? 0 : 3)) ? mine : zero_ad;
-  const unsigned adB = (here && ln.hi == (FWD ? 1 : 2)) ? mine : zero_ad;
-  const unsigned adC = (here && ln.hi == (FWD ? 2 : 1)) ? mine : zero_ad;
-  asm volatile("ds_read_b64 %0, %1" : "=v"(o.a0) : "v"(adA));
-  asm volatile("ds_read_b64 %0, %1" : "=v"(o.a1) : "v"(adB));
-  asm volatile("ds_read_b64 %0, %1" : "=v"(o.a2) : "v"(adC));
-#pragma unroll
-  for (int dq = 0; dq < DQ; ++dq) {
-    o.cf[dq] = 0.0;
-    if (Q + dq < NT) {
-      const unsigned s = min((unsigned)(ln.cX - (16 * dq - 4 * GQ)), (unsigned)w);
-      const unsigned ad = cur + s * 32u + ln.aX;
-      asm volatile("ds_read_b64 %0, %1" : "=v"(o.cf[dq]) : "v"(ad));
-    }
-  }
-}
 // Few blocks: where a lane reads its operands depends on (GQ, dq) and the band only, not on the chunk -- with the
 // compile-time ring the chunk's buffer is an immediate offset of the read.  The 12 + 4 DQ LDS addresses of a
 // sweep are formed once (they were 25 vector instructions per group: compare, select, clamp, shift-add) and the
@@ -645,7 +634,7 @@ template <int NT, int DQ, int Q, int H>
 __device__ __forceinline__ void g4_fwd_chunk_p(double (&T)[NT], int b, const double* __restrict__ rec,
                                                int chunk_doubles, double* lds0, int lane, const g4_pre<DQ>& pre,
                                                g4_ops<DQ>& A, g4_ops<DQ>& B) {
-  constexpr int C = 2 * Q + H, NLD = DQ, LS = NLD * 128;
+  constexpr int C = 2 * Q + H, NLD = DQ;       // (a chunk step requests DQ pieces of 1 KiB)
   const int nch = (b + 7) >> 3;
   constexpr int cn = C + G4F_RING - 1;
   g4_request_c<NLD>(rec, chunk_doubles, cn, cn < nch, lds0, lane);
@@ -682,7 +671,7 @@ template <int NT, int DQ, int Q, int H>
 __device__ __forceinline__ void g4_bwd_chunk_p(double (&T)[NT], int b, const double* __restrict__ rec,
                                                int chunk_doubles, double* lds0, int lane, g4_lane ln, const g4_pre<DQ>& pre,
                                                g4_ops<DQ>& A, g4_ops<DQ>& B) {
-  constexpr int C = 2 * Q + H, NLD = DQ, LS = NLD * 128;
+  constexpr int C = 2 * Q + H, NLD = DQ;       // (a chunk step requests DQ pieces of 1 KiB)
   const int nch = (b + 7) >> 3;
   constexpr int cn = C - (G4F_RING - 1);
   g4_request_c<NLD>(rec, chunk_doubles, cn >= 0 ? cn : 0, cn >= 0 && C < nch - 1, lds0, lane);
@@ -1040,137 +1029,8 @@ __global__ __launch_bounds__(256, OCC) void k_bj_g4(
   }
 }
 
-char g_err[256];
-int kfail(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return 0;
-  snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-  fprintf(stderr, "[prealps_hip] kernel launch failed: %s\n", g_err);
-  return 1;
-}
-
-#ifdef G4_PAIR
-// ---- the PAIR launch (bj_g4_pair*.hip: this source with G4_PAIR set, one unit per NT) ---------------------------
-// ntasks wavefronts of two blocks each.  Always ring 2, the many-blocks configuration the rule below picks it for:
-// the hand-kept wait counts of the Gram rows (g4_bwd_chunk: extra) are written for that depth.  A ring buffer is at
-// most 6 KiB (bands up to pa_bj_g4_max_band8() = 80), four wavefronts 48 KiB: no attribute to set.  Three wavefronts
-// per SIMD by registers (profiles/r21_bj_pair_resources.txt), four by LDS.
-template <int NT, int DQ>
-int launch_pair(const pa_bj_plan_t* pl, const int* list, const int* tasks, int ntasks, int wmax, int xs, int ncol,
-                const double* in, double* out, const double* gprev, double* gpart) {
-  const int cbuf = DQ * 128;            // doubles per ring buffer: DQ KiB, a compile-time stride (g4_fwd_chunk_q)
-  if (8 * (wmax + 4) > cbuf) return 1;  // (launch_pair_dq picks DQ from wmax: wmax <= 16 DQ - 16)
-  const int ring = 2, per_wave = ring * cbuf;
-  const int waves = 4;
-  const size_t lds = (size_t)waves * per_wave * 8;
-  if (lds > 64 * 1024) return 1;
-  const int blocks = (ntasks + waves - 1) / waves;
-  const double* Lg4 = static_cast<const double*>(pl->Lg4);
-  pa_g4_last[0] = ring; pa_g4_last[1] = 64; pa_g4_last[2] = 0; pa_g4_last[3] = 1;
-  if (gpart && xs == 4 && ncol == 4)
-    PA_LAUNCH((k_bj_g4<2, NT, DQ, 3, true, false, double, 1>), dim3(blocks), dim3(64 * waves), lds, cur_stream(), list, tasks, ntasks,
-              pl->row0, pl->nrows, pl->bw, pl->off2, pl->map_f, Lg4, pl->invd_f, per_wave, ring, xs, ncol, in, out, gprev, gpart);
-  else
-    PA_LAUNCH((k_bj_g4<2, NT, DQ, 3, false, false, double, 1>), dim3(blocks), dim3(64 * waves), lds, cur_stream(), list, tasks, ntasks,
-              pl->row0, pl->nrows, pl->bw, pl->off2, pl->map_f, Lg4, pl->invd_f, per_wave, ring, xs, ncol, in, out,
-              (const double*)nullptr, (double*)nullptr);
-  return kfail("k_bj_g4 (pair)");
-}
-
-template <int NT>
-int launch_pair_dq(const pa_bj_plan_t* pl, const int* list, const int* tasks, int ntasks, int wmax, int xs, int ncol,
-                   const double* in, double* out, const double* gprev, double* gpart) {
-  switch (((wmax + 15) >> 4) + 1) {
-    case 1: case 2: case 3: return launch_pair<NT, 3>(pl, list, tasks, ntasks, wmax, xs, ncol, in, out, gprev, gpart);
-    case 4: return launch_pair<NT, 4>(pl, list, tasks, ntasks, wmax, xs, ncol, in, out, gprev, gpart);
-    case 5: return launch_pair<NT, 5>(pl, list, tasks, ntasks, wmax, xs, ncol, in, out, gprev, gpart);
-    case 6: return launch_pair<NT, 6>(pl, list, tasks, ntasks, wmax, xs, ncol, in, out, gprev, gpart);
-    default: return 1;
-  }
-}
-#else
-
-template <typename RT, int NC, int NT, int DQ, int OCC>
-int launch_occ(const int* list, int count, const pa_bj_plan_t* pl, int wmax, int xs, int ncol, const double* in, double* out) {
-  // a chunk is two groups of (wmax + 4) rows x 4 pivots of RT: sizeof(RT) (wmax + 4) doubles' worth of bytes
-  const int cbuf = ((int)sizeof(RT) * (wmax + 4) + 127) & ~127;        // doubles per ring buffer, a multiple of 1 KiB
-  const int nld = cbuf >> 7;                                            // LDS-DMA pieces (1 KiB each) per chunk
-  constexpr bool F64 = sizeof(RT) == 8;
-  const RT* Lg4 = static_cast<const RT*>(pl->Lg4);
-  // Ring depth.  Many blocks (the chip is filled several wavefronts deep): two buffers, the LDS then
-  // allows six wavefronts per SIMD.  Few blocks (fewer than two per SIMD: a shard of a multi-GPU run):
-  // a lone wavefront cannot hide the memory latency behind other wavefronts, so up to eight chunks in
-  // flight.  PREALPS_BJ_G4_RING overrides (2, 4, 8).
-  static int ring_env = -1;
-  if (ring_env < 0) { const char* e = getenv("PREALPS_BJ_G4_RING"); ring_env = e ? atoi(e) : 0; }
-  const int simds = 4 * (pa_rt_num_cus() > 0 ? pa_rt_num_cus() : 256);
-  int ring = ring_env == 2 || ring_env == 4 || ring_env == 8 ? ring_env : (count < 2 * simds ? 8 : 2);
-  while (ring > 2 && ((ring - 1) * nld > 15 || (size_t)ring * cbuf * 8 > 40 * 1024)) ring >>= 1;
-  // (Fewer resident blocks, so that a block's records survive in the Infinity Cache between its two sweeps, was
-  // tried with padded LDS in round 3: 130.4 / 144.9 us against 122.1 us.  The switch is gone.)
-  const int per_wave = ring * cbuf;
-  int waves = (160 * 1024) / (per_wave * 8);
-  if (waves > 4) waves = 4;
-  if (waves < 1) return 1;
-  const size_t lds = (size_t)waves * per_wave * 8;
-  static size_t configured = 0;
-  if (lds > 64 * 1024 && lds > configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bj_g4<NC, NT, DQ, OCC, false, false, RT>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-        (NC == 1 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bj_g4<NC, NT, DQ, OCC, NC == 1, false, RT>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess))
-      return kfail("hipFuncSetAttribute(k_bj_g4)");
-    configured = lds;
-  }
-  const int blocks = (count + waves - 1) / waves;
-  pa_g4_last[0] = ring; pa_g4_last[1] = 8 * (int)sizeof(RT); pa_g4_last[2] = 0; pa_g4_last[3] = 0;
-  // (fp32 records: no pipelined chain -- few blocks take the plain chain with the deep ring below, as the classes
-  // outside NT == 12 && DQ <= 5 do)
-  if constexpr (F64 && NC == 1 && NT == 12 && DQ <= 5) {
-    // few blocks (fewer than two per SIMD): the software-pipelined group chain with its compile-time ring
-    // (G4F_RING buffers of DQ KiB and the spare one per wavefront)
-    if (ring >= 4) {
-      const int per_wave_f = (G4F_RING + 1) * DQ * 128;
-      // single-wavefront workgroups: they fill the 160 KiB of a CU to the last buffer set (six blocks per CU at
-      // DQ = 5; four-wavefront workgroups of 100 KiB leave room for one).  Measured 1 / 2 / 4 wavefronts per
-      // workgroup: 20.7 / 24.8 / 20.7 us on 709 blocks (1/8 of the headline problem), 28.5 / 28.3 / 28.9 us on 1418
-      const int waves_f = 1;
-      const size_t lds_f = (size_t)waves_f * per_wave_f * 8;
-      static size_t configured_p = 0;
-      if (lds_f > 64 * 1024 && lds_f > configured_p) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bj_g4<NC, NT, DQ, 1, true, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bj_g4<NC, NT, DQ, 1, false, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f) != hipSuccess)
-          return kfail("hipFuncSetAttribute(k_bj_g4, pipelined)");
-        configured_p = lds_f;
-      }
-      const int blocks_f = (count + waves_f - 1) / waves_f;
-      pa_g4_last[0] = G4F_RING; pa_g4_last[2] = 1;
-      if (pa_g4_gram_part && xs == 4 && ncol == 4)
-        PA_LAUNCH((k_bj_g4<NC, NT, DQ, 1, true, true>), dim3(blocks_f), dim3(64 * waves_f), lds_f, cur_stream(), list, (const int*)nullptr, count, pl->row0,
-                  pl->nrows, pl->bw, pl->off2, pl->map_f, Lg4, pl->invd_f, per_wave_f, G4F_RING, xs, ncol, in, out,
-                  pa_g4_gram_prev, pa_g4_gram_part);
-      else
-        PA_LAUNCH((k_bj_g4<NC, NT, DQ, 1, false, true>), dim3(blocks_f), dim3(64 * waves_f), lds_f, cur_stream(), list, (const int*)nullptr, count, pl->row0,
-                  pl->nrows, pl->bw, pl->off2, pl->map_f, Lg4, pl->invd_f, per_wave_f, G4F_RING, xs, ncol, in, out,
-                  (const double*)nullptr, (double*)nullptr);
-      return kfail("k_bj_g4");
-    }
-  }
-  if constexpr (NC == 1) {
-    if (pa_g4_gram_part && xs == 4 && ncol == 4) {
-      PA_LAUNCH((k_bj_g4<NC, NT, DQ, OCC, true, false, RT>), dim3(blocks), dim3(64 * waves), lds, cur_stream(), list, (const int*)nullptr, count, pl->row0,
-                pl->nrows, pl->bw, pl->off2, pl->map_f, Lg4, pl->invd_f, per_wave, ring, xs, ncol, in, out,
-                pa_g4_gram_prev, pa_g4_gram_part);
-      return kfail("k_bj_g4");
-    }
-  }
-  PA_LAUNCH((k_bj_g4<NC, NT, DQ, OCC, false, false, RT>), dim3(blocks), dim3(64 * waves), lds, cur_stream(), list, (const int*)nullptr, count, pl->row0,
-            pl->nrows, pl->bw, pl->off2, pl->map_f, Lg4, pl->invd_f, per_wave, ring, xs, ncol, in, out,
-            (const double*)nullptr, (double*)nullptr);
-  return kfail("k_bj_g4");
-}
+// ------------------------------------------------------------------------------------ launch ----
+static_assert(G4F_RING == PA_BJ_G4_PIPE_RING, "the planner sizes the pipelined chain's LDS for G4F_RING buffers + 1");
 
 #ifdef G4_F32
 typedef float g4_rec_t;       /* this translation unit: the kernels that read fp32 records (bj_g4_f32*.hip) */
@@ -1178,93 +1038,83 @@ typedef float g4_rec_t;       /* this translation unit: the kernels that read fp
 typedef double g4_rec_t;
 #endif
 
-template <int NC, int NT, int DQ>
-int launch(const int* list, int count, const pa_bj_plan_t* pl, int wmax, int xs, int ncol, const double* in, double* out) {
-  return launch_occ<g4_rec_t, NC, NT, DQ, (NC == 1 && NT <= 12 && DQ <= 5) ? 5 : (NC == 1 ? 4 : 3)>(list, count, pl, wmax, xs, ncol, in, out);
+// The launch L on one kernel of this unit: the instance <NC, NT, DQ, OCC, ., PIPE, RT, PAIR> with the Gram by-product
+// (it exists for one column set and for PAIR) or without.  More than 64 KiB of dynamic LDS (the deep rings of the
+// few-blocks regime) is asked for once per instance and size, for both.
+template <int NC, int NT, int DQ, int OCC, bool PIPE, typename RT, int PAIR>
+int g4_run(const pa_bj_g4_launch_t& L, const pa_bj_g4_args_t& a) {
+  constexpr bool HASGP = NC == 1 || PAIR;
+  const auto plain = &k_bj_g4<NC, NT, DQ, OCC, false, PIPE, RT, PAIR>;
+  const auto gram = &k_bj_g4<NC, NT, DQ, OCC, HASGP, PIPE, RT, PAIR>;
+  if (L.nt != NT || L.occ != OCC || L.bits != 8 * (int)sizeof(RT)) {
+    pa_rt_set_error("k_bj_g4: a launch for %d tiles, occupancy %d, %d-bit records on the kernel for %d, %d, %d", L.nt,
+                    L.occ, L.bits, NT, OCC, 8 * (int)sizeof(RT));
+    return 1;
+  }
+  static int configured = 0;
+  if (L.lds > 64 * 1024 && L.lds > configured) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(plain), hipFuncAttributeMaxDynamicSharedMemorySize, L.lds) != hipSuccess ||
+        (HASGP && hipFuncSetAttribute(reinterpret_cast<const void*>(gram), hipFuncAttributeMaxDynamicSharedMemorySize, L.lds) != hipSuccess))
+      return kfail("hipFuncSetAttribute(k_bj_g4)");
+    configured = L.lds;
+  }
+  const pa_bj_plan_t* pl = a.pl;
+  const bool gp = HASGP && L.gp;
+  const auto kernel = gp ? gram : plain;
+  PA_LAUNCH(kernel, dim3(L.blocks), dim3(64 * L.waves), (size_t)L.lds, cur_stream(), a.list, a.tasks, a.count,
+            pl->row0, pl->nrows, pl->bw, pl->off2, pl->map_f, static_cast<const RT*>(pl->Lg4), pl->invd_f, L.per_wave, L.ring,
+            a.xs, a.ncol, a.in, a.out, gp ? a.gprev : (const double*)nullptr, gp ? a.gpart : (double*)nullptr);
+  return kfail(PAIR ? "k_bj_g4 (pair)" : PIPE ? "k_bj_g4 (pipelined)" : "k_bj_g4");
 }
 
-template <int NC, int NT>
-int launch_dq(const int* list, int count, const pa_bj_plan_t* pl, int wmax, int xs, int ncol, const double* in, double* out) {
-  const int dq = ((wmax + 15) >> 4) + 1;
-  switch (dq) {
-    case 1: case 2: case 3: return launch<NC, NT, 3>(list, count, pl, wmax, xs, ncol, in, out);
-    case 4: return launch<NC, NT, 4>(list, count, pl, wmax, xs, ncol, in, out);
-    case 5: return launch<NC, NT, 5>(list, count, pl, wmax, xs, ncol, in, out);
-    case 6: if constexpr (NC <= 2) return launch<NC, NT, 6>(list, count, pl, wmax, xs, ncol, in, out); else return 1;
-    case 7: if constexpr (NC == 1) return launch<NC, NT, 7>(list, count, pl, wmax, xs, ncol, in, out); else return 1;
-    case 8: if constexpr (NC == 1) return launch<NC, NT, 8>(list, count, pl, wmax, xs, ncol, in, out); else return 1;
-    default: return 1;
-  }
-}
-#endif  // G4_PAIR
+constexpr int g4_key(int kind, int nc, int dq) { return (kind * 4 + nc) * 16 + dq; }
 
 }  // namespace
 
 extern "C" {
 
+// This unit's entry: (kind, nc, dq) -> the template instance.  The occupancy hint is the planner's rule again, as a
+// compile-time number (g4_run refuses a launch that disagrees): one column set 5 with 12 tiles and DQ <= 5, else 4;
+// two sets and PAIR 3; the pipelined chain 1.
+int G4_ENTRY(const pa_bj_g4_launch_t* L, const pa_bj_g4_args_t* a) {
+  constexpr int NT = G4_NT;
+  switch (g4_key(L->kind, L->nc, L->dq)) {
 #ifdef G4_PAIR
-/* ---- the PAIR launch: three units (bj_g4_pair.hip, bj_g4_pair_nt14.hip, bj_g4_pair_nt16.hip), fp64 records only ---- */
-#if G4_NT == 12
-int pa_k_bj_g4_pair_nt12(const pa_bj_plan_t* pl, const int* list, const int* tasks, int ntasks, int wmax, int xs, int ncol,
-                         const double* in, double* out, const double* gprev, double* gpart) {
-  return launch_pair_dq<12>(pl, list, tasks, ntasks, wmax, xs, ncol, in, out, gprev, gpart);
-}
-#elif G4_NT == 14
-int pa_k_bj_g4_pair_nt14(const pa_bj_plan_t* pl, const int* list, const int* tasks, int ntasks, int wmax, int xs, int ncol,
-                         const double* in, double* out, const double* gprev, double* gpart) {
-  return launch_pair_dq<14>(pl, list, tasks, ntasks, wmax, xs, ncol, in, out, gprev, gpart);
-}
+    case g4_key(PA_BJ_G4_PAIR, 2, 3): return g4_run<2, NT, 3, 3, false, double, 1>(*L, *a);
+    case g4_key(PA_BJ_G4_PAIR, 2, 4): return g4_run<2, NT, 4, 3, false, double, 1>(*L, *a);
+    case g4_key(PA_BJ_G4_PAIR, 2, 5): return g4_run<2, NT, 5, 3, false, double, 1>(*L, *a);
+    case g4_key(PA_BJ_G4_PAIR, 2, 6): return g4_run<2, NT, 6, 3, false, double, 1>(*L, *a);
 #else
-int pa_k_bj_g4_pair_nt16(const pa_bj_plan_t* pl, const int* list, const int* tasks, int ntasks, int wmax, int xs, int ncol,
-                         const double* in, double* out, const double* gprev, double* gpart) {
-  return launch_pair_dq<16>(pl, list, tasks, ntasks, wmax, xs, ncol, in, out, gprev, gpart);
-}
+    case g4_key(PA_BJ_G4_PLAIN, 1, 3): return g4_run<1, NT, 3, (NT == 12 ? 5 : 4), false, g4_rec_t, 0>(*L, *a);
+    case g4_key(PA_BJ_G4_PLAIN, 1, 4): return g4_run<1, NT, 4, (NT == 12 ? 5 : 4), false, g4_rec_t, 0>(*L, *a);
+    case g4_key(PA_BJ_G4_PLAIN, 1, 5): return g4_run<1, NT, 5, (NT == 12 ? 5 : 4), false, g4_rec_t, 0>(*L, *a);
+    case g4_key(PA_BJ_G4_PLAIN, 1, 6): return g4_run<1, NT, 6, 4, false, g4_rec_t, 0>(*L, *a);
+    case g4_key(PA_BJ_G4_PLAIN, 1, 7): return g4_run<1, NT, 7, 4, false, g4_rec_t, 0>(*L, *a);
+    case g4_key(PA_BJ_G4_PLAIN, 1, 8): return g4_run<1, NT, 8, 4, false, g4_rec_t, 0>(*L, *a);
+    case g4_key(PA_BJ_G4_PLAIN, 2, 3): return g4_run<2, NT, 3, 3, false, g4_rec_t, 0>(*L, *a);
+    case g4_key(PA_BJ_G4_PLAIN, 2, 4): return g4_run<2, NT, 4, 3, false, g4_rec_t, 0>(*L, *a);
+    case g4_key(PA_BJ_G4_PLAIN, 2, 5): return g4_run<2, NT, 5, 3, false, g4_rec_t, 0>(*L, *a);
+    case g4_key(PA_BJ_G4_PLAIN, 2, 6): return g4_run<2, NT, 6, 3, false, g4_rec_t, 0>(*L, *a);
+#if G4_NT == 12 && !defined(G4_F32)
+    case g4_key(PA_BJ_G4_PIPE, 1, 3): return g4_run<1, 12, 3, 1, true, double, 0>(*L, *a);
+    case g4_key(PA_BJ_G4_PIPE, 1, 4): return g4_run<1, 12, 4, 1, true, double, 0>(*L, *a);
+    case g4_key(PA_BJ_G4_PIPE, 1, 5): return g4_run<1, 12, 5, 1, true, double, 0>(*L, *a);
 #endif
-#elif defined(G4_F32)
-/* ---- fp32 records: the same three units again (bj_g4_f32.hip, bj_g4_f32_nt14.hip, bj_g4_f32_nt16.hip) ---- */
-#if G4_NT == 12
+#endif
+  }
+  pa_rt_set_error("k_bj_g4: no kernel of %d tiles for chain %d, %d column sets, records over %d tiles", NT, L->kind, L->nc, L->dq);
+  return 1;
+}
+
+#if G4_NT == 12 && defined(G4_F32)
 int pa_k_bj_g4_setup_f32(const int* list, int count, const int* nrows, const int* bw, const long long* off,
                           const long long* off2, const double* L, float* Lg4) {
   if (count <= 0) return 0;
   PA_LAUNCH(k_bj_g4_setup<float>, dim3(count), dim3(256), 0, cur_stream(), list, nrows, bw, off, off2, L, Lg4);
   return kfail("k_bj_g4_setup<float>");
 }
-
-int pa_k_bj_g4_f32_nt14(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int xs, int ncol, const double* in, double* out);
-int pa_k_bj_g4_f32_nt16(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int xs, int ncol, const double* in, double* out);
-
-/* pa_k_bj_g4 for a plan whose records are fp32 (pl->g4_bits == 32; called from there) */
-int pa_k_bj_g4_f32(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int bmax, int xs, int ncol,
-                   const double* in, double* out) {
-  if (bmax > 224) return pa_k_bj_g4_f32_nt16(pl, list, count, wmax, xs, ncol, in, out);
-  if (bmax > 192) return pa_k_bj_g4_f32_nt14(pl, list, count, wmax, xs, ncol, in, out);
-  return ncol > 4 ? launch_dq<2, 12>(list, count, pl, wmax, xs, ncol, in, out)
-                  : launch_dq<1, 12>(list, count, pl, wmax, xs, ncol, in, out);
-}
-#elif G4_NT == 14
-int pa_k_bj_g4_f32_nt14(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int xs, int ncol, const double* in, double* out) {
-  return ncol > 4 ? launch_dq<2, 14>(list, count, pl, wmax, xs, ncol, in, out)
-                  : launch_dq<1, 14>(list, count, pl, wmax, xs, ncol, in, out);
-}
-#else
-int pa_k_bj_g4_f32_nt16(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int xs, int ncol, const double* in, double* out) {
-  return ncol > 4 ? launch_dq<2, 16>(list, count, pl, wmax, xs, ncol, in, out)
-                  : launch_dq<1, 16>(list, count, pl, wmax, xs, ncol, in, out);
-}
-#endif
-#elif G4_NT == 12
-const double* pa_g4_gram_prev = nullptr;
-double* pa_g4_gram_part = nullptr;
-int pa_g4_last[4] = {0, 0, 0, 0};
-int pa_bj_g4_last(int which) { return which >= 0 && which < 4 ? pa_g4_last[which] : 0; }
-/* The next pa_k_bj_g4 on a 4-column panel also leaves, per block (in the order of `list`), the 8 x 4 block
- * [in | prev]^T out in part (32 doubles each).  Cleared by that call. */
-void pa_k_bj_g4_gram(const double* prev, double* part) { pa_g4_gram_prev = prev; pa_g4_gram_part = part; }
-
-int pa_bj_g4_max_rows(void) { return 256; }
-int pa_bj_g4_max_band(void) { return 112; }
-int pa_bj_g4_max_band8(void) { return 80; }     /* panels of 5 .. 8 columns (two column sets per wavefront) */
-
+#elif G4_NT == 12 && !defined(G4_PAIR)
+/* ---- the 12-tile unit of fp64 records: the record set-up, the one-shot Gram request, the launch itself ---- */
 int pa_k_bj_g4_setup(const int* list, int count, const int* nrows, const int* bw, const long long* off,
                       const long long* off2, const double* L, double* Lg4) {
   if (count <= 0) return 0;
@@ -1272,70 +1122,56 @@ int pa_k_bj_g4_setup(const int* list, int count, const int* nrows, const int* bw
   return kfail("k_bj_g4_setup");
 }
 
-int pa_k_bj_g4_nt14(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int xs, int ncol, const double* in, double* out);
-int pa_k_bj_g4_nt16(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int xs, int ncol, const double* in, double* out);
-int pa_k_bj_g4_f32(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int bmax, int xs, int ncol,
-                   const double* in, double* out);
+/* The next pa_k_bj_g4 on a 4-column panel also leaves, per block (in the order of `list`), the 8 x 4 block
+ * [in | prev]^T out in part (32 doubles each).  Cleared by that call. */
+static const double* pa_g4_gram_prev = nullptr;
+static double* pa_g4_gram_part = nullptr;
+void pa_k_bj_g4_gram(const double* prev, double* part) { pa_g4_gram_prev = prev; pa_g4_gram_part = part; }
+/* what the last launch was: ring depth, storage bits of the records, 1 = the pipelined few-blocks chain, 1 = PAIR
+ * (preAlps_hip_get_stat "bj_g4_last_ring" / "bj_g4_last_bits" / "bj_g4_last_pipelined" / "bj_g4_last_paired") */
+static int pa_g4_last[4] = {0, 0, 0, 0};
+int pa_bj_g4_last(int which) { return which >= 0 && which < 4 ? pa_g4_last[which] : 0; }
 
-int pa_k_bj_g4_pair_nt12(const pa_bj_plan_t* pl, const int* list, const int* tasks, int ntasks, int wmax, int xs, int ncol,
-                         const double* in, double* out, const double* gprev, double* gpart);
-int pa_k_bj_g4_pair_nt14(const pa_bj_plan_t* pl, const int* list, const int* tasks, int ntasks, int wmax, int xs, int ncol,
-                         const double* in, double* out, const double* gprev, double* gpart);
-int pa_k_bj_g4_pair_nt16(const pa_bj_plan_t* pl, const int* list, const int* tasks, int ntasks, int wmax, int xs, int ncol,
-                         const double* in, double* out, const double* gprev, double* gpart);
+int pa_k_bj_g4_f64_nt14(const pa_bj_g4_launch_t* L, const pa_bj_g4_args_t* a);
+int pa_k_bj_g4_f64_nt16(const pa_bj_g4_launch_t* L, const pa_bj_g4_args_t* a);
+int pa_k_bj_g4_f32_nt12(const pa_bj_g4_launch_t* L, const pa_bj_g4_args_t* a);
+int pa_k_bj_g4_f32_nt14(const pa_bj_g4_launch_t* L, const pa_bj_g4_args_t* a);
+int pa_k_bj_g4_f32_nt16(const pa_bj_g4_launch_t* L, const pa_bj_g4_args_t* a);
+int pa_k_bj_g4_pair_nt12(const pa_bj_g4_launch_t* L, const pa_bj_g4_args_t* a);
+int pa_k_bj_g4_pair_nt14(const pa_bj_g4_launch_t* L, const pa_bj_g4_args_t* a);
+int pa_k_bj_g4_pair_nt16(const pa_bj_g4_launch_t* L, const pa_bj_g4_args_t* a);
 
-/* The rule of the PAIR launch: two blocks of one class of identical blocks per wavefront, the
- * record read once for both.  Possible at all: the class has pair tasks with at least one pair, fp64 records, a
- * panel of up to 4 columns, bands the two-set kernels take, and no refresh has split a class since the create (a block
- * that reads its own records again must not be served from its partner's).  PREALPS_BJ_PAIR=1: then always; =0: never;
- * unset: the default below, and then in the many-blocks regime only (at least two blocks per SIMD -- below that the
- * pipelined few-blocks chain stays) and when at least half of the list's blocks have a partner. */
-#define G4_PAIR_DEFAULT 1
-static int g4_pairs(const pa_bj_plan_t* pl, const pa_bj_ptask_t* pt, int count, int wmax, int bmax, int xs, int ncol) {
-  if (!pt || !pt->tasks || pt->paired < 2 || pl->pair_mode == 0 || !pl->pair_intact) return 0;
-  if (pl->g4_bits != 64 || xs > 4 || ncol > 4 || wmax > pa_bj_g4_max_band8()) return 0;
-  if (pl->pair_mode == 1) return 1;
-  if (!G4_PAIR_DEFAULT) return 0;
-  /* measured (profiles/r21_bj_pair_speed.txt): the launch gains where it runs on precomputed operand addresses -- up to
-   * 192 rows and bands up to 48 -- and gains nothing or loses elsewhere */
-  if (bmax > 192 || wmax > 48) return 0;
-  const int simds = 4 * (pa_rt_num_cus() > 0 ? pa_rt_num_cus() : 256);
-  return count >= 2 * simds && 2 * pt->paired >= count;
-}
-
-/* One class of blocks (all with at most bmax rows and bands up to wmax) on a panel of row stride xs:
- * the ncol <= 8 columns starting at `in` / `out` (more than 4: bands up to pa_bj_g4_max_band8()).  The
- * kernels for 12 / 14 / 16 register tiles are compiled in three translation units (bj_g4.hip,
- * bj_g4_nt14.hip, bj_g4_nt16.hip: the same source, G4_NT set) so that they build in parallel; those that read
- * fp32 records (PREALPS_BJ_BAND_PRECISION=single) in three more (bj_g4_f32*.hip: G4_F32 set as well). */
+/* One class of blocks (all with at most bmax rows and bands up to wmax) on a panel of row stride xs: the ncol <= 8
+ * columns starting at `in` / `out` (more than 4: bands up to pa_bj_g4_max_band8()).  All the bookkeeping of a launch
+ * happens here, once: the query, the plan (bj_g4_plan.c; a refusal goes to pa_rt_error() with its reason), the
+ * one-shot Gram request, what pa_bj_g4_last reports -- then the unit that holds the kernel. */
 int pa_k_bj_g4(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int bmax, int xs, int ncol,
                const double* in, double* out, const pa_bj_ptask_t* pt) {
   if (count <= 0) return 0;
-  int rc;
-  if (g4_pairs(pl, pt, count, wmax, bmax, xs, ncol)) {
-    const double* gprev = xs == 4 && ncol == 4 ? pa_g4_gram_prev : nullptr;
-    double* gpart = xs == 4 && ncol == 4 ? pa_g4_gram_part : nullptr;
-    rc = bmax > 224 ? pa_k_bj_g4_pair_nt16(pl, list, pt->tasks, pt->ntasks, wmax, xs, ncol, in, out, gprev, gpart)
-       : bmax > 192 ? pa_k_bj_g4_pair_nt14(pl, list, pt->tasks, pt->ntasks, wmax, xs, ncol, in, out, gprev, gpart)
-                    : pa_k_bj_g4_pair_nt12(pl, list, pt->tasks, pt->ntasks, wmax, xs, ncol, in, out, gprev, gpart);
-  }
-  else if (pl->g4_bits == 32) rc = pa_k_bj_g4_f32(pl, list, count, wmax, bmax, xs, ncol, in, out);     /* fp32 records */
-  else if (bmax > 224) rc = pa_k_bj_g4_nt16(pl, list, count, wmax, xs, ncol, in, out);
-  else if (bmax > 192) rc = pa_k_bj_g4_nt14(pl, list, count, wmax, xs, ncol, in, out);
-  else rc = ncol > 4 ? launch_dq<2, 12>(list, count, pl, wmax, xs, ncol, in, out)
-                     : launch_dq<1, 12>(list, count, pl, wmax, xs, ncol, in, out);
+  static int ring_env = -1;     /* PREALPS_BJ_G4_RING: 2, 4 or 8 sets the ring depth */
+  if (ring_env < 0) { const char* e = getenv("PREALPS_BJ_G4_RING"); ring_env = e ? atoi(e) : 0; if (ring_env < 0) ring_env = 0; }
+  const int have_tasks = pt && pt->tasks;
+  pa_bj_g4_query_t q;
+  q.count = count; q.wmax = wmax; q.bmax = bmax; q.xs = xs; q.ncol = ncol;
+  q.bits = pl->g4_bits;
+  q.gram = pa_g4_gram_part != nullptr;
+  q.cus = pa_rt_num_cus();
+  q.ring_env = ring_env;
+  q.pair_mode = pl->pair_mode; q.pair_intact = pl->pair_intact;
+  q.have_tasks = have_tasks; q.ntasks = have_tasks ? pt->ntasks : 0; q.paired = have_tasks ? pt->paired : 0;
+  const double* gprev = pa_g4_gram_prev;
+  double* gpart = pa_g4_gram_part;
   pa_g4_gram_prev = nullptr; pa_g4_gram_part = nullptr;
-  return rc;
-}
-#elif G4_NT == 14
-int pa_k_bj_g4_nt14(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int xs, int ncol, const double* in, double* out) {
-  return ncol > 4 ? launch_dq<2, 14>(list, count, pl, wmax, xs, ncol, in, out)
-                  : launch_dq<1, 14>(list, count, pl, wmax, xs, ncol, in, out);
-}
-#else
-int pa_k_bj_g4_nt16(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int xs, int ncol, const double* in, double* out) {
-  return ncol > 4 ? launch_dq<2, 16>(list, count, pl, wmax, xs, ncol, in, out)
-                  : launch_dq<1, 16>(list, count, pl, wmax, xs, ncol, in, out);
+  pa_bj_g4_launch_t L;
+  char why[128];
+  if (pa_bj_g4_plan(&q, &L, why, (int)sizeof(why))) { pa_rt_set_error("pa_k_bj_g4: %s", why); return 1; }
+  for (int i = 0; i < 4; ++i) pa_g4_last[i] = L.last[i];
+  const bool pair = L.kind == PA_BJ_G4_PAIR;
+  const pa_bj_g4_args_t a = {pl, list, pair ? pt->tasks : nullptr, pair ? pt->ntasks : count, xs, ncol, in, out,
+                             L.gp ? gprev : nullptr, L.gp ? gpart : nullptr};
+  if (pair) return L.nt == 16 ? pa_k_bj_g4_pair_nt16(&L, &a) : L.nt == 14 ? pa_k_bj_g4_pair_nt14(&L, &a) : pa_k_bj_g4_pair_nt12(&L, &a);
+  if (L.bits == 32) return L.nt == 16 ? pa_k_bj_g4_f32_nt16(&L, &a) : L.nt == 14 ? pa_k_bj_g4_f32_nt14(&L, &a) : pa_k_bj_g4_f32_nt12(&L, &a);
+  return L.nt == 16 ? pa_k_bj_g4_f64_nt16(&L, &a) : L.nt == 14 ? pa_k_bj_g4_f64_nt14(&L, &a) : pa_k_bj_g4_f64_nt12(&L, &a);
 }
 #endif
 

@@ -50,7 +50,7 @@ typedef struct {
   double share_s;                                                  /* seconds of the class pass */
   /* The pair tasks of the classes that bj_g4.hip serves from fp64 records (bj_share.h: pa_bj_pair_tasks), built at the
    * create from the create's classes and never changed: the PAIR launch is only taken while no class has split
-   * (plan.pair_intact, set again by every refresh). */
+   * (plan.pair_intact, set again by every refresh; the rule itself is the launch planner's, bj_g4_plan.c). */
   int* d_ptask[PA_BJ_MAX_CLASSES]; pa_bj_ptask_t class_ptask[PA_BJ_MAX_CLASSES];
   int pair_mode, pair_tasks, paired_blocks;                        /* PREALPS_BJ_PAIR as the create read it; sums over the classes */
   void* d_Lg4; int g4_bits; double g4_bytes;                   /* one-copy records of bj_g4.hip (optional) */

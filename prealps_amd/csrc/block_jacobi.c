@@ -216,8 +216,8 @@ static int bj_upload_share(pa_bj_t* s) {
 
 /* ---- stage 8b: the pair tasks of the classes of the layout that bj_g4.hip serves ---- */
 /* Behind the class pass and the second layouts: for every class of the layout with fp64 one-copy records, the tasks
- * (i0, i1) of its launch list (bj_share.h), built once and uploaded once.  Whether a launch takes them is bj_g4.hip's
- * rule; with no sharing every block is a class of one and no list has a pair. */
+ * (i0, i1) of its launch list (bj_share.h), built once and uploaded once.  Whether a launch takes them is the launch
+ * planner's rule (bj_g4_plan.c); with no sharing every block is a class of one and no list has a pair. */
 static int bj_pair_pass(pa_bj_t* s, int pair_mode) {
   const pa_bj_layout_t* L = &s->lay;
   int rc = 0;

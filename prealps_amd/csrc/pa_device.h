@@ -8,6 +8,7 @@
 #ifndef PA_DEVICE_H
 #define PA_DEVICE_H
 #include <stddef.h>
+#include "bj_g4_plan.h"    /* pa_bj_g4_max_rows / _max_band / _max_band8: the limits of the band block solve */
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -349,7 +350,7 @@ typedef struct {
   /* optional (NULL: absent): the pair tasks of the classes that bj_g4.hip serves from fp64 records (bj_share.h:
    * pa_bj_pair_tasks), two blocks of one class of identical blocks per wavefront */
   const pa_bj_ptask_t* class_ptask;  /* host array, nclass */
-  int pair_mode;           /* PREALPS_BJ_PAIR: 0 never, 1 whenever a list has a pair, -1 (absent) the rule of bj_g4.hip */
+  int pair_mode;           /* PREALPS_BJ_PAIR: 0 never, 1 whenever a list has a pair, -1 (absent) the rule of bj_g4_plan.c */
   int pair_intact;         /* 1: every block reads the records it read at the create (no refresh has split a class) */
 } pa_bj_plan_t;
 /* Window of a wide block (rows in flight = record length, >= w + 64) for bandwidth w: a multiple of the
@@ -367,7 +368,8 @@ static inline PA_HOST_DEVICE int pa_bj_wide_window(int w) {
   if (W <= 2048) return W;
   return (w + 64 + 255) & ~255;
 }
-/* pt: the pair tasks of `list` (NULL: none); whether the launch pairs is decided there (bj_g4.hip: the rule) */
+/* pt: the pair tasks of `list` (NULL: none); whether the launch pairs is decided by the planner (bj_g4_plan.c: the
+ * rule).  A launch the planner refuses returns 1 with the reason in pa_rt_error(). */
 int pa_k_bj_g4(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int bmax, int xs, int ncol,
                 const double* in, double* out, const pa_bj_ptask_t* pt);
 /* One-shot: the next pa_k_bj_g4 on a 4-column panel also leaves the 8 x 4 block [in | prev]^T out of every
@@ -377,11 +379,8 @@ int pa_bj_max_R(void);
 int pa_k_bj_pairs(const int* list, int count, const int* nrows, const int* bw, const long long* off,
                   const long long* off2, const double* L, double* L2);
 /* bj_g4.hip: the records of Lg4 from the plain forward records, and the block solve that reads them
- * (blocks of at most pa_bj_g4_max_rows() rows, bands up to pa_bj_g4_max_band()); `in` / `out` point
- * at the first of up to four columns of panels with row stride xs. */
-int pa_bj_g4_max_rows(void);
-int pa_bj_g4_max_band(void);
-int pa_bj_g4_max_band8(void);
+ * (blocks of at most pa_bj_g4_max_rows() rows, bands up to pa_bj_g4_max_band(): bj_g4_plan.h, which knows the
+ * limits); `in` / `out` point at the first of up to four columns of panels with row stride xs. */
 int pa_k_bj_g4_setup(const int* list, int count, const int* nrows, const int* bw, const long long* off,
                       const long long* off2, const double* L, double* Lg4);
 /* the same records rounded to fp32: (float)v of the same fp64 value at the same position */

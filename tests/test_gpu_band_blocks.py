@@ -4,7 +4,7 @@ componentwise backward error of every block.
 Inputs.  Blocks L0 L0^T with prescribed rows b and a full band of exactly w, dense in values, optionally graded
 (condition up to 7e6), shuffled (the library's RCM order, a non-identity row map) or coupled.  Blocks far below their
 class maximum sit beside full-size ones; the class maxima sit on the edges of the dispatch: bands 32/33 .. 112/113
-(launch_dq, the 4/6/8 tiles of k_bj_mfma, pa_bj_g4_max_band8, pa_bj_factor_wmax, pa_bj_g4_max_band), rows 192/193,
+(the DQ of bj_g4_plan.c, the 4/6/8 tiles of k_bj_mfma, pa_bj_g4_max_band8, pa_bj_factor_wmax, pa_bj_g4_max_band), rows 192/193,
 224/225, 256/257 (12/14/16 register tiles, then out of bj_g4), register classes at 64 k.
 
 Criterion.  With B the scaled matrix (O.symrac_scale + O.permute_by_part), A_q = B[q, q], L its numpy Cholesky
@@ -214,7 +214,7 @@ def _family(cl, t, env, bits):
 
 
 def _g4_launch(cl, bits, ring_env, t):
-    """(ring depth, pipelined) that launch_occ reports for the class: G4F_RING = 4 buffers on the pipelined chain."""
+    """(ring depth, pipelined) that the launch planner (bj_g4_plan.c) reports for the class: G4F_RING = 4 buffers on the pipelined chain."""
     wmax, bmax = cl[1], cl[2]
     cbuf = ((bits // 8) * (wmax + 4) + 127) & ~127
     nld = cbuf >> 7
@@ -461,7 +461,7 @@ def test_mixed_rows_shuffled():
 # ---- 2. one case per band depth -------------------------------------------------------------------------------------
 @pytest.mark.parametrize("wmax", [32, 48, 64, 80, 96, 112])
 def test_every_band_depth_of_the_one_copy_records(wmax):
-    """The class maximum on the last band of each ring-buffer size of launch_dq (DQ = 3 .. 8 KiB), the other blocks
+    """The class maximum on the last band of each ring-buffer size of the launch planner (DQ = 3 .. 8 KiB), the other blocks
     15 and 16 below it and at the first band of the class; t = 4 for all, t = 8 on two column sets up to band 80
     (pa_bj_g4_max_band8) and on k_bj_mfma's 8 tiles above."""
     recs = run_apply("depth%d" % wmax, [4, 8], env=WAVEFRONT)
@@ -539,7 +539,7 @@ def test_ring_depths(ring):
     chain on the 12-tile build up to band 64 and the plain chain with as deep a ring as the LDS-DMA limit allows
     elsewhere: a chunk of band 80 or 112 is 6 or 8 LDS-DMA pieces and the ring stays at 2; 256 rows at band 40 are 3
     pieces, at most 4 buffers; at band 28 they are 2 pieces, and 8 buffers are allowed.  The class of the widest band
-    is launched last (_main_class_last): what that launch reported is compared with launch_occ's rule."""
+    is launched last (_main_class_last): what that launch reported is compared with the planner's rule (bj_g4_plan.c)."""
     jobs = [dict(fn="run_apply", name=n, ts=[4], grading=g, env=WAVEFRONT)
             for n, g in (("mixed", 3.0), ("depth80", 0.0), ("rows256", 0.0), ("rows256-40", 0.0), ("rows256-28", 0.0))]
     recs = _run_child(jobs, {"PREALPS_BJ_G4_RING": str(ring)})

@@ -166,7 +166,7 @@ def _run_child(snippet, env, timeout):
 
 
 def _ring_allowed(req, wmax):
-    """launch_occ's cap on the ring depth for fp32 records of band wmax: at most 15 LDS-DMA pieces of 1 KiB in flight
+    """The launch planner's (bj_g4_plan.c) cap on the ring depth for fp32 records of band wmax: at most 15 LDS-DMA pieces of 1 KiB in flight
     and at most 40 KiB of LDS per wavefront."""
     nld = (32 * (wmax + 4) + 1023) // 1024
     ring = req

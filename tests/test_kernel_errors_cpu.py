@@ -36,6 +36,17 @@ def test_update_xrz_reports_the_panel_width(L):
     assert nblk.value == -1
 
 
+def test_block_solve_reports_what_its_planner_refuses(L):
+    """bj_g4.hip reports where the other kernel units do: a plan of all zeros has records of 0 bits, which the launch
+    planner (bj_g4_plan.c) refuses before anything is looked up or launched"""
+    plan = C.create_string_buffer(1024)            # a zero-filled pa_bj_plan_t (and room to spare)
+    L.pa_k_bj_g4.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                             C.c_void_p]
+    L.pa_k_bj_g4.restype = C.c_int
+    rc = L.pa_k_bj_g4(plan, None, 1, 8, 64, 4, 4, None, None, None)
+    _refused(L, rc, "pa_k_bj_g4: records of 0 bits (64 or 32)")
+
+
 def test_rowsum_reports_an_unsupported_stride(L):
     rc = L.pa_k_rowsum(64, 3, 3, None, None)
     _refused(L, rc, "unsupported panel stride 3")
