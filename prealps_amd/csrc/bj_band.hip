@@ -948,152 +948,49 @@ __global__ __launch_bounds__(NT) void k_bj_wide(
 
 }  // namespace
 
-template <int TS, int CH, int XS>
-static int bj_launch_ch(const pa_bj_plan_t* pl, int R, int wmax, const int* list, int count,
-                        const double* in, double* out) {
-  // LDS per wave: two chunk buffers of CH records of the widest band in this class
-  const int wr = (wmax + 2) & ~1;
-  // Two chunk buffers.  (A ring of three with counted waits measured neutral in round 2 -- 183.6 vs 187.1 us
-  // on elasticity, 173.6 vs 172.1 on Poisson, same box: the sweep does not wait for its band -- and its
-  // switch is gone; the kernels still take the ring depth as an argument.)
-  const int cbuf = (CH * wr + 127) & ~127;      // doubles, each buffer a multiple of 1 KiB
-  const int nbuf = 2;
-  int per_wave = nbuf * cbuf;
-  int waves = (160 * 1024) / (per_wave * 8);
-  if (waves > 4) waves = 4;
-  if (waves < 1) { pa_rt_set_error("block-Jacobi band too wide for LDS (R=%d)", R); return 1; }
-  const size_t lds = (size_t)waves * per_wave * 8;
-  const int units = count * (XS / TS);   // one wavefront per (subdomain, column group)
-  const int blocks = (units + waves - 1) / waves;
-#define BJ_CASE(RR)                                                                               \
-  case RR: {                                                                                      \
-    static size_t configured = 0;                                                                 \
-    if (lds > 64 * 1024 && lds > configured) {                                                    \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bj_apply<TS, RR, CH, XS, 1>),          \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-        return kfail("hipFuncSetAttribute(k_bj_apply)");                                          \
-      configured = lds;                                                                           \
-    }                                                                                             \
-    PA_LAUNCH((k_bj_apply<TS, RR, CH, XS, 1>), dim3(blocks), dim3(64 * waves), lds,          \
-                       cur_stream(), list, count, pl->row0, pl->nrows, pl->bw, pl->off,           \
-                       pl->map_f, pl->map_b, pl->Lf, pl->Lb, pl->invd_f, pl->invd_b, per_wave, nbuf, in, out); \
-  } break;
-  // paired records (pa_k_bj_pairs ran at setup): classes R = 2, 3 at up to 4 columns
-  if constexpr (TS <= 4) {
-    if (pl->Lf2 && (R == 2 || R == 3)) {
-      const int wr2 = wmax + 4;
-      const int cb2 = (CH * wr2 + 127) & ~127;
-      const int nbuf2 = 2;
-      const int pw2 = nbuf2 * cb2;
-      int wv2 = (160 * 1024) / (pw2 * 8);
-      if (wv2 > 4) wv2 = 4;
-      if (wv2 >= 1) {
-        const size_t lds2 = (size_t)wv2 * pw2 * 8;
-        const int blocks2 = (units + wv2 - 1) / wv2;
-        static size_t conf2[2] = {0, 0};
-        const void* fn = R == 2 ? reinterpret_cast<const void*>(&k_bj_apply_pairs<TS, 2, CH, XS>)
-                                : reinterpret_cast<const void*>(&k_bj_apply_pairs<TS, 3, CH, XS>);
-        if (lds2 > 64 * 1024 && lds2 > conf2[R - 2]) {
-          if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) != hipSuccess)
-            return kfail("hipFuncSetAttribute(k_bj_apply_pairs)");
-          conf2[R - 2] = lds2;
-        }
-        if (R == 2)
-          PA_LAUNCH((k_bj_apply_pairs<TS, 2, CH, XS>), dim3(blocks2), dim3(64 * wv2), lds2, cur_stream(), list, count,
-                             pl->row0, pl->nrows, pl->bw, pl->off2, pl->map_f, pl->map_b, pl->Lf2, pl->Lb2, pl->invd_f,
-                             pl->invd_b, pw2, nbuf2, in, out);
-        else
-          PA_LAUNCH((k_bj_apply_pairs<TS, 3, CH, XS>), dim3(blocks2), dim3(64 * wv2), lds2, cur_stream(), list, count,
-                             pl->row0, pl->nrows, pl->bw, pl->off2, pl->map_f, pl->map_b, pl->Lf2, pl->Lb2, pl->invd_f,
-                             pl->invd_b, pw2, nbuf2, in, out);
-        return kfail("k_bj_apply_pairs");
-      }
-    }
+// ---- the launcher of the apply kernels.  Which family serves a class and how it is launched is decided in
+// bj_band_plan.c; bj_launch maps that description onto the template instance that has its numbers compiled in.
+// One launch of the instance K as L describes it; more than 64 KiB of dynamic LDS needs the attribute, set once per
+// instance and size.
+template <auto K, typename... A>
+static int bj_go(const pa_bj_band_launch_t& L, const char* what, A... args) {
+  static int configured = 0;
+  if (L.lds > 64 * 1024 && L.lds > configured) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, L.lds);
+    if (e != hipSuccess) { pa_rt_set_error("hipFuncSetAttribute(%s): %s", what, hipGetErrorString(e)); return 1; }
+    configured = L.lds;
   }
-  switch (R) {
-    BJ_CASE(1) BJ_CASE(2) BJ_CASE(3) BJ_CASE(4) BJ_CASE(5) BJ_CASE(6) BJ_CASE(7) BJ_CASE(8)
-    default:
-      pa_rt_set_error("block-Jacobi bandwidth class R=%d unsupported", R);
-      return 1;
-  }
-#undef BJ_CASE
-  return kfail("k_bj_apply");
+  PA_LAUNCH(K, dim3(L.blocks), dim3(L.threads), (size_t)L.lds, cur_stream(), args...);
+  return kfail(what);
 }
 
-template <int TS>
-static int bj_launch(const pa_bj_plan_t* pl, int R, int wmax, const int* list, int count,
-                     const double* in, double* out) {
-  // chunks of 8 steps: measured equal or better than 16 and 32 (smaller LDS footprint,
-  // more workgroups per CU)
-  // The matrix-core sweep (k_bj_mfma, bands up to 112) costs 210-250 us per apply whatever the
-  // panel width (latency: three wavefronts per SIMD, the chain of three lane moves and the
-  // pivot tile's MFMA per group of pivots), the register recurrence 172 / 246 / 443 us at
-  // 4 / 8 / 16 columns: so it takes the panels of 8 and 16 columns.
-  // PREALPS_BJ_MFMA=0: never; 2: always.
-  static int use_mfma = -1;
-  if (use_mfma < 0) { const char* e = getenv("PREALPS_BJ_MFMA"); use_mfma = e ? atoi(e) : 1; }
-  if (wmax <= 112 && ((TS >= 8 && use_mfma == 1) || use_mfma == 2)) {
-    const int wr = (wmax + 2) & ~1;
-    int per_wave = 2 * ((8 * wr + 127) & ~127);
-    int waves = 4;
-    const size_t lds = (size_t)waves * per_wave * 8;
-    const int blocks = (count + waves - 1) / waves;
-#define BJM_LAUNCH(NTT)                                                                              \
-    PA_LAUNCH((k_bj_mfma<TS, NTT>), dim3(blocks), dim3(64 * waves), lds, cur_stream(), list, count, \
-                       pl->row0, pl->nrows, pl->bw, pl->off, pl->map_f, pl->map_b, pl->Lf, pl->Lb,   \
-                       pl->invd_f, pl->invd_b, per_wave, in, out)
-    if (wmax <= 48) BJM_LAUNCH(4); else if (wmax <= 80) BJM_LAUNCH(6); else BJM_LAUNCH(8);
-#undef BJM_LAUNCH
-    return kfail("k_bj_mfma");
-  }
-  // (Panels of 8 / 16 columns as 2 / 4 wavefronts of 4 columns each per subdomain measured slower in round 1 --
-  // each wavefront streams the factor again through L2: 257 vs 243 us at 8 columns, 485 vs 434 us at 16 -- and
-  // the variant is gone.)
-  // Few blocks (a GPU of a multi-GPU run holds 1/8 of them): below one wavefront per SIMD the
-  // sweep is latency bound, so a 4-column panel is shared by two wavefronts of 2 columns each
-  // (half the FMAs and pivot broadcasts per wavefront; the band is read twice, from L2).
-  if constexpr (TS == 4) {
-    const int simds = 4 * (pa_rt_num_cus() > 0 ? pa_rt_num_cus() : 256);
-    if (count < simds) return bj_launch_ch<2, 8, 4>(pl, R, wmax, list, count, in, out);
-  }
-  return bj_launch_ch<TS, 8, TS>(pl, R, wmax, list, count, in, out);
-}
+// what every apply kernel takes first (OFF, LF, LB: the plain or the paired records)
+#define BJ_BLOCKS(OFF, LF, LB) list, count, pl->row0, pl->nrows, pl->bw, pl->OFF, pl->map_f, pl->map_b, pl->LF, pl->LB, pl->invd_f, pl->invd_b
+// (family, TS, XS -- k_bj_wide: the thread bound / 256 --, R -- k_bj_mfma: the tiles)
+#define BJ_KEY(f, a, b, c) ((((f) * 32 + (a)) * 32 + (b)) * 32 + (c))
+#define BJ_APPLY(TS, XS, R) case BJ_KEY(PA_BJ_BAND_APPLY, TS, XS, R): \
+  return bj_go<&k_bj_apply<TS, R, PA_BJ_BAND_CHUNK, XS, 1>>(L, "k_bj_apply", BJ_BLOCKS(off, Lf, Lb), L.per_wave, L.nbuf, in, out);
+#define BJ_APPLY8(TS, XS) BJ_APPLY(TS, XS, 1) BJ_APPLY(TS, XS, 2) BJ_APPLY(TS, XS, 3) BJ_APPLY(TS, XS, 4) BJ_APPLY(TS, XS, 5) BJ_APPLY(TS, XS, 6) BJ_APPLY(TS, XS, 7) BJ_APPLY(TS, XS, 8)
+// paired records (pa_k_bj_pairs ran at setup): classes R = 2, 3 at up to 4 columns
+#define BJ_PAIRS(TS, XS, R) case BJ_KEY(PA_BJ_BAND_APPLY_PAIRS, TS, XS, R): \
+  return bj_go<&k_bj_apply_pairs<TS, R, PA_BJ_BAND_CHUNK, XS>>(L, "k_bj_apply_pairs", BJ_BLOCKS(off2, Lf2, Lb2), L.per_wave, L.nbuf, in, out);
+#define BJ_MFMA(TS, NT) case BJ_KEY(PA_BJ_BAND_MFMA, TS, TS, NT): \
+  return bj_go<&k_bj_mfma<TS, NT>>(L, "k_bj_mfma", BJ_BLOCKS(off, Lf, Lb), L.per_wave, in, out);
+#define BJ_MFMA3(TS) BJ_MFMA(TS, 4) BJ_MFMA(TS, 6) BJ_MFMA(TS, 8)
+// one workgroup per block, R register sets per lane: the instance of at most 768 threads and the one of 1024
+#define BJ_WIDE(TS, R) \
+  case BJ_KEY(PA_BJ_BAND_WIDE, TS, 3, R): return bj_go<&k_bj_wide<TS, R, 768>>(L, "k_bj_wide", BJ_BLOCKS(off, Lf, Lb), in, out); \
+  case BJ_KEY(PA_BJ_BAND_WIDE, TS, 4, R): return bj_go<&k_bj_wide<TS, R, 1024>>(L, "k_bj_wide", BJ_BLOCKS(off, Lf, Lb), in, out);
 
-// R = register sets per lane (1 / 2 / 4 for windows up to 1024 / 2048 / 4096 rows)
-template <int TS, int R>
-static int bj_launch_wide(const pa_bj_plan_t* pl, int wmax, const int* list, int count, const double* in,
-                          double* out) {
-  const int W = pa_bj_wide_window(wmax);
-  const int nw = (W + 64 * R - 1) / (64 * R);
-  if (nw > 16 || TS * R > 16) {
-    pa_rt_set_error("block-Jacobi: bandwidth %d is too wide for panel stride %d (window %d rows); use more subdomains",
-                    wmax, TS, W);
-    fprintf(stderr, "[prealps_hip] %s\n", pa_rt_error());
-    return 1;
+static int bj_launch(const pa_bj_band_launch_t& L, const pa_bj_plan_t* pl, const int* list, int count, const double* in, double* out) {
+  switch (BJ_KEY(L.family, L.ts, L.family == PA_BJ_BAND_WIDE ? L.cap >> 8 : L.xs, L.family == PA_BJ_BAND_MFMA ? L.tiles : L.r)) {
+    BJ_APPLY8(2, 2) BJ_APPLY8(4, 4) BJ_APPLY8(8, 8) BJ_APPLY8(16, 16) BJ_APPLY8(2, 4)
+    BJ_PAIRS(2, 2, 2) BJ_PAIRS(2, 2, 3) BJ_PAIRS(4, 4, 2) BJ_PAIRS(4, 4, 3) BJ_PAIRS(2, 4, 2) BJ_PAIRS(2, 4, 3)
+    BJ_MFMA3(2) BJ_MFMA3(4) BJ_MFMA3(8) BJ_MFMA3(16)
+    BJ_WIDE(2, 1) BJ_WIDE(2, 2) BJ_WIDE(2, 4) BJ_WIDE(4, 1) BJ_WIDE(4, 2) BJ_WIDE(4, 4) BJ_WIDE(8, 1) BJ_WIDE(8, 2) BJ_WIDE(16, 1)
   }
-  if constexpr (TS * R <= 16) {
-    if (nw <= 12)
-      PA_LAUNCH((k_bj_wide<TS, R, 768>), dim3(count), dim3(64 * nw), 0, cur_stream(), list, count,
-                         pl->row0, pl->nrows, pl->bw, pl->off, pl->map_f, pl->map_b, pl->Lf, pl->Lb,
-                         pl->invd_f, pl->invd_b, in, out);
-    else
-      PA_LAUNCH((k_bj_wide<TS, R, 1024>), dim3(count), dim3(64 * nw), 0, cur_stream(), list, count,
-                         pl->row0, pl->nrows, pl->bw, pl->off, pl->map_f, pl->map_b, pl->Lf, pl->Lb,
-                         pl->invd_f, pl->invd_b, in, out);
-  }
-  return kfail("k_bj_wide");
-}
-
-template <int R>
-static int bj_wide_dispatch(const pa_bj_plan_t* pl, int ts, int wmax, const int* list, int count,
-                            const double* in, double* out) {
-  switch (ts) {
-    case 2: return bj_launch_wide<2, R>(pl, wmax, list, count, in, out);
-    case 4: return bj_launch_wide<4, R>(pl, wmax, list, count, in, out);
-    case 8: return bj_launch_wide<8, R>(pl, wmax, list, count, in, out);
-    case 16: return bj_launch_wide<16, R>(pl, wmax, list, count, in, out);
-    default: return 1;
-  }
+  pa_rt_set_error("pa_k_bj_apply: no kernel of family %d with TS=%d XS=%d R=%d, %d tiles, %d threads", L.family, L.ts, L.xs, L.r, L.tiles, L.cap);
+  return 1;
 }
 
 template <int NB>
@@ -1113,10 +1010,6 @@ static int bj_factor_big_launch(const int* list, int count, int wmax, const int*
 }
 
 extern "C" {
-
-int pa_bj_max_R(void) { return 8; }
-
-int pa_bj_factor_wmax(void) { return 96; }
 
 int pa_k_bj_factor(const int* list, int count, int wmax, const int* row0, const int* nrows, const int* bw,
                    const long long* off, const long long* boff, const double* band, double* Lf, double* Lb,
@@ -1181,35 +1074,37 @@ int pa_k_bj_gram_take(const double* in, const double* out) {
   return n;
 }
 
+/* Every class of the plan in turn: the query, the plan (bj_band_plan.c; a refusal goes to pa_rt_error() with its
+ * reason), the launcher of the family. */
 int pa_k_bj_apply(const pa_bj_plan_t* pl, int ts, const double* in, double* out) {
+  /* PREALPS_BJ_G4_WIDE=0: 8-column panels stay with k_bj_mfma; PREALPS_BJ_MFMA=0: never k_bj_mfma, 2: at every width */
+  static int g4_wide = -1, use_mfma = -1;
+  if (g4_wide < 0) {
+    const char* e = getenv("PREALPS_BJ_G4_WIDE"); g4_wide = e ? atoi(e) : 1;
+    e = getenv("PREALPS_BJ_MFMA"); use_mfma = e ? atoi(e) : 1;
+  }
   for (int c = 0; c < pl->nclass; ++c) {
-    if (pl->class_count[c] <= 0) continue;
-    int rc = 1;
-    static int g4_wide = -1;      /* PREALPS_BJ_G4_WIDE=0: 8-column panels stay with k_bj_mfma */
-    if (g4_wide < 0) { const char* e = getenv("PREALPS_BJ_G4_WIDE"); g4_wide = e ? atoi(e) : 1; }
-    if (pl->Lg4 && pl->class_g4[c] && pa_bj_g4_takes_panel(pl->class_wmax[c], ts, g4_wide)) {   /* one copy of the factor, matrix cores (bj_g4.hip) */
-      if (ts == 4 && g_bg.armed && pl->nclass == 1 && in == g_bg.in && out == g_bg.out && pl->class_count[c] <= g_bg.cap) {
-        pa_k_bj_g4_gram(g_bg.prev, g_bg.partials);      // this apply also leaves [in | prev]^T out (pa_k_bj_gram_arm)
-        g_bg.count = pl->class_count[c];
-        ++g_bg_applies;
-      } else if (g_bg.armed && in == g_bg.in && out == g_bg.out) {
-        g_bg.count = 0;
-      }
-      rc = pa_k_bj_g4(pl, pl->class_list[c], pl->class_count[c], pl->class_wmax[c], pl->class_bmax[c], ts, ts, in, out,
-                      pl->class_ptask ? &pl->class_ptask[c] : nullptr);
-      if (rc) return rc;
+    const int* list = pl->class_list[c];
+    const int count = pl->class_count[c];
+    if (count <= 0) continue;
+    const pa_bj_band_query_t q = {ts, pl->class_R[c], pl->class_wmax[c], count, pl->Lg4 && pl->class_g4[c], pl->Lf2 != nullptr,
+                                  g4_wide, use_mfma, pa_rt_num_cus()};
+    pa_bj_band_launch_t L;
+    char why[160];
+    if (pa_bj_band_plan(&q, &L, why, (int)sizeof(why))) { pa_rt_set_error("pa_k_bj_apply: %s", why); return 1; }
+    if (L.family != PA_BJ_BAND_G4) {
+      if (bj_launch(L, pl, list, count, in, out)) return 1;
       continue;
     }
-    if (pl->class_R[c] < 0) {   /* wide bands: one workgroup per subdomain, -class_R register sets */
-      const int Rw = -pl->class_R[c];
-      if (Rw == 1) rc = bj_wide_dispatch<1>(pl, ts, pl->class_wmax[c], pl->class_list[c], pl->class_count[c], in, out);
-      else if (Rw == 2) rc = bj_wide_dispatch<2>(pl, ts, pl->class_wmax[c], pl->class_list[c], pl->class_count[c], in, out);
-      else rc = bj_wide_dispatch<4>(pl, ts, pl->class_wmax[c], pl->class_list[c], pl->class_count[c], in, out);
-      if (rc) return rc;
-      continue;
+    /* one copy of the factor, matrix cores (bj_g4.hip) */
+    if (ts == 4 && g_bg.armed && pl->nclass == 1 && in == g_bg.in && out == g_bg.out && count <= g_bg.cap) {
+      pa_k_bj_g4_gram(g_bg.prev, g_bg.partials);      // this apply also leaves [in | prev]^T out (pa_k_bj_gram_arm)
+      g_bg.count = count;
+      ++g_bg_applies;
+    } else if (g_bg.armed && in == g_bg.in && out == g_bg.out) {
+      g_bg.count = 0;
     }
-    TS_DISPATCH(ts, rc = bj_launch<TS_>(pl, pl->class_R[c], pl->class_wmax[c], pl->class_list[c],
-                                        pl->class_count[c], in, out));
+    const int rc = pa_k_bj_g4(pl, list, count, q.wmax, pl->class_bmax[c], ts, ts, in, out, pl->class_ptask ? &pl->class_ptask[c] : nullptr);
     if (rc) return rc;
   }
   return 0;

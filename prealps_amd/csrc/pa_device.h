@@ -9,6 +9,7 @@
 #define PA_DEVICE_H
 #include <stddef.h>
 #include "bj_g4_plan.h"    /* pa_bj_g4_max_rows / _max_band / _max_band8: the limits of the band block solve */
+#include "bj_band_plan.h"  /* pa_bj_max_R, pa_bj_factor_wmax: the limits of the other band kernels */
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -375,7 +376,6 @@ int pa_k_bj_g4(const pa_bj_plan_t* pl, const int* list, int count, int wmax, int
 /* One-shot: the next pa_k_bj_g4 on a 4-column panel also leaves the 8 x 4 block [in | prev]^T out of every
  * block in part (32 doubles per block, in the order of its list; the layout of pa_k_gram with two panels). */
 void pa_k_bj_g4_gram(const double* prev, double* part);
-int pa_bj_max_R(void);
 int pa_k_bj_pairs(const int* list, int count, const int* nrows, const int* bw, const long long* off,
                   const long long* off2, const double* L, double* L2);
 /* bj_g4.hip: the records of Lg4 from the plain forward records, and the block solve that reads them
@@ -389,12 +389,6 @@ int pa_k_bj_g4_setup_f32(const int* list, int count, const int* nrows, const int
 /* the last launch of pa_k_bj_g4: 0 = ring depth, 1 = storage bits of the records it read, 2 = 1 if it was the
  * pipelined few-blocks chain, 3 = 1 if it was the PAIR launch (two blocks of one class per wavefront) */
 int pa_bj_g4_last(int which);
-/* Band Cholesky on the device for blocks with bandwidth <= pa_bj_factor_wmax(): `band` holds
- * each listed block's rows in factor order, (w+1) doubles per row (A(i, i-d) at d), at offset
- * boff[part]; writes the forward / backward sweep records and 1/L(j,j) straight into Lf, Lb
- * (pre-zeroed), invd_f, invd_b.  *fail (device, pre-zeroed) = 1 + local position of the first
- * non-positive pivot seen. */
-int pa_bj_factor_wmax(void);
 /* dst[off[e]] = val[e], e < n */
 int pa_k_scatter(size_t n, const long long* off, const double* val, double* dst);
 /* Wider bands (up to 4032): `band` diagonal-major per block (A(i, i-d) at boff + d*nrows + i),
@@ -403,9 +397,15 @@ int pa_k_scatter(size_t n, const long long* off, const double* val, double* dst)
 int pa_k_bj_factor_big(const int* list, int count, int wmax, int wide_from, const int* row0, const int* nrows,
                        const int* bw, const long long* off, const long long* boff, double* band, double* Lf, double* Lb,
                        double* invd_f, double* invd_b, int* fail);
+/* Band Cholesky on the device for blocks with bandwidth <= pa_bj_factor_wmax(): `band` holds
+ * each listed block's rows in factor order, (w+1) doubles per row (A(i, i-d) at d), at offset
+ * boff[part]; writes the forward / backward sweep records and 1/L(j,j) straight into Lf, Lb
+ * (pre-zeroed), invd_f, invd_b.  *fail (device, pre-zeroed) = 1 + local position of the first
+ * non-positive pivot seen. */
 int pa_k_bj_factor(const int* list, int count, int wmax, const int* row0, const int* nrows, const int* bw,
                    const long long* off, const long long* boff, const double* band, double* Lf, double* Lb,
                    double* invd_f, double* invd_b, int* fail);
+/* the block solve out = M^-1 in on panels of row stride ts: every class through the family bj_band_plan.c picks for it */
 int pa_k_bj_apply(const pa_bj_plan_t* pl, int ts, const double* in, double* out);
 /* bj_refactor.hip: band[boff[chunk_blk[c]] + dst[e]] = pv[src[e]] for the entries e of every chunk c of the band
  * map (bj_band_map.h); band zeroed beforehand, everything on the device. */

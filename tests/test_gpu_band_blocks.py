@@ -163,7 +163,8 @@ def _reference(name, grading, shuffle, t):
     return X, Zo, _omega(c, X, Zo)
 
 
-# ---- which kernel a class of blocks is given to (pa_k_bj_apply, bj_build_classes, bj_second_layouts) ---------------
+# ---- which kernel a class of blocks is given to (pa_bj_band_plan of bj_band_plan.c, pa_bj_layout_build; the labels of
+# _family are checked against the planner in test_bj_band_plan_cpu.py) ------------------------------------------------
 def _stride(t):
     ts = 2
     while ts < t:
