@@ -448,6 +448,40 @@ int preAlps_ECGSolveSystemRefined(preAlps_ECG_t* ecg, int nrhs, const double* b,
                                   double* res_hist, int* bs_hist, double* sys_hist, double* sys_normb,
                                   double* sys_res, int max_hist, int* n_hist, int max_passes, int* n_passes,
                                   int* pass_iters, double* pass_res, int* status);
+/* preAlps_ECGSolveSystem with the energy-norm error estimate per system, and optionally a stopping test on it.
+ *   With A-orthonormal directions an iteration is X += P alpha, and it takes exactly delta_j(i) = ||alpha_i 1_{G_j}||^2
+ * off ||x*_j - x_j||_A^2 (G_j: the columns of system j).  The norm is the same in the caller's system and in the
+ * scaled, permuted one, so no row map and no pass over a panel is needed: one small launch per iteration reads the
+ * alpha that the update of X uses, and the host reads its k words with the residual norm.  Several processes: alpha is
+ * global behind the Gram all-reduce, so every rank forms the same words and the iteration gains no collective.
+ *   The estimate of the error after iteration l, made at iteration n > l, is est_j(l)^2 = sum_{i=l}^{n-1} delta_j(i): a
+ * lower bound (Hestenes-Stiefel, with a delay).  Window rule (tau in (0, 0.5), dmin >= 2; 0.1 and 4 are the usual
+ * values): l_j(n) = the largest l <= n - dmin whose second half holds at most tau of the window's sum.  Under
+ * geometric decay est^2 / true^2 >= 1 - (tau / (1 - tau))^2; the estimate is a heuristic, not a guarantee
+ * (prealps_amd/csrc/ecg_energy.h states the rule and its limits).
+ *   flags: those of preAlps_ECGSolveSystem, and
+ * PREALPS_SYS_ENERGY: form the drops and return the estimates; the stopping test is the one the other flags select, and
+ *   x, every history and the iteration count are those of preAlps_ECGSolveSystem, bit for bit;
+ * PREALPS_SYS_STOP_ENERGY (implies PREALPS_SYS_ENERGY): the iteration goes on while for some system no window
+ *   qualifies or est_j(l_j(n))^2 > tol^2 * sum_{i<n} delta_j(i), the latter a lower bound of ||x*_j - x0_j||_A^2: the test
+ *   is relative to the initial error, with or without a guess.  ecg->maxIter, bs > 0 and a NaN stop as ever.
+ * Without either bit the entry IS preAlps_ECGSolveSystem (tau and dmin are not looked at, the new outputs not written).
+ *   Outputs, any of which may be NULL (leading dimension max_hist, system j): drop_hist[i + j*max_hist] = delta_j(i);
+ * err_hist[i + j*max_hist] = the best estimate of ||x*_j - x_j||_A after i iterations that was available when the solve
+ * ended, -1 where no window qualified; sys_err[j] = the estimate at the last window that qualified, sharpened by the
+ * drops since, and sys_err_iter[j] the iteration it belongs to (-1, and sys_err[j] = -1: none qualified);
+ * sys_energy[j] = sqrt(sum_i delta_j(i)).  A guess that already meets the residual threshold comes back after no
+ * iteration, as from preAlps_ECGSolveSystem, and the estimates say "none".
+ *   ORTHODIR and ORTHOMIN with NO_BS_RED, one system or several, one process or several.  Refused, naming this entry:
+ * ADAPT_BS or ORTHODIR_FUSED with an energy flag, PREALPS_SYS_STOP_ENERGY together with PREALPS_SYS_STOP_ORIGINAL, tau
+ * or dmin out of range, nrhs > 16, and everything preAlps_ECGSolveSystem refuses.  Statistic "ecg_energy_launches". */
+#define PREALPS_SYS_ENERGY      4   /* form the drops, return the estimates */
+#define PREALPS_SYS_STOP_ENERGY 8   /* implies 4; refused with PREALPS_SYS_STOP_ORIGINAL */
+int preAlps_ECGSolveSystemEnergy(preAlps_ECG_t* ecg, int nrhs, const double* b, int ldb,
+                                 const double* x0, int ldx0, double* x, int ldx, int flags, double tau, int dmin,
+                                 double* res_hist, int* bs_hist, double* sys_hist, double* sys_normb, double* sys_res,
+                                 double* drop_hist, double* err_hist, double* sys_err, int* sys_err_iter,
+                                 double* sys_energy, int max_hist, int* n_hist);
 /* 1 / 0: the two driver loops above and below replay each half of an iteration from a HIP graph
  * captured on its first passes (default: off, or PREALPS_ECG_GRAPH; plain launches measured faster). */
 void preAlps_hip_graphs(int on);
@@ -538,7 +572,8 @@ int preAlps_hip_panel_permute_solve(const CPLM_Mat_Dense_t* Z, CPLM_Mat_Dense_t*
  * records that are read at all; "bj_share_s": seconds of the create's class pass), "ecg_graph_captures" / "ecg_graph_replays" (iteration segments captured and graphs
  * launched by the driver loops so far, preAlps_hip_graphs), "ecg_x_skips" / "ecg_x_flushes" (row passes of the
  * library's loops that left X alone so far, and owed updates of X that a stop paid with a launch of its own,
- * PREALPS_ECG_X_DEFER), "spmm_precision" (64 / 32: storage of the values the plan in use streams, 0: no plan
+ * PREALPS_ECG_X_DEFER), "ecg_energy_launches" (launches of the energy-norm drops the iteration has queued so far:
+ * one per iteration of a solve with PREALPS_SYS_ENERGY / PREALPS_SYS_STOP_ENERGY, none otherwise), "spmm_precision" (64 / 32: storage of the values the plan in use streams, 0: no plan
  * yet), ...  Returns non-zero for unknown keys. */
 int preAlps_hip_get_stat(const char* key, double* value);
 /* A stopwatch made of two hipEvents on the library stream: start records the

@@ -165,6 +165,7 @@ void pa_ecg_request_gram_from_spmm(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
 int pa_ecg_reset_state(preAlps_ECG_t* ecg, ecg_priv_t* pv, int nrhs, int guess, int metric) {
   pv->nrhs = nrhs; pv->sgrp = ecg->enlFac / nrhs; pv->guess = guess; pv->metric = metric; pv->d_dl = NULL;
   pv->grp_dst = NULL;
+  pv->energy = NULL; pv->energy_stop = 0;
   ecg->tot_t = ecg->comm_t = ecg->trsm_t = ecg->gemm_t = ecg->potrf_t = ecg->pstrf_t = 0.0;
   ecg->lapmt_t = ecg->gesvd_t = ecg->geqrf_t = ecg->ormqr_t = ecg->copy_t = 0.0;
   int M = ecg->globPbSize, m = ecg->locPbSize, t = ecg->enlFac, ts = pv->ts;
@@ -408,6 +409,19 @@ int pa_ecg_stopping_end(preAlps_ECG_t* ecg, ecg_priv_t* pv, int* stop) {
   int info = (int)pv->h_pin[1];
   if (info != 0 && ecg->ortho_alg == ORTHOMIN) return PA_FAIL("ACHQR: dpotrf:\n ERROR: P^tAP is not spd!");
   ecg->res = sqrt(res2);
+  /* the energy-norm drops of this iteration lie in the pinned words behind the same event; e_on: the verdict of the
+   * tracker's rule where that is the test (1: on, 0: stop -- a drop that is not finite stops), -1 where it is not */
+  int e_on = -1;
+  if (pv->energy) {
+    double drops[PA_ENERGY_MAX_SYSTEMS];
+    const volatile double* h = pv->h_drop;
+    for (int j = 0; j < (pv->nrhs > 1 ? pv->nrhs : 1); ++j) drops[j] = h[j];
+    const int prc = pa_energy_push(pv->energy, drops);
+    if (prc != PA_ENERGY_OK && prc != PA_ENERGY_NAN)
+      return PA_FAIL("the energy-norm tracker took no drops at iteration %d (%s)", ecg->iter,
+                     prc == PA_ENERGY_FULL ? "it is full" : "bad arguments");
+    if (pv->energy_stop) e_on = pa_energy_goes_on(pv->energy, ecg->tol);
+  }
   if (pv->nrhs > 1 || pv->metric) {
     /* every system against its own right-hand side: on while one of them is above its threshold; a NaN stops
      * (the caller's metric: for one system too, both sides in the caller's units) */
@@ -419,11 +433,12 @@ int pa_ecg_stopping_end(preAlps_ECG_t* ecg, ecg_priv_t* pv, int* stop) {
       if (g > pv->sys_normb[j] * ecg->tol) above = 1;
       if (!(g == g)) nan = 1;
     }
+    if (e_on >= 0) above = e_on;
     *stop = (above && !nan && ecg->iter < ecg->maxIter && ecg->bs > 0) ? 0 : 1;
     return 0;
   }
   /* !(a > b) also stops on NaN, like the reference's comparison */
-  if (ecg->res > ecg->normb * ecg->tol && ecg->iter < ecg->maxIter && ecg->bs > 0) *stop = 0;
+  if ((e_on >= 0 ? e_on && ecg->res == ecg->res : ecg->res > ecg->normb * ecg->tol) && ecg->iter < ecg->maxIter && ecg->bs > 0) *stop = 0;
   else *stop = 1;
   return 0;
 }
@@ -535,6 +550,7 @@ static int fused_update(preAlps_ECG_t* ecg, ecg_priv_t* pv, int t, const double*
                             gram, pv->lazy_norm ? pv->d_uu + (size_t)pv->uu_cur * T * T : NULL));
   pv->rtr_nblk = nb;
   if (pa_ecg_queue_group_norms(ecg, pv, defer ? pv->lazy_ptr : pv->d_res2)) return 1;
+  if (pa_ecg_queue_energy(ecg, pv)) return 1;
   TAC(PA_T_UPDATE, trsm_t);
   pv->rtr_valid = defer ? RTR_COLUMN_SUMS : RTR_SUMMED;
   return 0;
@@ -550,6 +566,7 @@ static int update_iterate(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
                           ecg->AP->val, pv->d_X, pv->d_R, pv->d_rtr_part, &pv->rtr_nblk, ecg->enlFac,
                           pv->d_res2, pv->d_info, pa_world_size() == 1 ? pv->h_pin : NULL));
   if (pa_ecg_queue_group_norms(ecg, pv, pv->d_res2)) return 1;
+  if (pa_ecg_queue_energy(ecg, pv)) return 1;
   TAC(PA_T_UPDATE, gemm_t);
   pv->rtr_valid = RTR_SUMMED;
   pv->lazy_ptr = NULL;
@@ -568,6 +585,29 @@ int pa_ecg_flush_x(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
   PA_CHECK(pa_k_flush_x(pv->m, pv->ts, T, pv->d_uu + prev, pv->d_akeep + prev, pv->buf_v[1], pv->d_X));
   pv->x_pending = 0;
   ++g_x_flushes;
+  return 0;
+}
+
+/* The energy-norm drops (ecg_priv.h: energy).  Enabled between the start and the first iteration of a system solve. */
+static long long g_energy_launches;
+long long pa_ecg_energy_count(void) { return g_energy_launches; }
+int pa_ecg_energy_enable(preAlps_ECG_t* ecg, ecg_priv_t* pv, pa_energy_t* tracker, int stop) {
+  if (!tracker) return 0;
+  if (ecg->bs_red != NO_BS_RED || ecg->ortho_alg == ORTHODIR_FUSED)
+    return PA_FAIL("the energy-norm drops need every direction live: ORTHODIR or ORTHOMIN with NO_BS_RED");
+  if (!pv->d_drop) pv->d_drop = (double*)pa_rt_malloc(PA_ENERGY_MAX_SYSTEMS * sizeof(double));
+  if (!pv->h_drop) pv->h_drop = (double*)pa_rt_host_alloc_coherent(PA_ENERGY_MAX_SYSTEMS * sizeof(double));
+  if (!pv->d_drop || !pv->h_drop) return PA_FAIL("no room for the energy-norm drops: %s", pa_rt_error());
+  pv->energy = tracker; pv->energy_stop = stop;
+  pv->poll = 0; pv->use_graphs = 0;
+  return 0;
+}
+int pa_ecg_queue_energy(preAlps_ECG_t* ecg, ecg_priv_t* pv) {
+  if (!pv->energy) return 0;
+  const int k = pv->nrhs > 1 ? pv->nrhs : 1;
+  PA_CHECK(pa_k_energy_drops(pv->d_alpha, ecg->alpha->info.m, ecg->alpha->info.lda, ecg->alpha->info.n, k, pv->sgrp,
+                             pv->d_drop, pv->h_drop));
+  ++g_energy_launches;
   return 0;
 }
 
@@ -959,6 +999,8 @@ void _preAlps_ECGFree(preAlps_ECG_t* ecg) {
     pa_rt_sync();
     pa_rt_free(pv->d_info);
     pa_rt_free(pv->d_akeep);
+    pa_rt_free(pv->d_drop);
+    pa_rt_host_free(pv->h_drop);
     pa_rt_host_free(pv->h_pin);
     pa_rt_host_free(pv->h_pin_i);
     pa_rt_host_free(pv->h_grp);

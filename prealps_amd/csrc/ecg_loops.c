@@ -134,6 +134,8 @@ static int solve_first_step(preAlps_ECG_t* ecg, ecg_priv_t* pv, int ahead, int* 
   else pv->x_pending = 0;
   pv->rtr_nblk = nb;
   if (pa_ecg_queue_group_norms(ecg, pv, NULL)) return 1;      /* (never riding: solve_first_applies) */
+  /* (d_alpha is still this iteration's: the finish of the next one is queued further down, behind the product) */
+  if (pa_ecg_queue_energy(ecg, pv)) return 1;
   pv->uu_cur ^= 1;
   ecg->iter++;
   /* the norm of the new residual (and the Cholesky status) straight to the pinned words the host reads */
@@ -190,6 +192,7 @@ static int ecg_solve_loop(preAlps_ECG_t* ecg, double* rhs, double* sol, double* 
       if (n_hist) *n_hist = 0;
       return pa_ecg_finish_system(ecg, mu, 1);
     }
+    if (pa_ecg_energy_enable(ecg, priv_of(ecg), mu->energy, mu->energy_stop)) { _preAlps_ECGFree(ecg); return 1; }
   } else if (mu->nrhs > 0 && mu->x0) {
     int live = 0;
     if (preAlps_ECGInitializeGuess(ecg, mu->nrhs, rhs, mu->ldrhs, mu->x0, mu->ldx0, &rci)) return 1;
@@ -338,6 +341,46 @@ int preAlps_ECGSolveSystem(preAlps_ECG_t* ecg, int nrhs, const double* b, int ld
   const multi_args_t mu = {.nrhs = nrhs, .sys_hist = sys_hist, .sys_normb = sys_normb, .sys = &in, .sys_x = x, .sys_ldx = ldx,
                            .sys_res = sys_res};
   return solve_in_own_loop(ecg, NULL, NULL, res_hist, bs_hist, max_hist, n_hist, &mu);
+}
+
+/* preAlps_ECGSolveSystem with a tracker of the energy-norm drops (ecg_energy.h) that this entry owns: the loop hands it to
+ * the solver behind the start (pa_ecg_energy_enable), the stopping test pushes into it, and it outlives the solver,
+ * which the finish releases, so the estimates are read here. */
+int preAlps_ECGSolveSystemEnergy(preAlps_ECG_t* ecg, int nrhs, const double* b, int ldb, const double* x0, int ldx0,
+                                 double* x, int ldx, int flags, double tau, int dmin, double* res_hist, int* bs_hist,
+                                 double* sys_hist, double* sys_normb, double* sys_res, double* drop_hist, double* err_hist,
+                                 double* sys_err, int* sys_err_iter, double* sys_energy, int max_hist, int* n_hist) {
+  const int e_flags = PREALPS_SYS_ENERGY | PREALPS_SYS_STOP_ENERGY;
+  if (!(flags & e_flags))
+    return preAlps_ECGSolveSystem(ecg, nrhs, b, ldb, x0, ldx0, x, ldx, flags, res_hist, bs_hist, sys_hist, sys_normb,
+                                  sys_res, max_hist, n_hist);
+  if (system_args_refused(__func__, ecg, nrhs, b, ldb, x0, ldx0, x, ldx, flags & ~e_flags)) return 1;
+  const int stop = (flags & PREALPS_SYS_STOP_ENERGY) != 0;
+  if (stop && (flags & PREALPS_SYS_STOP_ORIGINAL))
+    return pa_fail_at(__func__, "flags = %d: PREALPS_SYS_STOP_ENERGY and PREALPS_SYS_STOP_ORIGINAL are two stopping tests", flags);
+  if (ecg->bs_red != NO_BS_RED || ecg->ortho_alg == ORTHODIR_FUSED)
+    return pa_fail_at(__func__, "the energy-norm drops need every direction live: ORTHODIR or ORTHOMIN with NO_BS_RED, "
+                                "not %s", ecg->ortho_alg == ORTHODIR_FUSED ? "ORTHODIR_FUSED" : "ADAPT_BS");
+  if (!pa_energy_args_ok(tau, dmin))
+    return pa_fail_at(__func__, "tau = %g, dmin = %d: tau in (0, 0.5) and dmin >= 2 are needed", tau, dmin);
+  if (nrhs > PA_ENERGY_MAX_SYSTEMS) return pa_fail_at(__func__, "nrhs = %d: at most %d systems at a time", nrhs, PA_ENERGY_MAX_SYSTEMS);
+  if (ecg->maxIter < 0) return pa_fail_at(__func__, "maxIter = %d", ecg->maxIter);
+  pa_energy_t tr;
+  /* (the loop tests after every iteration, the first included, so maxIter + 1 pushes at the most) */
+  const int irc = pa_energy_init(&tr, nrhs, ecg->maxIter + 2, tau, dmin);
+  if (irc) return pa_fail_at(__func__, irc == PA_ENERGY_NO_MEMORY ? "out of host memory for %d x %d drops" : "a tracker of %d x %d drops was refused", ecg->maxIter + 2, nrhs);
+  const int base = flags & ~e_flags;
+  const sys_in_t in = {b, ldb, x0, ldx0, (base & PREALPS_SYS_DEVICE) != 0, (base & PREALPS_SYS_STOP_ORIGINAL) != 0, 0, ldx};
+  const multi_args_t mu = {.nrhs = nrhs, .sys_hist = sys_hist, .sys_normb = sys_normb, .sys = &in, .sys_x = x, .sys_ldx = ldx,
+                           .sys_res = sys_res, .energy = &tr, .energy_stop = stop};
+  const int rc = solve_in_own_loop(ecg, NULL, NULL, res_hist, bs_hist, max_hist, n_hist, &mu);
+  ecg_priv_t* pv = priv_of(ecg);      /* (a failed solve may have left the solver standing: it must not keep the tracker) */
+  if (pv) { pv->energy = NULL; pv->energy_stop = 0; }
+  for (int j = 0; j < nrhs && !rc; ++j)
+    pa_energy_report(&tr, j, drop_hist ? drop_hist + (size_t)j * max_hist : NULL, err_hist ? err_hist + (size_t)j * max_hist : NULL,
+                     max_hist, sys_err ? sys_err + j : NULL, sys_err_iter ? sys_err_iter + j : NULL, sys_energy ? sys_energy + j : NULL);
+  pa_energy_release(&tr);
+  return rc;
 }
 
 /* ---- the refined system solve -----------------------------------------------------------------------------------

@@ -10,6 +10,7 @@
 
 #include "pa_host.h"
 #include "ecg_plan.h"
+#include "ecg_energy.h"
 
 #define PA_ECG_MAGIC 0x45434731u
 
@@ -126,6 +127,17 @@ typedef struct {
    * where ride puts the sums of several systems: [norm^2, status | g_0^2 .. g_nrhs-1^2], nrhs >= 1 words behind the
    * pair, in the same collective.  Every site that reads `ride` reads pa_ecg_rides instead. */
   int ride_sys;
+  /* The energy-norm drops (preAlps_ECGSolveSystemEnergy; ecg_energy.h).  energy != NULL: every launch that updates X
+   * and R (fused_update, update_iterate, the row pass of solve_first_step) is followed by pa_k_energy_drops on d_alpha,
+   * which at that point holds the coefficients of this iteration's A-orthonormal directions and is next written by the
+   * next iteration's finish; the k drops go to d_drop and to the pinned words h_drop (both allocated by
+   * pa_ecg_energy_enable, not in the pool), ahead of whatever carries the norm to the host, and the stopping test
+   * pushes them into the tracker, which belongs to the entry.  energy_stop: the test stops on the tracker's rule
+   * instead of the residual norms.  Polling and graphs are off, as for several systems: the drops may be queued behind
+   * the launch that writes the polled word.  pa_ecg_reset_state ends the request. */
+  pa_energy_t* energy;
+  int energy_stop;
+  double* d_drop; double* h_drop;
 } ecg_priv_t;
 static inline int pa_ecg_rides(const ecg_priv_t* pv) { return pv->ride || pv->ride_sys; }
 
@@ -160,6 +172,9 @@ typedef struct {      /* what preAlps_ECGSolveMulti adds to the arguments of pre
    * sys_hist_ld: the leading dimension of sys_hist where it is not max_hist (0: it is). */
   int (*gate)(void* ctx, int nrhs, const double* g0, const double* nb); void* gate_ctx;
   int sys_hist_ld;
+  /* ... and preAlps_ECGSolveSystemEnergy: the tracker the drops of every iteration are pushed into (NULL: none are
+   * formed), and whether its rule is the stopping test */
+  pa_energy_t* energy; int energy_stop;
 } multi_args_t;
 
 /* ---- ecg.c ---- */
@@ -176,6 +191,8 @@ int pa_ecg_stopping_end(preAlps_ECG_t* ecg, ecg_priv_t* pv, int* stop);
 int pa_ecg_shift_directions(preAlps_ECG_t* ecg, ecg_priv_t* pv, int ncopy);
 void pa_ecg_x_owed(ecg_priv_t* pv);                        /* a row pass skipped X: sets x_pending, counts */
 int pa_ecg_flush_x(preAlps_ECG_t* ecg, ecg_priv_t* pv);    /* pays what is owed to X, if anything (pa_k_flush_x) */
+int pa_ecg_energy_enable(preAlps_ECG_t* ecg, ecg_priv_t* pv, pa_energy_t* tracker, int stop);
+int pa_ecg_queue_energy(preAlps_ECG_t* ecg, ecg_priv_t* pv);   /* the drops of the update just queued; nothing without a tracker */
 /* ---- ecg_start.c ---- */
 int pa_ecg_start_systems(const char* who, preAlps_ECG_t* ecg, int nrhs, const double* rhs, int ldrhs,
                          const double* x0, int ldx0, int* rci_request, const sys_in_t* sys);

@@ -1210,6 +1210,7 @@ int preAlps_hip_get_stat(const char* key, double* value) {
   else if (!strcmp(key, "ecg_graph_replays")) *value = (double)pa_ecg_graph_count(1);
   else if (!strcmp(key, "ecg_x_skips")) *value = (double)pa_ecg_x_count(0);
   else if (!strcmp(key, "ecg_x_flushes")) *value = (double)pa_ecg_x_count(1);
+  else if (!strcmp(key, "ecg_energy_launches")) *value = (double)pa_ecg_energy_count();
   else if (!strcmp(key, "packs_fused")) *value = (double)g_packs_fused;
   else if (!strcmp(key, "allreduces")) *value = (double)pa_allreduce_count();
   else if (!strcmp(key, "spmm_slices")) *value = o->plan.nslices;

@@ -312,6 +312,13 @@ int pa_k_sys_copy_rows(int m, int k, const int* src, const double* Xin, int ldin
  * buf: 2 + k doubles on the device, nothing else is written.  Refuses k * s > ts and a NULL buf. */
 int pa_k_sys_norms_ride(const double* rtr_part, int rtr_nblk, const double* sys_part, int sys_nblk, int ts, int k, int s,
                         const int* info, double* buf);
+/* ---- the energy-norm drops of an iteration (dense_energy.hip; preAlps_ECGSolveSystemEnergy) ----
+ * alpha: rows x T on the device, column major with leading dimension ld, the coefficients of A-orthonormal directions
+ * that the update of X uses; system j of k owns its columns j*s .. j*s + s - 1.  out[j] = sum_r (sum_{c in G_j}
+ * alpha(r, c))^2, the inner sums in ascending c, the outer in ascending r (one fma each); host (pinned,
+ * device-visible, may be NULL) receives the same k values.  One workgroup, no atomics: two launches agree in bits.
+ * Refuses a NULL alpha or out, rows or T outside 1 .. 16, ld < rows, k < 1, s < 1 and k * s > T. */
+int pa_k_energy_drops(const double* alpha, int rows, int ld, int T, int k, int s, double* out, double* host);
 
 /* ---- block-Jacobi apply (block_jacobi.c:93-109, K8) --------------------- */
 /* the pair tasks of one class: device array of (i0, i1), positions into the class's list (i1 = -1: no partner) */

@@ -135,6 +135,7 @@ int pa_bj_nd_blocks(void);
 int pa_bj_nd_precision(void);       /* storage of the sparse factors (64 / 32), 0 if no block has one */
 long long pa_ecg_graph_count(int which);   /* 0: iteration segments captured so far, 1: graphs launched (ecg_loops.c) */
 long long pa_ecg_x_count(int which);       /* 0: row passes that left X alone so far, 1: owed updates paid by pa_k_flush_x (ecg.c) */
+long long pa_ecg_energy_count(void);      /* launches of pa_k_energy_drops the iteration has queued so far (ecg.c) */
 int pa_bj_apply_epoch(void);       /* + 1 per change of what preAlps_BlockJacobiApply launches or reads (create, free, coarse space) */
 int pa_bj_gram_blocks(void);       /* blocks of an apply that can leave [in | prev]^T out behind (0: cannot) */
 double pa_bj_g4_bytes(void);        /* bytes of the one-copy records of bj_g4.hip as stored (fp64 / fp32), 0 if absent */

@@ -10,6 +10,7 @@ ORTHOMIN, ORTHODIR, ORTHODIR_FUSED = 0, 1, 2
 ADAPT_BS, NO_BS_RED = 0, 1
 ROW_MAJOR, COL_MAJOR = 0, 1
 SYS_DEVICE, SYS_STOP_ORIGINAL = 1, 2      # flags of preAlps_ECGSolveSystem
+SYS_ENERGY, SYS_STOP_ENERGY = 4, 8        # ... and of preAlps_ECGSolveSystemEnergy
 # *status of preAlps_ECGSolveSystemRefined
 REFINE_STATUS = {0: "converged", 1: "out of passes", 2: "out of iterations", 3: "stagnated"}
 
@@ -89,7 +90,7 @@ EXPORTS = [
     "preAlps_OperatorGetScalingPtr", "preAlps_OperatorGetOwnedRows", "preAlps_ECGSolveSystem", "preAlps_OperatorSystemResiduals",
     "preAlps_BlockJacobiSetCoarseSpace", "preAlps_BlockJacobiClearCoarseSpace",
     "preAlps_BlockJacobiGetCoarseAggregates",
-    "preAlps_hip_set_operator_precision", "preAlps_ECGSolveSystemRefined",
+    "preAlps_hip_set_operator_precision", "preAlps_ECGSolveSystemRefined", "preAlps_ECGSolveSystemEnergy",
 ]
 
 _lib = None
@@ -136,6 +137,9 @@ def load():
                                          C.c_int, pd, pi, pd, pd, pd, C.c_int, pi]
     L.preAlps_ECGSolveSystemRefined.argtypes = [pe, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                                 C.c_int, pd, pi, pd, pd, pd, C.c_int, pi, C.c_int, pi, pi, pd, pi]
+    L.preAlps_ECGSolveSystemEnergy.argtypes = [pe, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                               C.c_int, C.c_double, C.c_int, pd, pi, pd, pd, pd, pd, pd, pd, pi, pd,
+                                               C.c_int, pi]
     L.preAlps_OperatorSystemResiduals.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, pd, pd]
     L.preAlps_OperatorGetScalingPtr.argtypes = [C.POINTER(pd), pi]
     L.preAlps_OperatorGetOwnedRows.argtypes = [C.POINTER(pi), pi]

@@ -49,6 +49,16 @@ class EcgResult:
     pass_iters: np.ndarray = None
     pass_res: np.ndarray = None
     refine_status: str = None
+    # solve_system(stop="energy") / solve_system(energy=True) only: delta_j(i), the squared energy-norm drop of every
+    # iteration (iterations x systems); err_hist[i, j], the best estimate of ||x*_j - x_j||_A after i iterations that was
+    # available at the end (iterations + 1 rows, -1 where no window qualified); err_est[j] / err_iter[j], the estimate
+    # at the last window that qualified and the iteration it belongs to (-1: none); energy_norm[j] = sqrt(sum_i delta_j(i)),
+    # a lower bound of ||x*_j - x0_j||_A
+    drop_hist: np.ndarray = None
+    err_hist: np.ndarray = None
+    err_est: np.ndarray = None
+    err_iter: np.ndarray = None
+    energy_norm: np.ndarray = None
 
 
 class DistributedHooks:
@@ -503,7 +513,7 @@ class EcgProblem:
             torch.cuda.current_stream().synchronize()
 
     def solve_system(self, b, t, x0=None, stop="original", ortho_alg=ORTHODIR, bs_red=NO_BS_RED, tol=1e-5,
-                     max_iter=1000, refine=False, max_passes=4):
+                     max_iter=1000, refine=False, max_passes=4, energy=False, tau=0.1, dmin=4):
         """preAlps_ECGSolveSystem: A x = b as the caller stated it -- the rows in the order of the matrix this problem
         was built from, the values in its units -- for one system (b of shape (N,)) or k systems (b of shape (N, k), t a
         multiple of k), with or without a starting value x0 of the same shape.
@@ -525,9 +535,19 @@ class EcgProblem:
         the x before it with a start residual formed on the fp64 matrix, until that residual meets tol (what makes
         set_operator_precision("single") safe); max_iter bounds all passes together, iters is their sum, the histories
         are concatenated, and passes / pass_iters / pass_res / refine_status say what happened.  refine=False is
-        preAlps_ECGSolveSystem, and max_passes is not looked at."""
-        if stop not in ("original", "scaled"):
-            raise ValueError("stop must be 'original' or 'scaled', not %r" % (stop,))
+        preAlps_ECGSolveSystem, and max_passes is not looked at.
+        stop="energy" (preAlps_ECGSolveSystemEnergy): iterate until, for every system, the estimate of the energy-norm
+        error ||x*_j - x_j||_A -- a delayed lower bound summed from the drops ||alpha 1_{G_j}||^2 of the iterations, window
+        rule tau / dmin -- is at most tol times the same bound of the initial error ||x*_j - x0_j||_A.  The estimate is a
+        heuristic, not a guarantee.  energy=True forms the drops and the estimates under any stop, at one small launch
+        per iteration and without changing a bit of x or of the histories.  Either way the result gains drop_hist,
+        err_hist, err_est, err_iter and energy_norm; sys_res / sys_hist are then in the scaled metric under stop="energy".
+        Not with refine=True."""
+        if stop not in ("original", "scaled", "energy"):
+            raise ValueError("stop must be 'original', 'scaled' or 'energy', not %r" % (stop,))
+        energy = bool(energy) or stop == "energy"
+        if energy and refine:
+            raise ValueError("solve_system: the energy-norm estimate is not formed across the passes of refine=True")
         kind, k, vector = self._system_args("solve_system", b, x0, "x0")
         if int(t) < 1 or int(t) % k != 0:
             raise ValueError("the enlarging factor t = %d is not a multiple of the %d right-hand sides" % (t, k))
@@ -576,6 +596,20 @@ class EcgProblem:
                   "preAlps_ECGSolveSystemRefined")
             extra = dict(passes=npass.value, pass_iters=pass_iters[:npass.value].copy(),
                          pass_res=pass_res[:npass.value + 1].copy(), refine_status=_l.REFINE_STATUS[status.value])
+        elif energy:
+            drops = np.zeros((cap, k), order="F")
+            errs = np.zeros((cap, k), order="F")
+            err_est, err_iter, e_norm = np.zeros(k), np.zeros(k, dtype=np.int32), np.zeros(k)
+            flags |= _l.SYS_STOP_ENERGY if stop == "energy" else _l.SYS_ENERGY
+            check(L.preAlps_ECGSolveSystemEnergy(C.byref(e), k, pb, ldb, px0, ldx0, px, ldx, flags, float(tau), int(dmin),
+                                                 _pd(res), _pi(bs), _pd(sys_hist), _pd(sys_normb), _pd(sys_end),
+                                                 _pd(drops), _pd(errs), _pd(err_est), _pi(err_iter), _pd(e_norm), cap,
+                                                 C.byref(nh)),
+                  "preAlps_ECGSolveSystemEnergy")
+            n_ = nh.value
+            extra = dict(drop_hist=np.ascontiguousarray(drops[:n_]),
+                         err_hist=np.ascontiguousarray(errs[:n_ + 1]),
+                         err_est=err_est, err_iter=err_iter, energy_norm=e_norm)
         else:
             check(L.preAlps_ECGSolveSystem(C.byref(e), k, pb, ldb, px0, ldx0, px, ldx, flags, _pd(res), _pi(bs),
                                            _pd(sys_hist), _pd(sys_normb), _pd(sys_end), cap, C.byref(nh)),
