@@ -482,6 +482,50 @@ int preAlps_ECGSolveSystemEnergy(preAlps_ECG_t* ecg, int nrhs, const double* b, 
                                  double* res_hist, int* bs_hist, double* sys_hist, double* sys_normb, double* sys_res,
                                  double* drop_hist, double* err_hist, double* sys_err, int* sys_err_iter,
                                  double* sys_energy, int max_hist, int* n_hist);
+/* ---- solution history: start a solve from the best mix of earlier solutions ---------------------------------------
+ * For a sequence of systems on one operator (a time loop, a Newton loop, a sweep).  The history belongs to the built
+ * operator and is process-global like it: Xh, up to capacity <= 16 columns of N doubles on the device, in the caller's
+ * order and units (exactly what preAlps_ECGSolveSystem returns; a scaling vector that preAlps_OperatorUpdateValues
+ * changes therefore needs no rescaling), kept as a ring -- a full ring evicts its oldest column -- and G = Xh^T A Xh
+ * (fp64, on the host, exactly symmetric, with the "op_values_epoch" it was formed at).  x^T A y is the same number in
+ * the caller's system and in the scaled, permuted one.
+ *   preAlps_SolutionHistoryProject (Fischer's projection): g = Xh^T B; G scaled to unit diagonal; a diagonally pivoted
+ * Cholesky that stops when the largest remaining pivot is <= rtol (rtol <= 0: 1e-12); a dropped column gets the
+ * coefficient 0 and *rank is the number kept; x0 = Xh c (N x nrhs, ldx0 >= N) is the element of span(Xh) closest to the
+ * solution of A x = b in the energy norm, and captured[j] (may be NULL) = c_j^T g_j = ||x0_j||_A^2.  An empty history
+ * gives rank 0 and x0 = 0.  Two projections of the same input agree in bits: the dots are folded in a fixed order, no
+ * atomics are used.  (prealps_amd/csrc/ecg_history.h states the rule and its limits.)
+ *   preAlps_SolutionHistoryAppend: w = A x by the library's own fp64 product -- the gather of (D^-1 x)[perm], a plain
+ * product at s = 1 on the fp64 values (as preAlps_OperatorSystemResiduals forms it) -- then the new rows and columns of
+ * G from Xh^T w and x^T w, read through the operator's row map, then the columns into the ring; the evicted rows and
+ * columns of G are overwritten on the host.  More columns than the capacity: the last `capacity` are kept.
+ *   Refresh: at the first project or append after preAlps_OperatorUpdateValues, G is formed again from Xh and the new
+ * matrix (one product over the live columns; stat "hist_gram_refreshes").
+ *   preAlps_ECGSolveSystemHistory: project, preAlps_ECGSolveSystem from that x0, append the returned x (nothing is
+ * appended when the start already met every threshold: *n_hist = 0, no iteration).  With an empty history, or rank 0,
+ * it is preAlps_ECGSolveSystem with x0 = NULL bit for bit; otherwise preAlps_ECGSolveSystem with the projected x0 bit
+ * for bit.  sys_res0 (may be NULL): the start residuals in the metric of the test; *rank (may be NULL): the columns the
+ * projection kept.  Every other argument is preAlps_ECGSolveSystem's.
+ *   preAlps_SolutionHistoryCreate(capacity), 1 .. 16, replaces an existing history; preAlps_SolutionHistoryFree (also
+ * done by preAlps_OperatorFree; no error without a history); preAlps_SolutionHistoryClear empties the ring.
+ *   flags: PREALPS_SYS_DEVICE (the arrays are device pointers, read and written on the library stream) and, for the
+ * solve, PREALPS_SYS_STOP_ORIGINAL.  Every entry returns after the library stream has drained.
+ *   Stats: "hist_capacity", "hist_columns", "hist_bytes", "hist_appends" (columns), "hist_projections",
+ * "hist_last_rank", "hist_gram_refreshes", "hist_values_epoch"; all 0 without a history.
+ *   Refused, naming the entry and leaving the history as it was: no operator, no history, a capacity out of range;
+ * nrhs < 1 or > 16; a leading dimension below N, a NULL array, a non-finite x or b; plan-only mode; more than one
+ * process or a preAlps_hip_loopback shard (the dots would need an all-reduce, the product the halo exchange);
+ * everything preAlps_ECGSolveSystem refuses; a G whose largest diagonal entry is not positive and finite. */
+int preAlps_SolutionHistoryCreate(int capacity);
+int preAlps_SolutionHistoryFree(void);
+int preAlps_SolutionHistoryClear(void);
+int preAlps_SolutionHistoryAppend(int nrhs, const double* x, int ldx, int flags);
+int preAlps_SolutionHistoryProject(int nrhs, const double* b, int ldb, double* x0, int ldx0, int flags, double rtol,
+                                   int* rank, double* captured);
+int preAlps_ECGSolveSystemHistory(preAlps_ECG_t* ecg, int nrhs, const double* b, int ldb, double* x, int ldx,
+                                  int flags, double rtol, double* res_hist, int* bs_hist, double* sys_hist,
+                                  double* sys_normb, double* sys_res, double* sys_res0, int* rank, int max_hist,
+                                  int* n_hist);
 /* 1 / 0: the two driver loops above and below replay each half of an iteration from a HIP graph
  * captured on its first passes (default: off, or PREALPS_ECG_GRAPH; plain launches measured faster). */
 void preAlps_hip_graphs(int on);

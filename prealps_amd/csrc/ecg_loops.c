@@ -333,14 +333,22 @@ static int system_args_refused(const char* who, const preAlps_ECG_t* ecg, int nr
   if (ldx < op->N) return pa_fail_at(who, "ldx = %d is smaller than the %d rows of the matrix", ldx, op->N);
   return 0;
 }
+/* sys_res0 (may be NULL): the start residuals in the metric of the test (x0 == NULL: ||b_j||); who: the entry the
+ * refusals of the arguments name (solution_history.c calls this for preAlps_ECGSolveSystemHistory) */
+int pa_ecg_solve_system_from(const char* who, preAlps_ECG_t* ecg, int nrhs, const double* b, int ldb, const double* x0,
+                             int ldx0, double* x, int ldx, int flags, double* res_hist, int* bs_hist, double* sys_hist,
+                             double* sys_normb, double* sys_res, double* sys_res0, int max_hist, int* n_hist) {
+  if (system_args_refused(who, ecg, nrhs, b, ldb, x0, ldx0, x, ldx, flags)) return 1;
+  const sys_in_t in = {b, ldb, x0, ldx0, (flags & PREALPS_SYS_DEVICE) != 0, (flags & PREALPS_SYS_STOP_ORIGINAL) != 0, 0, ldx};
+  const multi_args_t mu = {.nrhs = nrhs, .sys_hist = sys_hist, .sys_normb = sys_normb, .sys_res0 = sys_res0, .sys = &in,
+                           .sys_x = x, .sys_ldx = ldx, .sys_res = sys_res};
+  return solve_in_own_loop(ecg, NULL, NULL, res_hist, bs_hist, max_hist, n_hist, &mu);
+}
 int preAlps_ECGSolveSystem(preAlps_ECG_t* ecg, int nrhs, const double* b, int ldb, const double* x0, int ldx0, double* x,
                            int ldx, int flags, double* res_hist, int* bs_hist, double* sys_hist, double* sys_normb,
                            double* sys_res, int max_hist, int* n_hist) {
-  if (system_args_refused(__func__, ecg, nrhs, b, ldb, x0, ldx0, x, ldx, flags)) return 1;
-  const sys_in_t in = {b, ldb, x0, ldx0, (flags & PREALPS_SYS_DEVICE) != 0, (flags & PREALPS_SYS_STOP_ORIGINAL) != 0, 0, ldx};
-  const multi_args_t mu = {.nrhs = nrhs, .sys_hist = sys_hist, .sys_normb = sys_normb, .sys = &in, .sys_x = x, .sys_ldx = ldx,
-                           .sys_res = sys_res};
-  return solve_in_own_loop(ecg, NULL, NULL, res_hist, bs_hist, max_hist, n_hist, &mu);
+  return pa_ecg_solve_system_from(__func__, ecg, nrhs, b, ldb, x0, ldx0, x, ldx, flags, res_hist, bs_hist, sys_hist,
+                                  sys_normb, sys_res, NULL, max_hist, n_hist);
 }
 
 /* preAlps_ECGSolveSystem with a tracker of the energy-norm drops (ecg_energy.h) that this entry owns: the loop hands it to

@@ -193,6 +193,10 @@ void pa_ecg_x_owed(ecg_priv_t* pv);                        /* a row pass skipped
 int pa_ecg_flush_x(preAlps_ECG_t* ecg, ecg_priv_t* pv);    /* pays what is owed to X, if anything (pa_k_flush_x) */
 int pa_ecg_energy_enable(preAlps_ECG_t* ecg, ecg_priv_t* pv, pa_energy_t* tracker, int stop);
 int pa_ecg_queue_energy(preAlps_ECG_t* ecg, ecg_priv_t* pv);   /* the drops of the update just queued; nothing without a tracker */
+/* ---- ecg_loops.c ---- */
+int pa_ecg_solve_system_from(const char* who, preAlps_ECG_t* ecg, int nrhs, const double* b, int ldb, const double* x0,
+                             int ldx0, double* x, int ldx, int flags, double* res_hist, int* bs_hist, double* sys_hist,
+                             double* sys_normb, double* sys_res, double* sys_res0, int max_hist, int* n_hist);
 /* ---- ecg_start.c ---- */
 int pa_ecg_start_systems(const char* who, preAlps_ECG_t* ecg, int nrhs, const double* rhs, int ldrhs,
                          const double* x0, int ldx0, int* rci_request, const sys_in_t* sys);

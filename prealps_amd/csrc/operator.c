@@ -133,6 +133,7 @@ static void free_plan(pa_operator_t* o) {
 
 void preAlps_OperatorFree(void) {
   pa_operator_t* o = &g_op;
+  preAlps_SolutionHistoryFree();      /* (the history belongs to the operator) */
   free_plan(o);
   free(o->lcol); free(o->src); free(o->src_rowptr);
   free(o->info.rowPos); free(o->info.perm); free(o->info.scaling);
@@ -898,6 +899,7 @@ int preAlps_hip_set_operator_precision(int bits) {
 
 /* ------------------------------------------------------ new values in place ---- */
 int pa_operator_values_epoch(void) { return g_op.values_epoch; }
+int pa_operator_plan_stride(void) { return g_op.plan_ts; }
 int pa_operator_build_count(void) { return g_op_builds; }
 /* the last update: host seconds of scaling vector + panel, host seconds of the copy of the panel values to the
  * device, device seconds of k_plan_set_values between two events; the seconds the last value map took (cut, upload) */
@@ -1268,6 +1270,7 @@ int preAlps_hip_get_stat(const char* key, double* value) {
   else if (!strcmp(key, "bj_g4_last_bits")) *value = pa_bj_g4_last(1);
   else if (!strcmp(key, "bj_g4_last_pipelined")) *value = pa_bj_g4_last(2);
   else if (!strcmp(key, "bj_g4_last_paired")) *value = pa_bj_g4_last(3);
+  else if (!pa_hist_stat(key, value)) return 0;
   else return pa_bj_update_stat(key, value);
   return 0;
 }

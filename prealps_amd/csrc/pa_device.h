@@ -290,6 +290,20 @@ int pa_k_group_norms(const double* rtr_partials, int nblk, int ts, int k, int s,
 int pa_k_group_norms_ride(const double* rtr_partials, int nblk, int ts, int k, int s, const int* info, double* buf);
 /* sol[i + j*ld] = sum of X[i][c] over the columns of system j, ascending c (pa_k_rowsum per system). */
 int pa_k_rowsum_groups(int m, int ts, int k, int s, const double* X, double* sol, int ld);
+/* ---- the solution history (history.hip; preAlps_SolutionHistory*) ----
+ * Xh: n x cap, column major (ldh), logical column i (0: the oldest) in slot (head + i) % cap; K <= cap live columns.
+ * pa_k_hist_dots: out (K x q, ld K, device) = Xh^T W, W column major (ldw); pa_k_hist_dots_mapped: W is a panel of
+ * the iteration (m rows of ts doubles) in the operator's internal space, Xh is read at row src[r] and W(r, :) divided
+ * by dl[r].  part: pa_k_hist_part_doubles() doubles of scratch; the partial sums are folded in block order (no atomics:
+ * two launches agree in bits).  pa_k_hist_combine: X0 (n x q, ldx0) = Xh c, c K x q (ld K) on the device, the oldest
+ * column first.  K, q outside 1 .. 16, a ring that does not hold K, a leading dimension below n: refused. */
+size_t pa_k_hist_part_doubles(void);
+int pa_k_hist_dots(int n, int K, int q, const double* Xh, int ldh, int head, int cap, const double* W, int ldw,
+                   double* part, double* out);
+int pa_k_hist_dots_mapped(int m, int K, int q, const double* Xh, int ldh, int head, int cap, const int* src,
+                          const double* dl, const double* Wp, int ts, double* part, double* out);
+int pa_k_hist_combine(int n, int K, int q, const double* Xh, int ldh, int head, int cap, const double* c, double* X0,
+                      int ldx0);
 /* ---- the caller's own system (dense_system.hip; preAlps_ECGSolveSystem) ----
  * Local row i is the caller's row src[i] with scaling factor dl[i] (1.0 when the operator is unscaled); src, dl: m
  * entries on the device.  B, X0, Xout: device, column major, k columns, rows in the caller's order, ld >= m.

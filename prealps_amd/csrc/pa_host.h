@@ -95,6 +95,8 @@ int pa_operator_system_map(const int** src, const double** dl);
 /* The product of preAlps_BlockOperator on the fp64 values of the matrix whatever storage is in force
  * (preAlps_hip_set_operator_precision): what forms R0 = b - A x0.  It neither serves nor ends a Gram request. */
 int pa_operator_apply_exact(CPLM_Mat_Dense_t* X, CPLM_Mat_Dense_t* AX);
+int pa_operator_plan_stride(void);    /* the panel stride the SpMM plan in use was cut for (0: none yet) */
+int pa_hist_stat(const char* key, double* value);   /* the stats of the solution history by name (solution_history.c); 1: unknown key */
 int pa_operator_plan_epoch(void);     /* + 1 per change of what a product launches or reads (plan cut, repack, fp32 copy) */
 int pa_operator_values_epoch(void);   /* 0 after a build, + 1 per preAlps_OperatorUpdateValues */
 int pa_bj_values_epoch(void);         /* that count at the last preAlps_BlockJacobiCreate / preAlps_BlockJacobiUpdateValues */

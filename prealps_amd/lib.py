@@ -91,6 +91,8 @@ EXPORTS = [
     "preAlps_BlockJacobiSetCoarseSpace", "preAlps_BlockJacobiClearCoarseSpace",
     "preAlps_BlockJacobiGetCoarseAggregates",
     "preAlps_hip_set_operator_precision", "preAlps_ECGSolveSystemRefined", "preAlps_ECGSolveSystemEnergy",
+    "preAlps_SolutionHistoryCreate", "preAlps_SolutionHistoryFree", "preAlps_SolutionHistoryClear",
+    "preAlps_SolutionHistoryAppend", "preAlps_SolutionHistoryProject", "preAlps_ECGSolveSystemHistory",
 ]
 
 _lib = None
@@ -141,6 +143,14 @@ def load():
                                                C.c_int, C.c_double, C.c_int, pd, pi, pd, pd, pd, pd, pd, pd, pi, pd,
                                                C.c_int, pi]
     L.preAlps_OperatorSystemResiduals.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, pd, pd]
+    L.preAlps_SolutionHistoryCreate.argtypes = [C.c_int]
+    L.preAlps_SolutionHistoryFree.argtypes = []
+    L.preAlps_SolutionHistoryClear.argtypes = []
+    L.preAlps_SolutionHistoryAppend.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int]
+    L.preAlps_SolutionHistoryProject.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                                                 pi, pd]
+    L.preAlps_ECGSolveSystemHistory.argtypes = [pe, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                C.c_double, pd, pi, pd, pd, pd, pd, pi, C.c_int, pi]
     L.preAlps_OperatorGetScalingPtr.argtypes = [C.POINTER(pd), pi]
     L.preAlps_OperatorGetOwnedRows.argtypes = [C.POINTER(pi), pi]
     L._preAlps_ECGReset.argtypes = [pe, pd, pi]

@@ -59,6 +59,10 @@ class EcgResult:
     err_est: np.ndarray = None
     err_iter: np.ndarray = None
     energy_norm: np.ndarray = None
+    # solve_system(history=True) (preAlps_ECGSolveSystemHistory): the columns of the history the projection kept, and
+    # the start residuals of the projected start in the metric of the test (||b_j|| where nothing was kept)
+    history_rank: int = None
+    sys_res0: np.ndarray = None
 
 
 class DistributedHooks:
@@ -469,7 +473,7 @@ class EcgProblem:
         column given as a vector).  Raises ValueError."""
         def is_tensor(a):
             return type(a).__module__.split(".")[0] == "torch" and hasattr(a, "data_ptr")
-        arrays = [("b" if what == "solve_system" else "B", b)] + ([] if x0 is None else [(x0_name, x0)])
+        arrays = [("b" if what == "solve_system" else "X" if what == "history_append" else "B", b)] + ([] if x0 is None else [(x0_name, x0)])
         kinds = {"device" if (is_tensor(a) and a.is_cuda) else "host" for _, a in arrays}
         if len(kinds) > 1:
             raise ValueError("%s: host and device arguments are mixed (%s): pass NumPy arrays or float64 CUDA tensors, "
@@ -513,7 +517,8 @@ class EcgProblem:
             torch.cuda.current_stream().synchronize()
 
     def solve_system(self, b, t, x0=None, stop="original", ortho_alg=ORTHODIR, bs_red=NO_BS_RED, tol=1e-5,
-                     max_iter=1000, refine=False, max_passes=4, energy=False, tau=0.1, dmin=4):
+                     max_iter=1000, refine=False, max_passes=4, energy=False, tau=0.1, dmin=4, history=False,
+                     history_rtol=None):
         """preAlps_ECGSolveSystem: A x = b as the caller stated it -- the rows in the order of the matrix this problem
         was built from, the values in its units -- for one system (b of shape (N,)) or k systems (b of shape (N, k), t a
         multiple of k), with or without a starting value x0 of the same shape.
@@ -542,7 +547,15 @@ class EcgProblem:
         heuristic, not a guarantee.  energy=True forms the drops and the estimates under any stop, at one small launch
         per iteration and without changing a bit of x or of the histories.  Either way the result gains drop_hist,
         err_hist, err_est, err_iter and energy_norm; sys_res / sys_hist are then in the scaled metric under stop="energy".
-        Not with refine=True."""
+        Not with refine=True.
+        history=True (preAlps_ECGSolveSystemHistory; enable_history first): the solve starts from the projection of the
+        solution onto the span of the solutions in the history -- the closest element in the energy norm -- and its x
+        is appended afterwards; the result gains history_rank and sys_res0.  With an empty history it is this method
+        without x0 bit for bit, otherwise this method with x0 = history_project(b)[0] bit for bit.  Not together with
+        x0=, refine=True or the energy estimate: ValueError."""
+        if history and (x0 is not None or refine or energy or stop == "energy"):
+            raise ValueError("solve_system: history=True takes its start from the history and runs the plain solve: not "
+                             "together with x0=, refine=True, energy=True or stop='energy'")
         if stop not in ("original", "scaled", "energy"):
             raise ValueError("stop must be 'original', 'scaled' or 'energy', not %r" % (stop,))
         energy = bool(energy) or stop == "energy"
@@ -610,6 +623,14 @@ class EcgProblem:
             extra = dict(drop_hist=np.ascontiguousarray(drops[:n_]),
                          err_hist=np.ascontiguousarray(errs[:n_ + 1]),
                          err_est=err_est, err_iter=err_iter, energy_norm=e_norm)
+        elif history:
+            rank, res0 = C.c_int(), np.zeros(k)
+            check(L.preAlps_ECGSolveSystemHistory(C.byref(e), k, pb, ldb, px, ldx, flags,
+                                                  0.0 if history_rtol is None else float(history_rtol), _pd(res), _pi(bs),
+                                                  _pd(sys_hist), _pd(sys_normb), _pd(sys_end), _pd(res0), C.byref(rank),
+                                                  cap, C.byref(nh)),
+                  "preAlps_ECGSolveSystemHistory")
+            extra = dict(history_rank=rank.value, sys_res0=res0)
         else:
             check(L.preAlps_ECGSolveSystem(C.byref(e), k, pb, ldb, px0, ldx0, px, ldx, flags, _pd(res), _pi(bs),
                                            _pd(sys_hist), _pd(sys_normb), _pd(sys_end), cap, C.byref(nh)),
@@ -647,6 +668,61 @@ class EcgProblem:
         check(L.preAlps_OperatorSystemResiduals(k, pb, ldb, px, ldx, flags, _pd(res), _pd(normb)),
               "preAlps_OperatorSystemResiduals")
         return res[:k], normb[:k]
+
+    def enable_history(self, capacity=8):
+        """preAlps_SolutionHistoryCreate: keep the last `capacity` (1 .. 16) solutions of solve_system(history=True) /
+        history_append on the device, in the caller's order and units; replaces an existing history."""
+        check(self.L.preAlps_SolutionHistoryCreate(int(capacity)), "preAlps_SolutionHistoryCreate")
+
+    def disable_history(self):
+        """preAlps_SolutionHistoryFree (close() does it too)."""
+        check(self.L.preAlps_SolutionHistoryFree(), "preAlps_SolutionHistoryFree")
+
+    def clear_history(self):
+        """preAlps_SolutionHistoryClear: an empty ring of the same capacity."""
+        check(self.L.preAlps_SolutionHistoryClear(), "preAlps_SolutionHistoryClear")
+
+    def history_project(self, B, rtol=None):
+        """preAlps_SolutionHistoryProject: (x0, rank, captured) for B of shape (N,) or (N, k), k <= 16 (a NumPy array or
+        a float64 CUDA tensor; x0 comes back as the same kind and shape): x0 = the element of the span of the history
+        closest to the solution of A x = B in the energy norm, rank = the columns the pivoted Cholesky kept (pivots
+        above rtol, default 1e-12, on the unit-diagonal Gram matrix), captured[j] = ||x0_j||_A^2."""
+        kind, k, vector = self._system_args("history_project", B, None, "x0")
+        N = self.N
+        flags = 0
+        if kind == "device":
+            import torch
+            flags = _l.SYS_DEVICE
+            bk, pb, ldb = self._device_columns(B)
+            x0 = torch.empty((k, N), dtype=torch.float64, device=bk.device).t()
+            px = x0.data_ptr()
+            self._order_torch_stream()
+        else:
+            bk = np.asfortranarray(np.asarray(B, dtype=np.float64).reshape(N, k))
+            pb, ldb = bk.ctypes.data, max(N, 1)
+            x0 = np.zeros((N, k), order="F")
+            px = x0.ctypes.data
+        rank, captured = C.c_int(), np.zeros(max(k, 1))
+        check(self.L.preAlps_SolutionHistoryProject(k, pb, ldb, px, max(N, 1), flags, 0.0 if rtol is None else float(rtol),
+                                                    C.byref(rank), _pd(captured)),
+              "preAlps_SolutionHistoryProject")
+        if vector:
+            x0 = x0[:, 0].contiguous() if kind == "device" else np.ascontiguousarray(x0[:, 0])
+        return x0, rank.value, captured[:k]
+
+    def history_append(self, X):
+        """preAlps_SolutionHistoryAppend: the columns of X (shape (N,) or (N, k), k <= 16; NumPy or a float64 CUDA
+        tensor) enter the ring, the oldest columns leave a full one."""
+        kind, k, _ = self._system_args("history_append", X, None, "x0")
+        N = self.N
+        if kind == "device":
+            xk, px, ldx = self._device_columns(X)
+            self._order_torch_stream()
+        else:
+            xk = np.asfortranarray(np.asarray(X, dtype=np.float64).reshape(N, k))
+            px, ldx = xk.ctypes.data, max(N, 1)
+        check(self.L.preAlps_SolutionHistoryAppend(k, px, ldx, _l.SYS_DEVICE if kind == "device" else 0),
+              "preAlps_SolutionHistoryAppend")
 
     def reference_rhs(self):
         rhs = np.zeros(self.m)
