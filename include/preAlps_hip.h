@@ -513,9 +513,18 @@ int preAlps_ECGSolveSystemEnergy(preAlps_ECG_t* ecg, int nrhs, const double* b, 
  *   Stats: "hist_capacity", "hist_columns", "hist_bytes", "hist_appends" (columns), "hist_projections",
  * "hist_last_rank", "hist_gram_refreshes", "hist_values_epoch"; all 0 without a history.
  *   Refused, naming the entry and leaving the history as it was: no operator, no history, a capacity out of range;
- * nrhs < 1 or > 16; a leading dimension below N, a NULL array, a non-finite x or b; plan-only mode; more than one
- * process or a preAlps_hip_loopback shard (the dots would need an all-reduce, the product the halo exchange);
- * everything preAlps_ECGSolveSystem refuses; a G whose largest diagonal entry is not positive and finite. */
+ * nrhs < 1 or > 16; a leading dimension below N, a NULL array, a non-finite x or b; plan-only mode;
+ * everything preAlps_ECGSolveSystem refuses; a G whose largest diagonal entry is not positive and finite.
+ *   Several processes (or a preAlps_hip_loopback shard): the entries are collective.  The ring holds the m rows this
+ * process owns ("hist_bytes" = 8 m capacity); b, x and x0 stay the caller's global arrays (N rows, ld >= N) on every
+ * process, read and written at the owned rows alone -- the other rows of x0 are left untouched, so x0 buffers that start
+ * as zeros sum to the whole start vector.  The local sums of an entry travel in one all-reduce (a projection costs 1,
+ * an append and a refresh of G 2 each: the agreement ahead of the distributed product, then the sums), so rank, captured,
+ * G and every counter are the same on every process.  A wrong leading dimension, a NULL array or a failed allocation on
+ * one process makes every process return nonzero, a NaN or Inf in one process's rows makes every process refuse with
+ * the "not finite" message, and the history stays as it was on all of them.  Refused on every process: an operator
+ * built for another process group than the current one; more than one process without an all-reduce hook
+ * (preAlps_hip_set_comm, preAlps_hip_rccl_init, an MPI launcher). */
 int preAlps_SolutionHistoryCreate(int capacity);
 int preAlps_SolutionHistoryFree(void);
 int preAlps_SolutionHistoryClear(void);

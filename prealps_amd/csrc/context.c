@@ -210,6 +210,7 @@ int preAlps_hip_loopback(int rank, int size) {
   return 0;
 }
 int pa_comm_is_loopback(void) { return g_allreduce == loop_allreduce; }
+int pa_comm_has_allreduce(void) { return g_allreduce != NULL; }
 
 /* Round-trip check of whatever hooks are installed: sum of (rank+1) over the ranks, and a
  * ring exchange (send our rank to rank+1, receive from rank-1).  0 = both came back right. */

@@ -155,3 +155,22 @@ int pa_hist_project(const pa_hist_t* h, int q, const double* g, double rtol, dou
   }
   return PA_HIST_OK;
 }
+
+int pa_hist_red_layout(int entry, int K, int q, pa_hist_red_t* l) {
+  if (!l || K < 0 || K > PA_HIST_MAX) return PA_HIST_BAD_ARGS;
+  pa_hist_red_t n;
+  const int sums = 1, first = sums + PA_HIST_MAX, second = first + PA_HIST_MAX * PA_HIST_MAX;
+  if (entry == PA_HIST_RED_REFRESH) {
+    if (K < 1) return PA_HIST_BAD_ARGS;
+    n.off_a = first; n.rows_a = K; n.cols_a = K; n.off_b = second; n.rows_b = 0; n.cols_b = 0; n.words = second;
+  } else {
+    if (q < 1 || q > PA_HIST_MAX) return PA_HIST_BAD_ARGS;
+    if (entry == PA_HIST_RED_PROJECT) {
+      n.off_a = sums; n.rows_a = 1; n.cols_a = q; n.off_b = first; n.rows_b = K; n.cols_b = q; n.words = second;
+    } else if (entry == PA_HIST_RED_APPEND) {
+      n.off_a = first; n.rows_a = K; n.cols_a = q; n.off_b = second; n.rows_b = q; n.cols_b = q; n.words = PA_HIST_RED_WORDS;
+    } else return PA_HIST_BAD_ARGS;
+  }
+  *l = n;
+  return PA_HIST_OK;
+}

@@ -65,4 +65,21 @@ int pa_hist_factor_solve(int K, const double* Gs, int q, const double* gs, doubl
  * <= 0: the default; c K x q (ld K, logical order), *rank, captured[q].  An empty history gives rank 0. */
 int pa_hist_project(const pa_hist_t* h, int q, const double* g, double rtol, double* c, int* rank, double* captured);
 
+/* Several processes: the buffer one all-reduce of an entry carries, PA_HIST_RED_WORDS = 1 + 16 + 256 + 256 doubles on
+ * the device: [failed | 16 sums | a first block of 256 | a second block of 256].  Word 0 is nonzero where a process
+ * failed.  A block is column major with the leading dimension of its rows and starts where its region starts:
+ *   PA_HIST_RED_PROJECT  a = the q sums b_j^2 (1 x q) at word 1,  b = g = Xl^T b (K x q) at word 17, K >= 0; 273 words
+ *   PA_HIST_RED_APPEND   a = DO = Xl^T W (K x q) at word 17, K >= 0,  b = DN = Xn^T W (q x q) at word 273; 529 words
+ *   PA_HIST_RED_REFRESH  a = G = Xl^T W (K x K) at word 17, K >= 1,  b empty; q is not looked at; 273 words
+ * words: what the all-reduce carries, word 0 included.  Neither the place of entry (i, j) nor the word count of an
+ * entry depends on q (nor, for j = 0, on anything but i): a library that sums the processes' shares chunk by chunk of
+ * the buffer (the ring of gloo or RCCL) adds them in an order that the place and the count decide, so column j of a
+ * projection of q columns has the bits of the same column projected with fewer or more beside it.  The words an
+ * entry does not fill are zero (the glue clears the buffer first).  PA_HIST_BAD_ARGS, and l untouched, for an unknown
+ * entry or a K or q outside 0 / 1 .. PA_HIST_MAX. */
+#define PA_HIST_RED_WORDS (1 + 16 + 256 + 256)
+enum { PA_HIST_RED_PROJECT = 0, PA_HIST_RED_APPEND = 1, PA_HIST_RED_REFRESH = 2 };
+typedef struct { int off_a, rows_a, cols_a, off_b, rows_b, cols_b, words; } pa_hist_red_t;
+int pa_hist_red_layout(int entry, int K, int q, pa_hist_red_t* l);
+
 #endif

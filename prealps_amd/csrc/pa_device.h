@@ -304,6 +304,27 @@ int pa_k_hist_dots_mapped(int m, int K, int q, const double* Xh, int ldh, int he
                           const double* dl, const double* Wp, int ts, double* part, double* out);
 int pa_k_hist_combine(int n, int K, int q, const double* Xh, int ldh, int head, int cap, const double* c, double* X0,
                       int ldx0);
+/* Several processes: the ring Xl holds the m rows this process owns (m x cap, ldh >= m); local row r is the caller's row
+ * src[r] < N, and the caller's arrays (N rows, ld >= N) are touched at the owned rows alone.  part:
+ * pa_k_hist_owned_part_doubles() doubles; red: the buffer one all-reduce carries (ecg_history.h: PA_HIST_RED_WORDS
+ * doubles, the offsets from pa_hist_red_layout); a fold writes its two blocks and leaves word 0 and the rest alone.
+ * pa_k_hist_gather: out(r, slots[j]) = a[src[r] + j lda] (slots on the host; NULL: column j to slot j; a negative slot
+ * is skipped; every slot < cap).  pa_k_hist_ring_scaled: out(r, i) = Xl(r, i) / dl[r], i < K by physical slot.
+ * pa_k_hist_project_owned: red[off_g ..) = Xl^T b[src] (K x q, ld K, logical order) and red[off_bb ..) = the q sums
+ * b_j^2 over the owned rows, one launch and one fold; K = 0 is an empty ring.  pa_k_hist_gram_owned: W the panel (ts
+ * doubles per row) divided by dl; red[off_do ..) = Xl^T W (K x q) and, with Xn (m x q in local row order, ldn),
+ * red[off_dn ..) = Xn^T W (q x q).  pa_k_hist_combine_owned: X0[src[r] + j ldx0] = (Xl c)(r, j), the terms of
+ * pa_k_hist_combine. */
+size_t pa_k_hist_owned_part_doubles(void);
+int pa_k_hist_gather(int m, int N, int q, const int* src, const double* a, int lda, const int* slots, int cap, double* out,
+                     int ldo);
+int pa_k_hist_ring_scaled(int m, int K, const double* Xl, int ldh, const double* dl, double* out, int ldo);
+int pa_k_hist_project_owned(int m, int N, int K, int q, const double* Xl, int ldh, int head, int cap, const int* src,
+                            const double* b, int ldb, double* part, double* red, int off_bb, int off_g);
+int pa_k_hist_gram_owned(int m, int K, int q, const double* Xl, int ldh, int head, int cap, const double* Xn, int ldn,
+                         const double* dl, const double* Wp, int ts, double* part, double* red, int off_do, int off_dn);
+int pa_k_hist_combine_owned(int m, int N, int K, int q, const double* Xl, int ldh, int head, int cap, const double* c,
+                            const int* src, double* X0, int ldx0);
 /* ---- the caller's own system (dense_system.hip; preAlps_ECGSolveSystem) ----
  * Local row i is the caller's row src[i] with scaling factor dl[i] (1.0 when the operator is unscaled); src, dl: m
  * entries on the device.  B, X0, Xout: device, column major, k columns, rows in the caller's order, ld >= m.

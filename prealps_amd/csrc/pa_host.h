@@ -33,6 +33,7 @@ int pa_host_threads(void);            /* OpenMP threads worth starting here (cgr
 int pa_world_rank(void);
 int pa_world_size(void);
 int pa_comm_is_loopback(void);
+int pa_comm_has_allreduce(void);      /* 1: an all-reduce hook is installed (preAlps_hip_set_comm, RCCL, MPI, loopback) */
 /* sum a device buffer over the processes (no-op for one process) */
 int pa_allreduce(double* dev_buf, int count);
 long long pa_allreduce_count(void);   /* calls of the all-reduce hook so far */

@@ -551,8 +551,10 @@ class EcgProblem:
         history=True (preAlps_ECGSolveSystemHistory; enable_history first): the solve starts from the projection of the
         solution onto the span of the solutions in the history -- the closest element in the energy norm -- and its x
         is appended afterwards; the result gains history_rank and sys_res0.  With an empty history it is this method
-        without x0 bit for bit, otherwise this method with x0 = history_project(b)[0] bit for bit.  Not together with
-        x0=, refine=True or the energy estimate: ValueError."""
+        without x0 bit for bit, otherwise this method with x0 = history_project(b)[0] bit for bit (on a distributed=True
+        or shard= problem: collective, on the same ranks, with x0 = the SUM all-reduce of history_project(b)[0]; the
+        history holds the rows each rank owns, history_rank is the same on every rank).  Not together with x0=,
+        refine=True or the energy estimate: ValueError."""
         if history and (x0 is not None or refine or energy or stop == "energy"):
             raise ValueError("solve_system: history=True takes its start from the history and runs the plain solve: not "
                              "together with x0=, refine=True, energy=True or stop='energy'")
@@ -671,7 +673,10 @@ class EcgProblem:
 
     def enable_history(self, capacity=8):
         """preAlps_SolutionHistoryCreate: keep the last `capacity` (1 .. 16) solutions of solve_system(history=True) /
-        history_append on the device, in the caller's order and units; replaces an existing history."""
+        history_append on the device, in the caller's order and units; replaces an existing history.
+        On a distributed=True or shard= problem the call is collective: every rank keeps the rows it owns (owned_rows) of
+        every solution, m x capacity doubles (stat("hist_bytes") = 8 m capacity), and either every rank holds a ring
+        afterwards or none has changed anything."""
         check(self.L.preAlps_SolutionHistoryCreate(int(capacity)), "preAlps_SolutionHistoryCreate")
 
     def disable_history(self):
@@ -679,14 +684,19 @@ class EcgProblem:
         check(self.L.preAlps_SolutionHistoryFree(), "preAlps_SolutionHistoryFree")
 
     def clear_history(self):
-        """preAlps_SolutionHistoryClear: an empty ring of the same capacity."""
+        """preAlps_SolutionHistoryClear: an empty ring of the same capacity.  On a distributed=True or shard= problem
+        every rank calls it (no collective is needed: the ring's bookkeeping is the same on all of them)."""
         check(self.L.preAlps_SolutionHistoryClear(), "preAlps_SolutionHistoryClear")
 
     def history_project(self, B, rtol=None):
         """preAlps_SolutionHistoryProject: (x0, rank, captured) for B of shape (N,) or (N, k), k <= 16 (a NumPy array or
         a float64 CUDA tensor; x0 comes back as the same kind and shape): x0 = the element of the span of the history
         closest to the solution of A x = B in the energy norm, rank = the columns the pivoted Cholesky kept (pivots
-        above rtol, default 1e-12, on the unit-diagonal Gram matrix), captured[j] = ||x0_j||_A^2."""
+        above rtol, default 1e-12, on the unit-diagonal Gram matrix), captured[j] = ||x0_j||_A^2.
+        On a distributed=True or shard= problem the call is collective (one all-reduce): B keeps the global shape on every
+        rank and is read at the rows the rank owns; x0 holds those rows and zeros in every other, so a SUM all-reduce of
+        x0 over the ranks is the whole start vector (what solve_system(x0=) takes); rank and captured are global and
+        have the same bits on every rank.  A NaN or Inf in a row one rank owns raises on every rank."""
         kind, k, vector = self._system_args("history_project", B, None, "x0")
         N = self.N
         flags = 0
@@ -694,7 +704,9 @@ class EcgProblem:
             import torch
             flags = _l.SYS_DEVICE
             bk, pb, ldb = self._device_columns(B)
-            x0 = torch.empty((k, N), dtype=torch.float64, device=bk.device).t()
+            # several ranks: zeros in the rows this rank does not own (the library writes the owned rows and no other)
+            alloc = torch.zeros if self.comm_kind != "none" else torch.empty
+            x0 = alloc((k, N), dtype=torch.float64, device=bk.device).t()
             px = x0.data_ptr()
             self._order_torch_stream()
         else:
@@ -712,7 +724,11 @@ class EcgProblem:
 
     def history_append(self, X):
         """preAlps_SolutionHistoryAppend: the columns of X (shape (N,) or (N, k), k <= 16; NumPy or a float64 CUDA
-        tensor) enter the ring, the oldest columns leave a full one."""
+        tensor) enter the ring, the oldest columns leave a full one.
+        On a distributed=True or shard= problem the call is collective (two all-reduces and one halo exchange): X keeps
+        the global shape and is read at the rows this rank owns alone, so the x of solve_system can be appended as it
+        came back, without assembling it.  A NaN or Inf in a row one rank owns raises on every rank, and the history
+        is then unchanged on all of them."""
         kind, k, _ = self._system_args("history_append", X, None, "x0")
         N = self.N
         if kind == "device":
